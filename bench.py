@@ -53,6 +53,28 @@ def open_scene(fray_amd, name, W, H, over):
     return s
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(folder, outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: writes every host array of `outputs` ({name: [H, W, ...] array}) as folder/<name>.npy, float32 kept, anything else as
+    float64 (hit ids are int32, exact in float64).  When the arrays would take more than `limit` bytes together, every one is cut to the same
+    pixels, a fixed seeded sample (sorted flat pixel indices, written beside them as pixel_index.npy), so two runs stay comparable file for file."""
+    import numpy as np
+    arrs = {k: np.ascontiguousarray(v if v.dtype == np.float32 else v.astype(np.float64)) for k, v in outputs.items()}
+    H, W = next(iter(arrs.values())).shape[:2]
+    if sum(a.nbytes for a in arrs.values()) > limit:
+        per_pixel = sum(a.nbytes for a in arrs.values()) // (H * W) + 8
+        n = (limit - 4096) // per_pixel             # 4096: headroom for the .npy headers
+        idx = np.sort(np.random.default_rng(0).choice(H * W, n, replace=False))
+        arrs = {k: a.reshape(H * W, *a.shape[2:])[idx] for k, a in arrs.items()}
+        arrs["pixel_index"] = idx.astype(np.float64)
+    os.makedirs(folder, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(folder, k + ".npy"), a)
+    return sorted(arrs)
+
+
 def usable_cores():
     """Cores this process may actually use: affinity mask, capped by a cgroup CPU quota if there is one."""
     try:
@@ -210,7 +232,11 @@ def main():
     ap.add_argument("--no-contracted", action="store_true", help="skip the second timed region that renders the same frame with option fp_contract = 1 (profiling passes: one arithmetic per run)")
     ap.add_argument("--library-gather", action="store_true", help="with --backend gloo: still exchange through frayhip_gather_buckets (the library binds whatever RCCL "
                     "FRAYHIP_RCCL_LIBRARY names -- on a one-GPU box the test suite's loopback stand-in, since RCCL itself refuses two ranks on one device)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed (the frame; hit ids and distances "
+                    "for a primary-ray workload) as DIR/<name>.npy in float32 / float64, at most 64 MB in all (beyond that a fixed seeded sample of pixels)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -349,6 +375,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t[0])
     ms_per_step = elapsed * 1e3 / args.steps
+    # the last timed step's outputs, taken now: the passes below render into the same buffers
+    if args.dump_outputs and rank == 0:
+        outs = {"hit_id": ids, "hit_dist": dists} if mode == abi.MODE_PRIMARY_ID else {"frame": frame}
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in outs.items()})
 
     check = None
     if args.check and world > 1 and mode == abi.MODE_PRIMARY_ID:

@@ -1,5 +1,5 @@
 import os, sys, time
-sys.path.insert(0, '/root/repo' if os.path.isdir('/root/repo') else '.')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, fray_amd
 fray_amd.lib.frayhip_init(0)
 s = fray_amd.Scene.parseScene(os.path.join(os.path.dirname(fray_amd.__file__), '..', 'scenes', 'hw10', 'bokeh.fray'))
