@@ -1,5 +1,5 @@
 """File-only front end over the C ABI (the reference's main() opens an SDL window instead,
-src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --height H --spp N]"""
+src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --height H --spp N] [--progress] [--time-limit SECONDS]"""
 import argparse
 import sys
 import time
@@ -16,6 +16,9 @@ def main(argv=None):
     ap.add_argument("--spp", type=int, help="pathsPerPixel (gi scenes) / numSamples (dof scenes)")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--progress", action="store_true", help="print one line per finished batch of samples")
+    ap.add_argument("--time-limit", type=float, metavar="SECONDS",
+                    help="cancel the frame once this much time has passed and write what is finished (an exact frame of fewer samples per pixel)")
     a = ap.parse_args(argv)
     s = Scene.parseScene(a.scene)
     if a.width:
@@ -29,8 +32,25 @@ def main(argv=None):
             s.camera.numDOFSamples = a.spp
     s.beginRender(a.device)
     t0 = time.time()
-    img, st = s.render(seed=a.seed)
-    print("Render took %.2fs (%d x %d, %d spp, kernels %.1f ms)" % (time.time() - t0, img.shape[1], img.shape[0], s.samples_per_pixel(), st["ms_kernels"]))
+    if a.progress or a.time_limit is not None:
+        def progress(info):
+            if a.progress:
+                print("%s%d / %d spp, batch %d / %d, %.1f ms" % ("done: " if info["final"] else "", info["samples_done"], info["samples_total"],
+                                                                info["batches_done"], info["batches_total"], info["ms_elapsed"]), flush=True)
+            if a.time_limit is not None and not info["final"] and info["ms_elapsed"] >= a.time_limit * 1000.0:
+                cancel_at.append(info["ms_elapsed"])
+                return True
+            return False
+        cancel_at = []
+        img, st = s.render(seed=a.seed, progress=progress)
+        spp = st["samples_done"]
+        if st["cancelled"]:
+            print("Time limit of %gs reached: the frame holds %d of %d samples per pixel (finished %.1f ms after the cancel)"
+                  % (a.time_limit, spp, s.samples_per_pixel(), st["ms_total"] - cancel_at[0]))
+    else:
+        img, st = s.render(seed=a.seed)
+        spp = s.samples_per_pixel()
+    print("Render took %.2fs (%d x %d, %d spp, kernels %.1f ms)" % (time.time() - t0, img.shape[1], img.shape[0], spp, st["ms_kernels"]))
     rc = lib.frayhip_save_bmp(a.output.encode(), img.ctypes.data, img.shape[1], img.shape[0])
     if rc:
         print(lib.frayhip_last_error().decode(), file=sys.stderr)

@@ -10,7 +10,7 @@ P = C.POINTER
 
 ABI_VERSION = 3
 
-OK, E_ARG, E_PARSE, E_NODEVICE, E_UNSUPPORTED, E_NOMEM, E_HIP = 0, -1, -2, -3, -4, -5, -6
+OK, E_ARG, E_PARSE, E_NODEVICE, E_UNSUPPORTED, E_NOMEM, E_HIP, E_CANCELLED = 0, -1, -2, -3, -4, -5, -6, -7
 GEOM_PLANE, GEOM_SPHERE, GEOM_CUBE, GEOM_MESH, GEOM_CSG = range(5)
 TEX_CHECKER, TEX_BITMAP, TEX_BUMP, TEX_FRESNEL = range(4)
 SHADER_CONST, SHADER_LAMBERT, SHADER_PHONG, SHADER_REFL, SHADER_REFR, SHADER_LAYERED = range(6)
@@ -143,13 +143,30 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class Progress(C.Structure):
+    _fields_ = [("samples_done", i32), ("samples_total", i32), ("batches_done", i32), ("batches_total", i32),
+                ("ms_elapsed", f64), ("preview", i32), ("final", i32), ("rgb", P(f32))]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "rgb"}
+
+
+# int (*fn)(void* user, const frayhip_progress*)
+PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, P(Progress))
+
+
+class Progressive(C.Structure):
+    _fields_ = [("fn", PROGRESS_FN), ("user", C.c_void_p), ("preview_ms", f64)]
+
+
 STRUCTS = {"frayhip_transform": Transform, "frayhip_geom_ref": GeomRef, "frayhip_node": Node,
            "frayhip_plane": Plane, "frayhip_sphere": Sphere, "frayhip_cube": Cube,
            "frayhip_csg": Csg, "frayhip_triangle": Triangle, "frayhip_kdnode": KDNode,
            "frayhip_mesh": Mesh, "frayhip_texture": Texture, "frayhip_shader": Shader,
            "frayhip_layer": Layer, "frayhip_light": Light, "frayhip_camera": Camera,
            "frayhip_settings": Settings, "frayhip_environment": Environment,
-           "frayhip_scene_desc": SceneDesc, "frayhip_frame": Frame, "frayhip_stats": Stats}
+           "frayhip_scene_desc": SceneDesc, "frayhip_frame": Frame, "frayhip_stats": Stats,
+           "frayhip_progress": Progress, "frayhip_progressive": Progressive}
 
 # Every symbol include/frayhip.h declares: name -> (restype, argtypes)
 VP = C.c_void_p
@@ -165,6 +182,8 @@ SYMBOLS = {
     "frayhip_scene_get_option": (C.c_int, [VP, C.c_char_p, P(i64)]),
     "frayhip_render": (C.c_int, [VP, P(Frame), VP, VP, VP, P(Stats)]),
     "frayhip_render_device": (C.c_int, [VP, P(Frame), VP, VP, VP, VP, P(Stats)]),
+    "frayhip_render_progressive": (C.c_int, [VP, P(Frame), P(Progressive), VP, VP, VP, P(Stats)]),
+    "frayhip_render_device_progressive": (C.c_int, [VP, P(Frame), P(Progressive), VP, VP, VP, VP, P(Stats)]),
     "frayhip_bucket_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "frayhip_pack_buckets_device": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP]),
     "frayhip_unpack_buckets_device": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP]),

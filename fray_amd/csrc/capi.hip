@@ -773,6 +773,7 @@ int frayhip_scene_get_option(frayhip_scene* s, const char* name, int64_t* value)
 int frayhip_scene_set_option(frayhip_scene* s, const char* name, int64_t value)
 {
     if (!s || !name) { set_error("frayhip_scene_set_option: null argument"); return FRAYHIP_E_ARG; }
+    if (s->rendering) { set_error("frayhip_scene_set_option: the scene is rendering a frame"); return FRAYHIP_E_ARG; }
     const std::string n(name);
     if (n == "pt_lanes") {
         if (value < 1 || value > FRAY_PT_LANES) { set_error("frayhip_scene_set_option: pt_lanes must be 1.." + std::to_string(FRAY_PT_LANES)); return FRAYHIP_E_ARG; }
@@ -800,6 +801,7 @@ int frayhip_scene_set_option(frayhip_scene* s, const char* name, int64_t value)
 int frayhip_scene_set_view(frayhip_scene* s, const frayhip_camera* camera, const frayhip_settings* settings)
 {
     if (!s) { set_error("frayhip_scene_set_view: null scene"); return FRAYHIP_E_ARG; }
+    if (s->rendering) { set_error("frayhip_scene_set_view: the scene is rendering a frame"); return FRAYHIP_E_ARG; }
     if (settings && (settings->frameWidth <= 0 || settings->frameHeight <= 0)) { set_error("frayhip_scene_set_view: bad frame size"); return FRAYHIP_E_ARG; }
     if (camera) s->camera = *camera;
     if (settings) s->settings = *settings;
@@ -826,21 +828,32 @@ void frayhip_scene_destroy(frayhip_scene* s)
 }
 
 
-int frayhip_render_device(frayhip_scene* s, const frayhip_frame* f, float* d_rgb, int32_t* d_hit_id, double* d_hit_dist, void* hip_stream,
-                          frayhip_stats* st)
+namespace {
+// Every render entry: the kernel flag word the scene needs, and the per-scene `rendering` flag that turns a render, a change or a destruction of the
+// scene from inside a progress callback into FRAYHIP_E_ARG.
+int render_dispatch(frayhip_scene* s, const frayhip_frame* f, float* d_rgb, int32_t* d_hit_id, double* d_hit_dist, hipStream_t stream, frayhip_stats* st,
+                    const frayhip_detail::Progress* prog)
 {
-    if (!s || !f) { set_error("frayhip_render_device: null argument"); return FRAYHIP_E_ARG; }
-    hipStream_t stream = (hipStream_t)hip_stream;
+    if (s->rendering) { set_error("frayhip_render: the scene is already rendering a frame (a render call from inside a progress callback?)"); return FRAYHIP_E_ARG; }
+    struct Busy { frayhip_scene* s; Busy(frayhip_scene* x) : s(x) { s->rendering = true; } ~Busy() { s->rendering = false; } } busy(s);
     const bool stats = (f->flags & FRAYHIP_FRAME_STATS) != 0;
-    if (s->extGeometry) return stats ? frayhip_detail::render_impl<3>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st) : frayhip_detail::render_impl<2>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st);
-    if (s->kdMeshes) return stats ? frayhip_detail::render_impl<5>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st) : frayhip_detail::render_impl<4>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st);
-    if (s->textured) return stats ? frayhip_detail::render_impl<9>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st) : frayhip_detail::render_impl<8>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st);
-    return stats ? frayhip_detail::render_impl<1>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st) : frayhip_detail::render_impl<0>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st);
+    if (s->extGeometry) return stats ? frayhip_detail::render_impl<3>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog) : frayhip_detail::render_impl<2>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog);
+    if (s->kdMeshes) return stats ? frayhip_detail::render_impl<5>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog) : frayhip_detail::render_impl<4>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog);
+    if (s->textured) return stats ? frayhip_detail::render_impl<9>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog) : frayhip_detail::render_impl<8>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog);
+    return stats ? frayhip_detail::render_impl<1>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog) : frayhip_detail::render_impl<0>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog);
 }
 
-int frayhip_render(frayhip_scene* s, const frayhip_frame* f, float* rgb, int32_t* hit_id, double* hit_dist, frayhip_stats* st)
+int check_progressive(const frayhip_progressive* p, const char* who)
 {
-    if (!s || !f) { set_error("frayhip_render: null argument"); return FRAYHIP_E_ARG; }
+    if (!p) { set_error(std::string(who) + ": null progress request"); return FRAYHIP_E_ARG; }
+    if (std::isnan(p->preview_ms)) { set_error(std::string(who) + ": preview_ms is NaN"); return FRAYHIP_E_ARG; }
+    return FRAYHIP_OK;
+}
+
+// The host entries: device buffers for the call, the caller's frame uploaded first when the call renders a subset of the buckets, the results
+// copied back.  A progressive frame's rgb is already on the host (render_impl copies it before the final callback), also when it was cancelled.
+int render_host(frayhip_scene* s, const frayhip_frame* f, const frayhip_progressive* p, float* rgb, int32_t* hit_id, double* hit_dist, frayhip_stats* st)
+{
     const size_t n = (size_t)s->settings.frameWidth * s->settings.frameHeight;
     float* d_rgb = nullptr; int32_t* d_id = nullptr; double* d_dist = nullptr;
     int rc = FRAYHIP_OK;
@@ -859,15 +872,47 @@ int frayhip_render(frayhip_scene* s, const frayhip_frame* f, float* rgb, int32_t
         if (d_dist && ce == hipSuccess) ce = hipMemcpy(d_dist, hit_dist, n * 8, hipMemcpyHostToDevice);
     }
     if (ce != hipSuccess) { set_error(std::string("frayhip_render: host-to-device copy failed: ") + hipGetErrorString(ce)); cleanup(); return frayhip_detail::hip_error_code(ce); }
-    rc = frayhip_render_device(s, f, d_rgb, d_id, d_dist, nullptr, st);
-    if (!rc) {
-        if (d_rgb && ce == hipSuccess) ce = hipMemcpy(rgb, d_rgb, n * 12, hipMemcpyDeviceToHost);
+    const frayhip_detail::Progress prog{p, rgb};
+    rc = render_dispatch(s, f, d_rgb, d_id, d_dist, nullptr, st, p ? &prog : nullptr);
+    if (!rc || rc == FRAYHIP_E_CANCELLED) {
+        if (d_rgb && !p && ce == hipSuccess) ce = hipMemcpy(rgb, d_rgb, n * 12, hipMemcpyDeviceToHost);
         if (d_id && ce == hipSuccess) ce = hipMemcpy(hit_id, d_id, n * 4, hipMemcpyDeviceToHost);
         if (d_dist && ce == hipSuccess) ce = hipMemcpy(hit_dist, d_dist, n * 8, hipMemcpyDeviceToHost);
         if (ce != hipSuccess) { set_error(std::string("frayhip_render: device-to-host copy failed: ") + hipGetErrorString(ce)); rc = frayhip_detail::hip_error_code(ce); }
     }
     cleanup();
     return rc;
+}
+}  // namespace
+
+int frayhip_render_device(frayhip_scene* s, const frayhip_frame* f, float* d_rgb, int32_t* d_hit_id, double* d_hit_dist, void* hip_stream,
+                          frayhip_stats* st)
+{
+    if (!s || !f) { set_error("frayhip_render_device: null argument"); return FRAYHIP_E_ARG; }
+    return render_dispatch(s, f, d_rgb, d_hit_id, d_hit_dist, (hipStream_t)hip_stream, st, nullptr);
+}
+
+int frayhip_render(frayhip_scene* s, const frayhip_frame* f, float* rgb, int32_t* hit_id, double* hit_dist, frayhip_stats* st)
+{
+    if (!s || !f) { set_error("frayhip_render: null argument"); return FRAYHIP_E_ARG; }
+    return render_host(s, f, nullptr, rgb, hit_id, hit_dist, st);
+}
+
+int frayhip_render_device_progressive(frayhip_scene* s, const frayhip_frame* f, const frayhip_progressive* p, float* d_rgb, int32_t* d_hit_id,
+                                      double* d_hit_dist, void* hip_stream, frayhip_stats* st)
+{
+    if (const int rc = check_progressive(p, "frayhip_render_device_progressive")) return rc;
+    if (!s || !f) { set_error("frayhip_render_device_progressive: null argument"); return FRAYHIP_E_ARG; }
+    const frayhip_detail::Progress prog{p, nullptr};
+    return render_dispatch(s, f, d_rgb, d_hit_id, d_hit_dist, (hipStream_t)hip_stream, st, &prog);
+}
+
+int frayhip_render_progressive(frayhip_scene* s, const frayhip_frame* f, const frayhip_progressive* p, float* rgb, int32_t* hit_id, double* hit_dist,
+                               frayhip_stats* st)
+{
+    if (const int rc = check_progressive(p, "frayhip_render_progressive")) return rc;
+    if (!s || !f) { set_error("frayhip_render_progressive: null argument"); return FRAYHIP_E_ARG; }
+    return render_host(s, f, p, rgb, hit_id, hit_dist, st);
 }
 
 __global__ void k_debug_rng(uint32_t seed, int n, float* f, double* d, int32_t* it, int hi, uint32_t* work)

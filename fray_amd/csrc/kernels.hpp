@@ -16,6 +16,7 @@
 //   k_pt_shadow    visible() for every queued next-event segment: the sample's radiance term of this bounce
 //   k_pt_resolve_terms   mono: per pixel, every sample's terms added innermost first and the samples in sample order (the reference's FP32 order)
 //   k_pt_fold, k_pt_resolve   stereo (two passes share the term lists): a sample's radiance from its terms; then the per-pixel sum and the anaglyph blend
+//   k_resolve_mean the running sum of the first s samples / s: a progressive frame's preview, a cancelled frame's result
 //   k_pack         bucket-major <-> row-major copies for the multi-GPU gather (dev_pack.hpp)
 #pragma once
 #include "dev_shade.hpp"
@@ -1517,5 +1518,20 @@ static __global__ __launch_bounds__(256) void k_pt_resolve(DFrame F, DCamera C, 
         } else {
             sum[si] = a.r; sum[si + 1] = a.g; sum[si + 2] = a.b;
         }
+    }
+}
+
+// A progressive frame's preview, or a cancelled frame's result: vfb[y][x] = (the running per-pixel sum of the first s samples) / s.  Every resolve
+// above (k_pt_resolve, k_pt_resolve_terms; mono, stereo -- whose sum already holds the blended eyes -- and the Whitted batches) leaves the same
+// layout between batches, and divides the same way at the last one, so the result is the frame of s samples per pixel, bit for bit.
+static __global__ __launch_bounds__(256) void k_resolve_mean(DFrame F, int nItems, int s, const float* __restrict__ sum, float* __restrict__ rgb)
+{
+    for (int item = blockIdx.x * blockDim.x + threadIdx.x; item < nItems; item += gridDim.x * blockDim.x) {
+        int x, y;
+        if (!item_pixel(F, item, x, y)) continue;
+        const size_t si = (size_t)item * 3;
+        const C3 a = c3(sum[si], sum[si + 1], sum[si + 2]) / (float)s;
+        const size_t p = ((size_t)y * F.W + x) * 3;
+        rgb[p] = a.r; rgb[p + 1] = a.g; rgb[p + 2] = a.b;
     }
 }

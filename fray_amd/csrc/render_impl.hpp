@@ -42,10 +42,103 @@ size_t shadow_bytes(size_t n)
     auto r = [](size_t b) { return (b + 255) / 256 * 256; };
     return 6 * r(n * 8) + 4 * r(n * 4) + r(n);
 }
+
+// The batch loop of every integrator that renders a frame in batches of `chunk` samples per pixel.  trace(j) enqueues batch j up to its resolve,
+// resolve(j) the resolve (the ordered per-pixel sum) and whatever belongs after it; both return 0 or an error code.  laneOf(j) is the stream
+// batch j runs on; evOrder (the path tracer's evResolved, one per lane) is recorded after every resolve.
+// Without a progress request the batches are enqueued back to back, as they always were.  With one (include/frayhip.h, progressive frames):
+//   - at most `window` (= lanes) batches are traced ahead of the batch being reported, so the device keeps working while the host waits;
+//   - batch r's resolve is enqueued only after batch r - 1's callback returned, and a preview (k_resolve_mean, plus the copy to the host frame
+//     for the host entry) follows it on the same lane, before the event the host waits on and the next resolve waits on is recorded: `sum` and
+//     the frame are not touched again until the host has seen them, and evOrder[r % window] is re-recorded only after that;
+//   - a cancel stops the tracing; the batches already traced are resolved in order (no more callbacks), and finish() writes their mean.
+struct Batches {
+    frayhip_scene* sc = nullptr;
+    const Progress* prog = nullptr;
+    std::chrono::steady_clock::time_point t0;
+    DFrame F{};
+    int nItems = 0;
+    float* d_rgb = nullptr;
+    size_t frameBytes = 0;            // the host entry's whole-frame copy
+    float* sum = nullptr;             // the running per-pixel sum between batches
+    int total = 1, chunk = 1, nBatches = 1, window = 1;
+    int resolved = 1, samplesDone = 1;
+    bool cancelled = false;
+    double lastPreviewMs = 0;
+
+    double elapsed_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+    int call(bool preview, bool final, const float* rgb) const
+    {
+        if (!prog->req->fn) return 0;
+        frayhip_progress p{};
+        p.samples_done = samplesDone; p.samples_total = total;
+        p.batches_done = resolved; p.batches_total = nBatches;
+        p.ms_elapsed = elapsed_ms();
+        p.preview = preview ? 1 : 0; p.final = final ? 1 : 0;
+        p.rgb = rgb;
+        return prog->req->fn(prog->req->user, &p);
+    }
+    bool preview_due()
+    {
+        const double every = prog->req->preview_ms;
+        if (every < 0 || !d_rgb) return false;
+        const double now = elapsed_ms();
+        if (every > 0 && now - lastPreviewMs < every) return false;
+        lastPreviewMs = now;
+        return true;
+    }
+    template <class Trace, class Resolve, class LaneOf>
+    int run(Trace&& trace, Resolve&& resolve, LaneOf&& laneOf, hipEvent_t* evOrder)
+    {
+        if (!prog) {
+            for (int j = 0; j < nBatches; j++) {
+                if (const int rc = trace(j)) return rc;
+                if (const int rc = resolve(j)) return rc;
+                if (evOrder) HIP_TRY(hipEventRecord(evOrder[j % window], laneOf(j)));
+            }
+            resolved = nBatches; samplesDone = total;
+            return FRAYHIP_OK;
+        }
+        resolved = samplesDone = 0;
+        int traced = 0;
+        for (; traced < std::min(window, nBatches); traced++)
+            if (const int rc = trace(traced)) return rc;
+        for (int r = 0; r < traced; r++) {
+            if (const int rc = resolve(r)) return rc;
+            const hipStream_t ls = laneOf(r);
+            const bool last = r == nBatches - 1;
+            const bool preview = !last && !cancelled && preview_due();
+            if (preview) {
+                hipLaunchKernelGGL(k_resolve_mean, dim3(grid_for(nItems)), dim3(256), 0, ls, F, nItems, std::min(total, (r + 1) * chunk), (const float*)sum, d_rgb);
+                if (prog->h_rgb) HIP_TRY(hipMemcpyAsync(prog->h_rgb, d_rgb, frameBytes, hipMemcpyDeviceToHost, ls));
+            }
+            hipEvent_t ev = evOrder ? evOrder[r % window] : sc->evResolved[0];
+            HIP_TRY(hipEventRecord(ev, ls));
+            if (!cancelled && traced < nBatches) {
+                if (const int rc = trace(traced)) return rc;
+                traced++;
+            }
+            resolved = r + 1;
+            samplesDone = std::min(total, (r + 1) * chunk);
+            if (cancelled || last) continue;
+            HIP_TRY(hipEventSynchronize(ev));
+            HIP_TRY(hipGetLastError());
+            if (call(preview, false, preview ? (prog->h_rgb ? prog->h_rgb : d_rgb) : nullptr)) cancelled = true;
+        }
+        return FRAYHIP_OK;
+    }
+    // a cancelled frame: the mean of the resolved samples, on `stream` after every lane has been joined into it
+    bool cut_short() const { return prog && samplesDone < total; }
+    void finish(hipStream_t stream) const
+    {
+        if (cut_short() && d_rgb && sum && samplesDone > 0)
+            hipLaunchKernelGGL(k_resolve_mean, dim3(grid_for(nItems)), dim3(256), 0, stream, F, nItems, samplesDone, (const float*)sum, d_rgb);
+    }
+};
 }  // namespace
 
 template <int ST>
-int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t* d_id, double* d_dist, hipStream_t stream, frayhip_stats* st)
+int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t* d_id, double* d_dist, hipStream_t stream, frayhip_stats* st, const Progress* prog)
 {
     const auto t0 = std::chrono::steady_clock::now();
     const frayhip_settings& set = sc->settings;
@@ -71,6 +164,10 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
     S.gi = set.gi;
     S.saturation = set.saturation;
     DCamera C = camera_begin_frame(sc->camera, W, H);
+    Batches B;
+    B.sc = sc; B.prog = prog; B.t0 = t0; B.F = F; B.nItems = nItems; B.d_rgb = d_rgb;
+    B.frameBytes = (size_t)W * H * 12;
+    B.total = B.samplesDone = f->mode == FRAYHIP_MODE_PRIMARY_ID ? 1 : spp;          // one-shot paths (k_primary, k_black) report one batch
 
     // An early (error) return below must not leave work in flight on the side lanes' streams, which the caller cannot see: whatever
     // was enqueued is drained before the call returns.
@@ -145,8 +242,8 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                     SPB.cok = take(kids);
                     SPB.cdraws = take(kids);
                 }
-                for (int s0 = 0; s0 < spp; s0 += chunk) {
-                    const int cn = std::min(chunk, spp - s0);
+                auto trace = [&](int j) -> int {
+                    const int s0 = j * chunk, cn = std::min(chunk, spp - s0);
                     if (s0 > 0) HIP_TRY(hipMemsetAsync(cursors, 0, 3 * sizeof(DCursors), stream));  // the tile cursors of the previous batch
                     if (fan > 0) HIP_TRY(hipMemsetAsync(SPB.counters, 0, s0 == 0 ? 256 : 32, stream));
                     hipLaunchKernelGGL(k_seed, dim3(seed_grid(((size_t)nItems * cn + FRAY_SEED_CHAINS - 1) / FRAY_SEED_CHAINS)), dim3(256), 0, stream, F, nItems, s0, cn, x397);
@@ -180,9 +277,16 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                     }
                     HIP_TRY(hipEventRecord(b, stream));
                     nTraceEvents += 2;
+                    return FRAYHIP_OK;
+                };
+                auto resolve = [&](int j) -> int {
+                    const int s0 = j * chunk, cn = std::min(chunk, spp - s0);
                     if (spp > 1) hipLaunchKernelGGL(k_pt_resolve, dim3(grid_for(nItems)), dim3(256), 0, stream, F, C, set.saturation, nItems, s0, cn, rad, (const float*)nullptr, sum, d_rgb);
                     if (fan > 0) hipLaunchKernelGGL(k_add4, dim3(1), dim3(64), 0, stream, SPB.counters, (unsigned long long*)(SPB.counters + 8));       // the frame's totals over its batches
-                }
+                    return FRAYHIP_OK;
+                };
+                B.sum = sum; B.chunk = chunk; B.nBatches = (spp + chunk - 1) / chunk;
+                if (const int rc = B.run(trace, resolve, [&](int) { return stream; }, nullptr)) return rc;
                 fanTotals = fan > 0 ? (const unsigned long long*)(SPB.counters + 8) : nullptr;
             } else if (nItems > 0) {
                 // Wavefront Whitted (no recursive shader in the scene): batches of `chunk` samples per pixel through
@@ -231,8 +335,9 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 const bool fusedShade = T <= sc->fusedWhittedMax && !kd_variant(ST);
                 sc->lastWhittedPath = fusedShade ? 2 : 1;
                 const bool draws = F.jitter || sc->camera.dof || sc->lightDraws;
-                for (int s0 = 0; s0 < spp; s0 += chunk) {
-                    const int cn = std::min(chunk, spp - s0);
+                const bool direct = fusedShade && spp == 1 && !stereo;      // the fused kernel writes the pixel itself
+                auto trace = [&](int j) -> int {
+                    const int s0 = j * chunk, cn = std::min(chunk, spp - s0);
                     const size_t bs = (size_t)nItems * cn, bN = bs * eyes;      // this batch's slots: arrays are used with stride bN
                     if (!fusedShade || draws)
                         hipLaunchKernelGGL(k_seed, dim3(seed_grid((bs + FRAY_SEED_CHAINS - 1) / FRAY_SEED_CHAINS)), dim3(256), 0, stream, F, nItems, s0, cn, x397);
@@ -244,13 +349,11 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                     // tiles are claimed when a wave gets at least 16 of them, walked with a fixed stride otherwise (next_tile, kernels.hpp)
                     const bool claimShade = bs / 64 >= (size_t)grid * 4 * 16;
                     if (fusedShade) {
-                        const bool direct = spp == 1 && !stereo;
                         hipLaunchKernelGGL((k_wh_shade<ST, true>), dim3(grid), dim3(256), 0, stream,
                                            WhShadeArgs{S, C, F, nItems, s0, cn, Q, mtWork, draws ? x397 : nullptr, sc->d_stats, claimShade ? cursors : nullptr, radL, radR, direct ? d_rgb : nullptr});
                         HIP_TRY(hipEventRecord(eb, stream));
                         nTraceEvents += 2;
-                        if (!direct) hipLaunchKernelGGL(k_pt_resolve, dim3(grid_for(nItems)), dim3(256), 0, stream, F, C, set.saturation, nItems, s0, cn, radL, stereo ? radR : nullptr, sum, d_rgb);
-                        continue;
+                        return FRAYHIP_OK;
                     }
                     const int gridVis = persistent_grid(bN * (size_t)T, anyhit_waves(ST));
                     const bool claimVis = (bN * (size_t)T) / 64 >= (size_t)gridVis * 4 * 16;
@@ -262,8 +365,15 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                     HIP_TRY(hipEventRecord(ed, stream));
                     nShadowEvents += 2;
                     hipLaunchKernelGGL(k_wh_gather, dim3(grid_for(bN)), dim3(256), 0, stream, S, Q, bN, bs, radL, radR);
-                    hipLaunchKernelGGL(k_pt_resolve, dim3(grid_for(nItems)), dim3(256), 0, stream, F, C, set.saturation, nItems, s0, cn, radL, stereo ? radR : nullptr, sum, d_rgb);
-                }
+                    return FRAYHIP_OK;
+                };
+                auto resolve = [&](int j) -> int {
+                    const int s0 = j * chunk, cn = std::min(chunk, spp - s0);
+                    if (!direct) hipLaunchKernelGGL(k_pt_resolve, dim3(grid_for(nItems)), dim3(256), 0, stream, F, C, set.saturation, nItems, s0, cn, radL, stereo ? radR : nullptr, sum, d_rgb);
+                    return FRAYHIP_OK;
+                };
+                B.sum = sum; B.chunk = chunk; B.nBatches = (spp + chunk - 1) / chunk;
+                if (const int rc = B.run(trace, resolve, [&](int) { return stream; }, nullptr)) return rc;
             }
         } else if (nItems > 0) {
             if (set.maxTraceDepth > 2000) { set_error("frayhip_render: maxTraceDepth above 2000 is not supported (three launches per level and batch)"); return FRAYHIP_E_UNSUPPORTED; }
@@ -377,9 +487,8 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
             const int nBounce = set.maxTraceDepth + 2;
             HIP_TRY(hipEventRecord(sc->evLaneStart, stream));               // the side lanes start after whatever precedes this frame on the caller's stream
             for (int k = 1; k < nLanes; k++) HIP_TRY(hipStreamWaitEvent(sc->laneStream[k], sc->evLaneStart, 0));
-            int batch = 0;
-            for (int s0 = 0; s0 < spp; s0 += chunk, batch++) {
-                const int cn = std::min(chunk, spp - s0);
+            auto trace = [&](int batch) -> int {
+                const int s0 = batch * chunk, cn = std::min(chunk, spp - s0);
                 Lane& L = lane[batch % nLanes];
                 hipStream_t ls = L.stream;
                 hipLaunchKernelGGL(k_seed, dim3(seed_grid(((size_t)nItems * cn + FRAY_SEED_CHAINS - 1) / FRAY_SEED_CHAINS)), dim3(256), 0, ls, F, nItems, s0, cn, L.x397);
@@ -435,19 +544,28 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                     if (stereo) hipLaunchKernelGGL(k_pt_fold, dim3(grid_for((size_t)nItems * cn)), dim3(256), 0, ls, TermBuf{L.terms, L.termCount, (uint32_t)nPaths, 0},
                                                    (uint32_t)((size_t)nItems * cn), rad);
                 }
-                // the running per-pixel sum takes the batches in sample order
+                return FRAYHIP_OK;
+            };
+            auto resolve = [&](int batch) -> int {
+                const int s0 = batch * chunk, cn = std::min(chunk, spp - s0);
+                Lane& L = lane[batch % nLanes];
+                hipStream_t ls = L.stream;
+                // the running per-pixel sum takes the batches in sample order (evResolved is recorded after each resolve, Batches::run)
                 if (batch > 0 && nLanes > 1) HIP_TRY(hipStreamWaitEvent(ls, sc->evResolved[(batch - 1) % nLanes], 0));
                 if (stereo) hipLaunchKernelGGL(k_pt_resolve, dim3(grid_for(nItems)), dim3(256), 0, ls, F, C, set.saturation, nItems, s0, cn, L.sampleRad, L.sampleRadR, sum, d_rgb);
                 else hipLaunchKernelGGL(k_pt_resolve_terms, dim3(grid_for(nItems)), dim3(256), 0, ls, F, nItems, s0, cn, TermBuf{L.terms, L.termCount, (uint32_t)nPaths, 0}, sum, d_rgb);
-                HIP_TRY(hipEventRecord(sc->evResolved[batch % nLanes], ls));
-            }
-            // the last resolve follows every earlier one, and each resolve is the last launch of its batch
-            if (nLanes > 1) HIP_TRY(hipStreamWaitEvent(stream, sc->evResolved[(batch - 1) % nLanes], 0));
+                return FRAYHIP_OK;
+            };
+            B.sum = sum; B.chunk = chunk; B.nBatches = nBatches; B.window = nLanes;
+            if (const int rc = B.run(trace, resolve, [&](int batch) { return lane[batch % nLanes].stream; }, sc->evResolved)) return rc;
+            // the last resolve follows every earlier one, and each resolve is the last launch of its batch (a cancelled frame: of the batches traced)
+            if (nLanes > 1) HIP_TRY(hipStreamWaitEvent(stream, sc->evResolved[(B.resolved - 1) % nLanes], 0));
         }
     } else {
         set_error("frayhip_render: unknown mode");
         return FRAYHIP_E_ARG;
     }
+    B.finish(stream);                       // a cancelled progressive frame: the mean of the samples resolved
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sc->evB, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -536,6 +654,13 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
         o.alg_flops_shadow = flops(b);
         o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         *st = o;
+    }
+    if (prog) {
+        // the final call: the finished (or cancelled) frame, copied to the host frame first for the host entry
+        const bool rgbOut = f->mode == FRAYHIP_MODE_RENDER;
+        if (rgbOut && prog->h_rgb) HIP_TRY(hipMemcpy(prog->h_rgb, d_rgb, B.frameBytes, hipMemcpyDeviceToHost));
+        (void)B.call(rgbOut, true, rgbOut ? (prog->h_rgb ? prog->h_rgb : d_rgb) : nullptr);
+        if (B.cut_short()) { set_error("frayhip_render: cancelled by the progress callback"); return FRAYHIP_E_CANCELLED; }
     }
     return FRAYHIP_OK;
 }

@@ -78,6 +78,7 @@ struct frayhip_scene {
     // allocation fails all the same -- never re-derived per frame (other processes' allocations would move the batch size, and every growth of the
     // workspace is a hipFree + hipMalloc in the middle of a run).  0 = not computed yet.
     size_t ptBudgetEff = 0;
+    bool rendering = false;           // a frame of this scene is being rendered: set by every render entry, so that a progress callback cannot render or change it
 };
 
 namespace frayhip_detail {
@@ -95,18 +96,25 @@ int bounce_grid(size_t n, bool alone);
 int grid_for(size_t n);
 int seed_grid(size_t n);
 int ensure_work(frayhip_scene* sc, size_t bytes);
+
+// A progressive frame's request (frayhip_render_progressive / frayhip_render_device_progressive): the caller's callback and preview interval;
+// h_rgb is the host frame the host entry copies every preview (and the final frame) to before it calls back, nullptr for the device entry.
+struct Progress {
+    const frayhip_progressive* req;
+    float* h_rgb;
+};
 // i-th event of a pool, created on first use; nullptr (and the error text set) when hipEventCreate fails
 hipEvent_t pool_event(std::vector<hipEvent_t>& pool, size_t i);
 
 template <int ST>
-int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t* d_id, double* d_dist, hipStream_t stream, frayhip_stats* st);
-extern template int render_impl<0>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*);
-extern template int render_impl<1>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*);
-extern template int render_impl<2>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*);
-extern template int render_impl<3>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*);
-extern template int render_impl<4>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*);
-extern template int render_impl<5>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*);
-extern template int render_impl<8>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*);
-extern template int render_impl<9>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*);
+int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t* d_id, double* d_dist, hipStream_t stream, frayhip_stats* st, const Progress* prog);
+extern template int render_impl<0>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
+extern template int render_impl<1>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
+extern template int render_impl<2>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
+extern template int render_impl<3>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
+extern template int render_impl<4>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
+extern template int render_impl<5>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
+extern template int render_impl<8>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
+extern template int render_impl<9>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
 
 }  // namespace frayhip_detail

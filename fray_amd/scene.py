@@ -48,6 +48,45 @@ def render_info():
     return {"library": _LIB_PATH, "abi_version": lib.frayhip_abi_version()}
 
 
+class _ProgressRun:
+    """The Python side of a progressive call: turns every callback into an info dict for `progress`, keeps an exception raised inside it
+    (ctypes would print it and carry on) and cancels the frame instead, and re-raises it after the call."""
+
+    def __init__(self, progress, frame_view):
+        self.progress, self.frame_view = progress, frame_view
+        self.error, self.samples_done = None, 0
+
+    def __call__(self, _user, p):
+        try:
+            p = p.contents
+            self.samples_done = p.samples_done
+            info = p.as_dict()
+            if p.preview and p.rgb:
+                info.update(self.frame_view(p))
+            return 1 if self.progress(info) else 0
+        except BaseException as e:          # noqa: B902 -- KeyboardInterrupt too: it cancels the frame, then propagates
+            if self.error is None:
+                self.error = e
+            return 1
+
+    def finish(self, rc, st):
+        if self.error is not None:
+            raise self.error
+        if rc not in (abi.OK, abi.E_CANCELLED):
+            _check(rc)
+        d = st.as_dict()
+        d["samples_done"] = self.samples_done
+        d["cancelled"] = rc == abi.E_CANCELLED
+        return d
+
+
+def _progress_request(progress, preview_ms, frame_view):
+    run = _ProgressRun(progress, frame_view)
+    req = abi.Progressive(fn=abi.PROGRESS_FN(run), user=None, preview_ms=float(preview_ms))
+    req._run = run                          # the request keeps the ctypes callback object alive for the call
+    return req, run
+
+
 class Scene:
     """`Scene scene` of the reference (scene.h:280-299).
 
@@ -132,15 +171,26 @@ class Scene:
         if not self._dev:
             raise FrayError(abi.E_ARG, "Scene.beginRender() has not been called")
 
-    def render(self, seed=42, bucket_first=0, bucket_stride=1, spp_chunk=0, stats=False, out=None):
-        """Full render; returns (vfb, stats dict)."""
+    def render(self, seed=42, bucket_first=0, bucket_stride=1, spp_chunk=0, stats=False, out=None, progress=None, preview_ms=-1):
+        """Full render; returns (vfb, stats dict).
+
+        progress(info): called after batches of the frame (frayhip_render_progressive, include/frayhip.h): info holds samples_done,
+        samples_total, batches_done, batches_total, ms_elapsed, preview and final; when info["preview"] is set, info["image"] is a
+        float32 [H, W, 3] view of the frame's running mean, valid during the call only.  preview_ms < 0: no previews, 0: one per batch,
+        > 0: at most one per that many milliseconds.  A truthy return cancels the frame; so does an exception, which is raised again
+        once the call has returned.  With a progress callback the stats dict also holds "samples_done" and "cancelled": a cancelled
+        frame is returned, not raised -- vfb is the exact frame of its samples_done samples per pixel."""
         self._need_dev()
         W, H = self.frame_size
         rgb = out if out is not None else np.zeros((H, W, 3), np.float32)
         st = abi.Stats()
         fr = self._frame(abi.MODE_RENDER, seed, bucket_first, bucket_stride, spp_chunk, stats)
-        _check(lib.frayhip_render(self._dev, C.byref(fr), rgb.ctypes.data, None, None, C.byref(st)))
-        return rgb, st.as_dict()
+        if progress is None:
+            _check(lib.frayhip_render(self._dev, C.byref(fr), rgb.ctypes.data, None, None, C.byref(st)))
+            return rgb, st.as_dict()
+        req, run = _progress_request(progress, preview_ms, lambda p: {"image": np.ctypeslib.as_array(p.rgb, shape=(H, W, 3))})
+        rc = lib.frayhip_render_progressive(self._dev, C.byref(fr), C.byref(req), rgb.ctypes.data, None, None, C.byref(st))
+        return rgb, run.finish(rc, st)
 
     def primary_hits(self, bucket_first=0, bucket_stride=1, stats=False):
         """Closest hit of the camera ray through every integer pixel: (ids int32 [H,W], dist f64 [H,W], stats)."""
@@ -154,13 +204,18 @@ class Scene:
         return ids, dist, st.as_dict()
 
     def render_device(self, d_rgb_ptr, seed=42, bucket_first=0, bucket_stride=1, spp_chunk=0, stats=False,
-                      stream=None, mode=abi.MODE_RENDER, d_id_ptr=None, d_dist_ptr=None):
-        """Render into caller-owned device memory (e.g. torch tensors' data_ptr())."""
+                      stream=None, mode=abi.MODE_RENDER, d_id_ptr=None, d_dist_ptr=None, progress=None, preview_ms=-1):
+        """Render into caller-owned device memory (e.g. torch tensors' data_ptr()).  progress / preview_ms as in render(); a preview's
+        info["d_rgb"] is the device address of the frame (d_rgb_ptr), complete when the callback runs."""
         self._need_dev()
         st = abi.Stats()
         fr = self._frame(mode, seed, bucket_first, bucket_stride, spp_chunk, stats)
-        _check(lib.frayhip_render_device(self._dev, C.byref(fr), d_rgb_ptr, d_id_ptr, d_dist_ptr, stream, C.byref(st)))
-        return st.as_dict()
+        if progress is None:
+            _check(lib.frayhip_render_device(self._dev, C.byref(fr), d_rgb_ptr, d_id_ptr, d_dist_ptr, stream, C.byref(st)))
+            return st.as_dict()
+        req, run = _progress_request(progress, preview_ms, lambda p: {"d_rgb": C.cast(p.rgb, C.c_void_p).value})
+        rc = lib.frayhip_render_device_progressive(self._dev, C.byref(fr), C.byref(req), d_rgb_ptr, d_id_ptr, d_dist_ptr, stream, C.byref(st))
+        return run.finish(rc, st)
 
     def close(self):
         self.endRender()

@@ -32,6 +32,7 @@ enum {
     FRAYHIP_E_UNSUPPORTED = -4,  /* scene uses an element the device path does not implement  */
     FRAYHIP_E_NOMEM       = -5,  /* host or device allocation failed                           */
     FRAYHIP_E_HIP         = -6,  /* any other HIP runtime failure (launch, copy, event); text in frayhip_last_error() */
+    FRAYHIP_E_CANCELLED   = -7,  /* a progressive frame was cancelled by its callback: the output holds the frame of the samples resolved */
 };
 
 /* ---- scene description (flattened `Scene`, scene.h:280-299) ------------------------------ */
@@ -322,6 +323,53 @@ int  frayhip_render(frayhip_scene* s, const frayhip_frame* f,
 int  frayhip_render_device(frayhip_scene* s, const frayhip_frame* f,
                            float* d_rgb, int32_t* d_hit_id, double* d_hit_dist,
                            void* hip_stream, frayhip_stats* st);
+
+/* ---- progressive frames (stand behind the reference's displayVFBRect / `rendering` seam, sdl.cpp:287-311, main.cpp:339-368) ----
+ * A frame is rendered in batches of frayhip_frame.spp_chunk samples per pixel (0 = as many as the queue budget holds).  The per-pixel FP32
+ * sum runs in sample order from batch to batch, and sample i of a pixel is seeded the same whatever the frame's spp, so after the batches
+ * covering the first s samples, sum / (float)s IS the frame this scene renders with s samples per pixel, bit for bit: a preview is an exact
+ * lower-spp frame, and a cancelled frame is an exact, usable one.
+ *
+ * Callback thread and timing: fn runs on the calling thread, after a batch's resolve has completed on the device.  samples_done strictly
+ *   increases from call to call and always falls on a batch boundary.  The last call has final = 1 (its return value is ignored);
+ *   MODE_PRIMARY_ID, maxTraceDepth < 0 and one-batch frames make exactly that one call.  A call that fails with an error makes no final call.
+ * Cancel: a nonzero return means cancel.  No further batch is enqueued; the batches already in flight are finished and resolved in order,
+ *   then rgb receives the mean of every resolved sample (the same FP32 division as the resolve), the final call reports that sample count
+ *   and the call returns FRAYHIP_E_CANCELLED with rgb and *st valid (*st counts the work of the resolved batches).  A cancel that comes when
+ *   every batch is already in flight cuts nothing: the frame completes and the call returns FRAYHIP_OK.
+ * Cancel latency: at most the batches in flight when fn returned, which is at most the number of lanes (option "pt_lanes"; one for the
+ *   Whitted integrators).  The caller chooses the granularity through frame.spp_chunk.
+ * Previews: preview_ms < 0 asks for none, 0 for one after every batch but the last, > 0 for at most one per that many milliseconds of wall
+ *   time (counted from the start of the call).  A preview writes the running mean of the call's buckets into the caller's rgb buffer, as
+ *   the reference's vfb fills in while it renders; pixels of other buckets are untouched.  preview = 1 when rgb holds such a frame; the
+ *   final call of a MODE_RENDER frame always carries the finished frame (preview = 1).  The host entry has copied the frame to the host rgb
+ *   before calling back; the device entry's frame is complete in device memory (the batch's stream was synchronised) before calling back.
+ *   The rgb pointer is valid during the call only.
+ * Pacing: at most `lanes` batches are enqueued ahead of the one being reported, so the device keeps working while the host waits on a
+ *   batch; a batch's resolve is enqueued after the previous batch's call returned, so the buffer is not rewritten while fn reads it.
+ * Reentrancy: fn must not render or change the same scene: frayhip_render* and frayhip_scene_set_view / _set_option return FRAYHIP_E_ARG
+ *   while the scene renders (the frame being rendered is unaffected).  Nor may fn destroy it.  Other scenes may be used. */
+typedef struct frayhip_progress {
+    int32_t samples_done;        /* samples per pixel resolved so far (a batch boundary)                                  */
+    int32_t samples_total;       /* samples per pixel of the whole frame                                                   */
+    int32_t batches_done, batches_total;
+    double  ms_elapsed;          /* wall time since the call started                                                       */
+    int32_t preview;             /* 1: rgb holds the running mean of the call's buckets                                    */
+    int32_t final;               /* 1: the last call of this frame                                                         */
+    const float* rgb;            /* the frame: host memory for frayhip_render_progressive, device memory for the device entry; NULL unless preview */
+} frayhip_progress;
+
+typedef struct frayhip_progressive {
+    int  (*fn)(void* user, const frayhip_progress* p);     /* nonzero return = cancel                                     */
+    void*  user;
+    double preview_ms;           /* < 0 no previews, 0 after every batch, > 0 at most one per that many ms (NaN: FRAYHIP_E_ARG) */
+} frayhip_progressive;
+
+/* frayhip_render / frayhip_render_device with a progress request (p may not be NULL; p->fn may be NULL for a frame that only paces). */
+int  frayhip_render_progressive(frayhip_scene* s, const frayhip_frame* f, const frayhip_progressive* p,
+                                float* rgb, int32_t* hit_id, double* hit_dist, frayhip_stats* st);
+int  frayhip_render_device_progressive(frayhip_scene* s, const frayhip_frame* f, const frayhip_progressive* p,
+                                       float* d_rgb, int32_t* d_hit_id, double* d_hit_dist, void* hip_stream, frayhip_stats* st);
 
 /* Multi-GPU tile exchange helpers.  pack: gathers this rank's buckets from a
  * full-frame device buffer into a compact bucket-major buffer of
