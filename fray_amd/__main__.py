@@ -1,13 +1,17 @@
 """File-only front end over the C ABI (the reference's main() opens an SDL window instead,
-src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --height H --spp N] [--progress] [--time-limit SECONDS]"""
+src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --height H --spp N] [--progress] [--time-limit SECONDS]
+                         python -m fray_amd scene.fray --probe X Y [--width W --height H]   (one JSON line: what the camera ray through pixel X, Y hits)"""
 import argparse
+import json
 import sys
 import time
+
+import numpy as np
 
 from . import Scene, lib
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(prog="python -m fray_amd")
     ap.add_argument("scene")
     ap.add_argument("-o", "--output", default="fray_0000.bmp")
@@ -19,7 +23,22 @@ def main(argv=None):
     ap.add_argument("--progress", action="store_true", help="print one line per finished batch of samples")
     ap.add_argument("--time-limit", type=float, metavar="SECONDS",
                     help="cancel the frame once this much time has passed and write what is finished (an exact frame of fewer samples per pixel)")
-    a = ap.parse_args(argv)
+    ap.add_argument("--probe", type=float, nargs=2, metavar=("X", "Y"),
+                    help="trace the camera ray through pixel (X, Y) and print its hit record as one JSON line (the reference's debugRayTrace); no image is written")
+    return ap
+
+
+def probe(s, x, y):
+    """debugRayTrace (main.cpp:426-435): the camera ray through (x, y) and its closest hit, as a dict."""
+    o, d = s.camera_rays(np.array([[x, y]], np.float64))
+    r = s.trace_rays(o, d, record=True)
+    rec = [float(v) for v in r["hit_rec"][0]]
+    return {"x": x, "y": y, "origin": [float(v) for v in o[0]], "dir": [float(v) for v in d[0]], "hit_id": int(r["hit_id"][0]),
+            "dist": rec[0], "ip": rec[1:4], "norm": rec[4:7], "u": rec[7], "v": rec[8]}
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     s = Scene.parseScene(a.scene)
     if a.width:
         s.settings.frameWidth = a.width
@@ -31,6 +50,9 @@ def main(argv=None):
         elif s.camera.dof:
             s.camera.numDOFSamples = a.spp
     s.beginRender(a.device)
+    if a.probe:
+        print(json.dumps(probe(s, a.probe[0], a.probe[1])))
+        return 0
     t0 = time.time()
     if a.progress or a.time_limit is not None:
         def progress(info):

@@ -184,6 +184,12 @@ SYMBOLS = {
     "frayhip_render_device": (C.c_int, [VP, P(Frame), VP, VP, VP, VP, P(Stats)]),
     "frayhip_render_progressive": (C.c_int, [VP, P(Frame), P(Progressive), VP, VP, VP, P(Stats)]),
     "frayhip_render_device_progressive": (C.c_int, [VP, P(Frame), P(Progressive), VP, VP, VP, VP, P(Stats)]),
+    "frayhip_camera_rays": (C.c_int, [VP, i64, VP, C.c_int, VP, VP]),
+    "frayhip_camera_rays_device": (C.c_int, [VP, i64, VP, C.c_int, VP, VP, VP]),
+    "frayhip_trace_rays": (C.c_int, [VP, i64, VP, VP, C.c_int, VP, VP, VP, P(Stats)]),
+    "frayhip_trace_rays_device": (C.c_int, [VP, i64, VP, VP, C.c_int, VP, VP, VP, VP, P(Stats)]),
+    "frayhip_visible": (C.c_int, [VP, i64, VP, VP, C.c_int, VP, P(Stats)]),
+    "frayhip_visible_device": (C.c_int, [VP, i64, VP, VP, C.c_int, VP, VP, P(Stats)]),
     "frayhip_bucket_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "frayhip_pack_buckets_device": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP]),
     "frayhip_unpack_buckets_device": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP]),

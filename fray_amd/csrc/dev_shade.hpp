@@ -60,11 +60,12 @@ FD void prim_attributes(const DScene& S, int kind, int index, V3 ipl, int code, 
 }
 
 // BARY: the hit record carries no barycentrics (the path tracer's hit queue): they are re-derived for meshes that read them.
-template <int ST, bool BARY = false>
+// ANY_UV: needUV is honoured in every variant, also those compiled without texture code (the ray queries' hit record, query_variant.hip).
+template <int ST, bool BARY = false, bool ANY_UV = false>
 FD void finalize_hit(const DScene& S, const HitT<ST>& h, V3 o, V3 d, bool needUV, HitInfo& info)
 {
     const FRAY_RO DNode& N = S.nodes[h.node];
-    needUV = needUV && tex_variant(ST);                       // no texture in the scene reads (u, v)
+    needUV = needUV && (ANY_UV || tex_variant(ST));           // no texture in the scene reads (u, v)
     const bool needBump = tex_variant(ST) && N.bumpTex >= 0;
     V3 ls = mulM(o - ld3(N.T.off), N.T.inv);
     V3 ldir = normalized(mulM(d, N.T.inv));

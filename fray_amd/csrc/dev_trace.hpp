@@ -1020,6 +1020,17 @@ FD bool light_intersect(const FRAY_RO DLight& L, V3 o, V3 d, double& dist, Cnt& 
     return true;
 }
 
+// What RectLight::intersect (lights.cpp:79-103) leaves in the IntersectionInfo of a light that light_intersect reported hit: ip and norm, in its
+// arithmetic (the ray queries' hit record, query_variant.hip).
+FD void light_record(const FRAY_RO DLight& L, V3 o, V3 d, V3& ip, V3& norm)
+{
+    V3 ls = mulM(o - ld3(L.T.off), L.T.inv);
+    V3 ldir = normalized(mulM(d, L.T.inv));
+    double scaling = fray_div(fabs(ls.y), fabs(ldir.y));
+    ip = mulM(ls + ldir * scaling, L.T.m) + ld3(L.T.off);
+    norm = normalized(mulM(v3(0, -1, 0), L.T.m));
+}
+
 // The two loops of raytrace()/pathtrace(): first node wins ties (strict <), then lights.
 // gateFree: the ray's producer PROVED that it misses every gate of the scene (kernels.hpp ray_gate_class with DScene::gatesExact; dev_misscert.hpp): the
 // gated nodes' geometry then reports no intersection, as the reference computes it, and is not asked (the counting variants ask: a CsgOp node's

@@ -87,6 +87,62 @@ def _progress_request(progress, preview_ms, frame_view):
     return req, run
 
 
+def _torch_tensor(x):
+    t = sys.modules.get("torch")
+    return t is not None and isinstance(x, t.Tensor)
+
+
+def _query_inputs(named, width=3):
+    """The inputs of a ray query, [(name, value)]: numpy arrays or device torch tensors (not a mix), float64, shaped [..., width], all of one
+    shape.  Returns (contiguous inputs, leading shape, torch device or None)."""
+    tensors = [_torch_tensor(v) for _, v in named]
+    if any(tensors) and not all(tensors):
+        raise TypeError("ray query: pass numpy arrays or torch tensors, not a mix")
+    out, shape, device = [], None, None
+    for name, v in named:
+        if tensors[0]:
+            import torch
+            if not v.is_cuda:
+                raise TypeError("ray query: %s is a CPU tensor; pass a tensor on the GPU (device entry) or a numpy array (host entry)" % name)
+            if v.dtype != torch.float64:
+                raise TypeError("ray query: %s must be float64, got %s" % (name, v.dtype))
+            if device is not None and v.device != device:
+                raise ValueError("ray query: the inputs are on different devices")
+            device = v.device
+        else:
+            v = np.asarray(v)
+            if v.dtype != np.float64:
+                raise TypeError("ray query: %s must be float64, got %s" % (name, v.dtype))
+        if v.ndim < 1 or v.shape[-1] != width:
+            raise ValueError("ray query: %s must be shaped [..., %d], got %s" % (name, width, tuple(v.shape)))
+        if shape is not None and tuple(v.shape[:-1]) != shape:
+            raise ValueError("ray query: the inputs' shapes differ: %s and %s" % (shape, tuple(v.shape[:-1])))
+        shape = tuple(v.shape[:-1])
+        out.append(v)
+    return out, shape, device
+
+
+class _DeviceCall:
+    """A device entry's call on a torch stream: inputs made contiguous and outputs allocated on that stream (the entry synchronises it)."""
+
+    def __init__(self, device, stream):
+        import torch
+        self.torch = torch
+        self.stream = stream if stream is not None else torch.cuda.current_stream(device)
+        self.ctx = torch.cuda.stream(self.stream)
+
+    def __enter__(self):
+        self.ctx.__enter__()
+        return self
+
+    def __exit__(self, *exc):
+        return self.ctx.__exit__(*exc)
+
+    @property
+    def handle(self):
+        return C.c_void_p(self.stream.cuda_stream)
+
+
 class Scene:
     """`Scene scene` of the reference (scene.h:280-299).
 
@@ -216,6 +272,81 @@ class Scene:
         req, run = _progress_request(progress, preview_ms, lambda p: {"d_rgb": C.cast(p.rgb, C.c_void_p).value})
         rc = lib.frayhip_render_device_progressive(self._dev, C.byref(fr), C.byref(req), d_rgb_ptr, d_id_ptr, d_dist_ptr, stream, C.byref(st))
         return run.finish(rc, st)
+
+    # ---- ray queries (include/frayhip.h): numpy arrays through the host entries, torch tensors on the GPU through the device entries ----
+    def camera_rays(self, xy=None, eye=0, stream=None):
+        """Camera::getScreenRay(x, y, eye) of the current view (eye 0 = CENTER, 1 = LEFT, 2 = RIGHT): (origin, dir).  xy None: every integer
+        pixel, shaped [H, W, 3] (the rays of primary_hits(), bit for bit); else film positions [..., 2] float64 -> [..., 3]."""
+        self._need_dev()
+        if xy is None:
+            W, H = self.frame_size
+            org, dirs = np.empty((H, W, 3)), np.empty((H, W, 3))
+            _check(lib.frayhip_camera_rays(self._dev, W * H, None, int(eye), org.ctypes.data, dirs.ctypes.data))
+            return org, dirs
+        (xy,), shape, device = _query_inputs([("xy", xy)], 2)
+        n = int(np.prod(shape, dtype=np.int64))
+        if device is None:
+            xy = np.ascontiguousarray(xy)
+            org, dirs = np.empty(shape + (3,)), np.empty(shape + (3,))
+            _check(lib.frayhip_camera_rays(self._dev, n, xy.ctypes.data, int(eye), org.ctypes.data, dirs.ctypes.data))
+            return org, dirs
+        with _DeviceCall(device, stream) as call:
+            torch = call.torch
+            xy = xy.contiguous()
+            org = torch.empty(shape + (3,), dtype=torch.float64, device=device)
+            dirs = torch.empty(shape + (3,), dtype=torch.float64, device=device)
+            if n:                                   # (an empty tensor's data_ptr() is 0: nothing to call)
+                _check(lib.frayhip_camera_rays_device(self._dev, n, xy.data_ptr(), int(eye), org.data_ptr(), dirs.data_ptr(), call.handle))
+        return org, dirs
+
+    def trace_rays(self, origin, dir, record=False, stats=False, stream=None):
+        """The reference's closestHit for rays origin / dir [..., 3] float64: {"hit_id" (int32, -1 miss, -2-i light i), "hit_dist" (1e99 on a miss),
+        "hit_rec" (only with record: [..., 9] = dist, ip, norm, u, v), "stats"}."""
+        self._need_dev()
+        (o, d), shape, device = _query_inputs([("origin", origin), ("dir", dir)])
+        n = int(np.prod(shape, dtype=np.int64))
+        st = abi.Stats()
+        flags = abi.FRAME_STATS if stats else 0
+        if device is None:
+            o, d = np.ascontiguousarray(o), np.ascontiguousarray(d)
+            ids, dist = np.empty(shape, np.int32), np.empty(shape, np.float64)
+            rec = np.empty(shape + (9,), np.float64) if record else None
+            _check(lib.frayhip_trace_rays(self._dev, n, o.ctypes.data, d.ctypes.data, flags, ids.ctypes.data, dist.ctypes.data,
+                                          rec.ctypes.data if record else None, C.byref(st)))
+        else:
+            with _DeviceCall(device, stream) as call:
+                torch = call.torch
+                o, d = o.contiguous(), d.contiguous()
+                ids = torch.empty(shape, dtype=torch.int32, device=device)
+                dist = torch.empty(shape, dtype=torch.float64, device=device)
+                rec = torch.empty(shape + (9,), dtype=torch.float64, device=device) if record else None
+                if n:                                   # (an empty tensor's data_ptr() is 0: nothing to call)
+                    _check(lib.frayhip_trace_rays_device(self._dev, n, o.data_ptr(), d.data_ptr(), flags, ids.data_ptr(), dist.data_ptr(),
+                                                         rec.data_ptr() if record else None, call.handle, C.byref(st)))
+        out = {"hit_id": ids, "hit_dist": dist, "stats": st.as_dict()}
+        if record:
+            out["hit_rec"] = rec
+        return out
+
+    def visible(self, a, b, stats=False, stream=None):
+        """visible(a, b) (main.cpp:64-80) for segments a -> b [..., 3] float64: (vis, stats), vis a bool array / tensor [...]."""
+        self._need_dev()
+        (a, b), shape, device = _query_inputs([("a", a), ("b", b)])
+        n = int(np.prod(shape, dtype=np.int64))
+        st = abi.Stats()
+        flags = abi.FRAME_STATS if stats else 0
+        if device is None:
+            a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+            vis = np.empty(shape, np.bool_)
+            _check(lib.frayhip_visible(self._dev, n, a.ctypes.data, b.ctypes.data, flags, vis.ctypes.data, C.byref(st)))
+        else:
+            with _DeviceCall(device, stream) as call:
+                torch = call.torch
+                a, b = a.contiguous(), b.contiguous()
+                vis = torch.empty(shape, dtype=torch.bool, device=device)       # one byte per element: the entry's uint8 output
+                if n:                                   # (an empty tensor's data_ptr() is 0: nothing to call)
+                    _check(lib.frayhip_visible_device(self._dev, n, a.data_ptr(), b.data_ptr(), flags, vis.data_ptr(), call.handle, C.byref(st)))
+        return vis, st.as_dict()
 
     def close(self):
         self.endRender()

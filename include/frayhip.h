@@ -371,6 +371,47 @@ int  frayhip_render_progressive(frayhip_scene* s, const frayhip_frame* f, const 
 int  frayhip_render_device_progressive(frayhip_scene* s, const frayhip_frame* f, const frayhip_progressive* p,
                                        float* d_rgb, int32_t* d_hit_id, double* d_hit_dist, void* hip_stream, frayhip_stats* st);
 
+/* ---- ray queries (stand behind Camera::getScreenRay, camera.cpp:59-92; the closest-hit loops that debugRayTrace fires through a clicked
+ *      pixel, main.cpp:178-199, 250-271, 426-435; and visible(), main.cpp:64-80) ----------------------------------------------------------
+ * Rays the caller chooses, traced against an uploaded scene.  All arrays are row-major and contiguous; n rows each.  The _device entries take
+ * DEVICE pointers, enqueue on `hip_stream` (NULL = default stream) and return after that stream has been synchronised, as
+ * frayhip_render_device does; the host entries copy in, run the same device path and copy out.
+ *
+ * frayhip_camera_rays: Camera::getScreenRay(x, y, eye) of the scene's current view (frayhip_scene_set_view) for the film positions xy[n][2];
+ *   eye 0 = CENTER, 1 = LEFT, 2 = RIGHT.  origin[n][3] and dir[n][3] (either may be NULL, not both).  The device's camera ray of a frame, on the
+ *   same camera record: for integer positions these are the rays of FRAYHIP_MODE_PRIMARY_ID, bit for bit.  xy == NULL means every integer pixel
+ *   in row-major order (x fastest) and requires n == frameWidth * frameHeight.  Thin-lens (DOF) rays draw random numbers and are not offered.
+ * frayhip_trace_rays: the reference's closestHit -- every node in order, the first node wins ties, then the rect lights -- for origin[n][3],
+ *   dir[n][3].  Directions are used as given, as Ray.dir is: node and light tests normalise in their own local frame, so any nonzero finite
+ *   direction is defined.  Outputs, any of them may be NULL (not all three):
+ *     hit_id[n]      node index, -1 miss, -2-i light i (the ids of FRAYHIP_MODE_PRIMARY_ID)
+ *     hit_dist[n]    world distance, 1e99 on a miss
+ *     hit_rec[n][9]  dist, ip[3], norm[3], u, v: the IntersectionInfo of the winner before bump mapping.  A rect light's record holds the ip and norm
+ *                    RectLight::intersect writes (lights.cpp:79-103) and u = v = 0; a miss is {1e99, 0, ...}.  u, v are made for every geometry
+ *                    (a sphere's atan2 / asin ones included, whatever the scene's textures).  NULL: the winner is never finalised.
+ * frayhip_visible: visible(a[i], b[i]) as main.cpp:64-80 computes it (dir = normalize(b - a), maxDist = |a - b|, lights do not occlude):
+ *   vis[i] = 1 when the segment is visible, 0 otherwise.
+ * Degenerate input is answered without tracing (the outcome the reference's arithmetic gives anyway, and no NaN enters the KD walk):
+ *   a ray with a non-finite component, or whose direction's squared length dir.x^2 + dir.y^2 + dir.z^2 is 0 (a zero direction) or overflows,
+ *   is a miss; a segment with a non-finite endpoint, or whose length |b - a| is 0 (a == b) or overflows, is visible.
+ * flags: FRAYHIP_FRAME_STATS selects the counting kernel variants.  *st may be NULL; when given it holds ms_total, ms_kernels and the query kernel's
+ *   device time in ms_trace / trace_launches (frayhip_visible: ms_shadow / shadow_launches), and with the stats flag the work counters of the rays
+ *   traced: closest_rays (shadow_rays), node_tests, kd_inner_visits, leaf_refs, tri_tests, prim_tests, smooth_hits.  The alg_* fields stay 0.
+ * FRAYHIP_E_ARG, before the device is touched: a NULL scene, n < 0 or n > INT32_MAX, a NULL input with n > 0, no output, a double / int32 device
+ *   pointer that is not 8 / 4-byte aligned, eye outside 0..2, and any call on a scene whose frame is being rendered (from inside its progress
+ *   callback).  n == 0 is a successful no-op.  A query changes no option of the scene and none of the last frame's figures that
+ *   frayhip_scene_get_option reports. */
+int  frayhip_camera_rays(frayhip_scene* s, int64_t n, const double* xy, int eye, double* origin, double* dir);
+int  frayhip_camera_rays_device(frayhip_scene* s, int64_t n, const double* d_xy, int eye,
+                                double* d_origin, double* d_dir, void* hip_stream);
+int  frayhip_trace_rays(frayhip_scene* s, int64_t n, const double* origin, const double* dir, int flags,
+                        int32_t* hit_id, double* hit_dist, double* hit_rec, frayhip_stats* st);
+int  frayhip_trace_rays_device(frayhip_scene* s, int64_t n, const double* d_origin, const double* d_dir, int flags,
+                               int32_t* d_hit_id, double* d_hit_dist, double* d_hit_rec, void* hip_stream, frayhip_stats* st);
+int  frayhip_visible(frayhip_scene* s, int64_t n, const double* a, const double* b, int flags, uint8_t* vis, frayhip_stats* st);
+int  frayhip_visible_device(frayhip_scene* s, int64_t n, const double* d_a, const double* d_b, int flags,
+                            uint8_t* d_vis, void* hip_stream, frayhip_stats* st);
+
 /* Multi-GPU tile exchange helpers.  pack: gathers this rank's buckets from a
  * full-frame device buffer into a compact bucket-major buffer of
  * frayhip_bucket_count(W,H,first,stride) * 48*48*channels floats; unpack is the inverse and
