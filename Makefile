@@ -28,7 +28,9 @@ VARIANT_OBJ := $(foreach st,0 1 2 3 4 5 8 9,fray_amd/csrc/variant$(st).o)
 CONTRACT_OBJ := $(foreach st,0 1 4 5 8 9,fray_amd/csrc/variantC$(st).o)
 # query_variant.hip: the ray query kernels (frayhip_trace_rays / frayhip_visible) per flag word, in objects of their own beside the frame kernels
 QUERY_OBJ := $(foreach st,0 1 2 3 4 5 8 9,fray_amd/csrc/query$(st).o)
-HIP_OBJ  := fray_amd/csrc/capi.o fray_amd/csrc/capi_comm.o fray_amd/csrc/capi_query.o $(VARIANT_OBJ) $(CONTRACT_OBJ) $(QUERY_OBJ)
+# shade_variant.hip: the radiance query (frayhip_shade_rays) per flag word, in objects of their own as well
+SHADE_OBJ := $(foreach st,0 1 2 3 4 5 8 9,fray_amd/csrc/shade$(st).o)
+HIP_OBJ  := fray_amd/csrc/capi.o fray_amd/csrc/capi_comm.o fray_amd/csrc/capi_query.o fray_amd/csrc/capi_shade.o $(VARIANT_OBJ) $(CONTRACT_OBJ) $(QUERY_OBJ) $(SHADE_OBJ)
 HIP_HDR  := $(wildcard fray_amd/csrc/*.h) $(wildcard fray_amd/csrc/*.hpp) include/frayhip.h
 
 all: fray_amd/libfrayhip.so oracle/libfray_oracle.so examples/fray_render examples/fray_render_mgpu tests/native/librccl_loopback.so ref
@@ -46,6 +48,9 @@ fray_amd/csrc/variant%.o: fray_amd/csrc/render_variant.hip $(HIP_HDR)
 
 fray_amd/csrc/query%.o: fray_amd/csrc/query_variant.hip $(HIP_HDR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -DFRAY_ST=$* -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> fray_amd/csrc/query$*.resources.txt || (cat fray_amd/csrc/query$*.resources.txt; false)
+
+fray_amd/csrc/shade%.o: fray_amd/csrc/shade_variant.hip $(HIP_HDR)
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -DFRAY_ST=$* -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> fray_amd/csrc/shade$*.resources.txt || (cat fray_amd/csrc/shade$*.resources.txt; false)
 
 # (the last -ffp-contract on the command line wins)
 fray_amd/csrc/variantC%.o: fray_amd/csrc/render_contract.hip $(HIP_HDR)
@@ -74,8 +79,8 @@ tests/native/librccl_loopback.so: tests/native/rccl_loopback.cpp
 ref:
 	@if [ -d /root/reference/src ]; then $(MAKE) -C oracle -f Makefile.ref; else echo "reference tree absent: oracle/_ref not rebuilt"; fi
 
-resources: $(VARIANT_OBJ) $(QUERY_OBJ)
-	python3 tools/kernel_resources.py fray_amd/csrc/variant*.resources.txt fray_amd/csrc/query*.resources.txt
+resources: $(VARIANT_OBJ) $(QUERY_OBJ) $(SHADE_OBJ)
+	python3 tools/kernel_resources.py fray_amd/csrc/variant*.resources.txt fray_amd/csrc/query*.resources.txt fray_amd/csrc/shade*.resources.txt
 
 clean:
 	rm -f fray_amd/csrc/*.o fray_amd/csrc/*.resources.txt fray_amd/libfrayhip.so oracle/libfray_oracle.so examples/fray_render examples/fray_render_mgpu tests/native/librccl_loopback.so

@@ -1,6 +1,7 @@
 """File-only front end over the C ABI (the reference's main() opens an SDL window instead,
 src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --height H --spp N] [--progress] [--time-limit SECONDS]
-                         python -m fray_amd scene.fray --probe X Y [--width W --height H]   (one JSON line: what the camera ray through pixel X, Y hits)"""
+                         python -m fray_amd scene.fray --probe X Y [--shade] [--width W --height H]   (one JSON line: what the camera ray through pixel X, Y hits;
+                                                                                          --shade: and its colour)"""
 import argparse
 import json
 import sys
@@ -25,16 +26,24 @@ def build_parser():
                     help="cancel the frame once this much time has passed and write what is finished (an exact frame of fewer samples per pixel)")
     ap.add_argument("--probe", type=float, nargs=2, metavar=("X", "Y"),
                     help="trace the camera ray through pixel (X, Y) and print its hit record as one JSON line (the reference's debugRayTrace); no image is written")
+    ap.add_argument("--shade", action="store_true",
+                    help="with --probe: also fire the scene's integrator along that ray (one sample, key floor(Y) * width + floor(X), --seed) and add its \"rgb\"")
     return ap
 
 
-def probe(s, x, y):
-    """debugRayTrace (main.cpp:426-435): the camera ray through (x, y) and its closest hit, as a dict."""
+def probe(s, x, y, shade=False, seed=42):
+    """debugRayTrace (main.cpp:426-435): the camera ray through (x, y) and its closest hit, as a dict; with `shade` also trace() of that ray -- one
+    sample of the scene's integrator, generator key floor(y) * width + floor(x) -- as "rgb"."""
     o, d = s.camera_rays(np.array([[x, y]], np.float64))
     r = s.trace_rays(o, d, record=True)
     rec = [float(v) for v in r["hit_rec"][0]]
-    return {"x": x, "y": y, "origin": [float(v) for v in o[0]], "dir": [float(v) for v in d[0]], "hit_id": int(r["hit_id"][0]),
-            "dist": rec[0], "ip": rec[1:4], "norm": rec[4:7], "u": rec[7], "v": rec[8]}
+    out = {"x": x, "y": y, "origin": [float(v) for v in o[0]], "dir": [float(v) for v in d[0]], "hit_id": int(r["hit_id"][0]),
+           "dist": rec[0], "ip": rec[1:4], "norm": rec[4:7], "u": rec[7], "v": rec[8]}
+    if shade:
+        key = int(np.floor(y)) * s.frame_size[0] + int(np.floor(x))
+        rgb = s.shade_rays(o, d, seed=seed, keys=np.array([key], np.uint32))
+        out["rgb"] = [float(v) for v in rgb[0]]
+    return out
 
 
 def main(argv=None):
@@ -51,7 +60,7 @@ def main(argv=None):
             s.camera.numDOFSamples = a.spp
     s.beginRender(a.device)
     if a.probe:
-        print(json.dumps(probe(s, a.probe[0], a.probe[1])))
+        print(json.dumps(probe(s, a.probe[0], a.probe[1], a.shade, a.seed)))
         return 0
     t0 = time.time()
     if a.progress or a.time_limit is not None:

@@ -159,6 +159,11 @@ class Progressive(C.Structure):
     _fields_ = [("fn", PROGRESS_FN), ("user", C.c_void_p), ("preview_ms", f64)]
 
 
+class ShadeRequest(C.Structure):
+    _fields_ = [("seed", u32), ("spp", i32), ("sample_first", i32), ("rng_skip", i32), ("flags", i32), ("_pad", i32),
+                ("keys", C.c_void_p)]
+
+
 STRUCTS = {"frayhip_transform": Transform, "frayhip_geom_ref": GeomRef, "frayhip_node": Node,
            "frayhip_plane": Plane, "frayhip_sphere": Sphere, "frayhip_cube": Cube,
            "frayhip_csg": Csg, "frayhip_triangle": Triangle, "frayhip_kdnode": KDNode,
@@ -166,7 +171,8 @@ STRUCTS = {"frayhip_transform": Transform, "frayhip_geom_ref": GeomRef, "frayhip
            "frayhip_layer": Layer, "frayhip_light": Light, "frayhip_camera": Camera,
            "frayhip_settings": Settings, "frayhip_environment": Environment,
            "frayhip_scene_desc": SceneDesc, "frayhip_frame": Frame, "frayhip_stats": Stats,
-           "frayhip_progress": Progress, "frayhip_progressive": Progressive}
+           "frayhip_progress": Progress, "frayhip_progressive": Progressive,
+           "frayhip_shade_request": ShadeRequest}
 
 # Every symbol include/frayhip.h declares: name -> (restype, argtypes)
 VP = C.c_void_p
@@ -190,6 +196,8 @@ SYMBOLS = {
     "frayhip_trace_rays_device": (C.c_int, [VP, i64, VP, VP, C.c_int, VP, VP, VP, VP, P(Stats)]),
     "frayhip_visible": (C.c_int, [VP, i64, VP, VP, C.c_int, VP, P(Stats)]),
     "frayhip_visible_device": (C.c_int, [VP, i64, VP, VP, C.c_int, VP, VP, P(Stats)]),
+    "frayhip_shade_rays": (C.c_int, [VP, i64, VP, VP, P(ShadeRequest), VP, P(Stats)]),
+    "frayhip_shade_rays_device": (C.c_int, [VP, i64, VP, VP, P(ShadeRequest), VP, VP, P(Stats)]),
     "frayhip_bucket_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "frayhip_pack_buckets_device": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP]),
     "frayhip_unpack_buckets_device": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP]),

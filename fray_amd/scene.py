@@ -348,6 +348,44 @@ class Scene:
                     _check(lib.frayhip_visible_device(self._dev, n, a.data_ptr(), b.data_ptr(), flags, vis.data_ptr(), call.handle, C.byref(st)))
         return vis, st.as_dict()
 
+    def shade_rays(self, origin, dir, spp=1, seed=42, sample_first=0, rng_skip=0, keys=None, stats=False, stream=None):
+        """trace(ray, rnd) (main.cpp:286-293) for rays origin / dir [..., 3] float64: the mean colour of samples sample_first .. sample_first + spp - 1
+        of each ray under the scene's integrator, float32 [..., 3] (include/frayhip.h, radiance queries).  keys: uint32 [...], the generator key of
+        each ray (None: its flat index).  numpy arrays go through the host entry, GPU torch tensors through the device entry on `stream` (default:
+        the current one).  With stats=True returns (rgb, stats)."""
+        self._need_dev()
+        (o, d), shape, device = _query_inputs([("origin", origin), ("dir", dir)])
+        n = int(np.prod(shape, dtype=np.int64))
+        st = abi.Stats()
+        req = abi.ShadeRequest(seed=int(seed) & 0xffffffff, spp=int(spp), sample_first=int(sample_first), rng_skip=int(rng_skip),
+                               flags=abi.FRAME_STATS if stats else 0, keys=None)
+        if device is None:
+            o, d = np.ascontiguousarray(o), np.ascontiguousarray(d)
+            if keys is not None:
+                keys = np.ascontiguousarray(keys, dtype=np.uint32)
+                if keys.shape != shape:
+                    raise ValueError("shade_rays: keys must be shaped %s, got %s" % (shape, keys.shape))
+                req.keys = keys.ctypes.data
+            rgb = np.empty(shape + (3,), np.float32)
+            _check(lib.frayhip_shade_rays(self._dev, n, o.ctypes.data, d.ctypes.data, C.byref(req), rgb.ctypes.data, C.byref(st)))
+        else:
+            with _DeviceCall(device, stream) as call:
+                torch = call.torch
+                o, d = o.contiguous(), d.contiguous()
+                if keys is not None:
+                    if not _torch_tensor(keys) or keys.device != device:
+                        raise TypeError("shade_rays: keys must be a tensor on the rays' device")
+                    if tuple(keys.shape) != shape:
+                        raise ValueError("shade_rays: keys must be shaped %s, got %s" % (shape, tuple(keys.shape)))
+                    if keys.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                        raise TypeError("shade_rays: keys must be int32 / uint32, got %s" % keys.dtype)
+                    keys = keys.contiguous()
+                    req.keys = keys.data_ptr() if n else None
+                rgb = torch.empty(shape + (3,), dtype=torch.float32, device=device)
+                if n:                                   # (an empty tensor's data_ptr() is 0: nothing to call)
+                    _check(lib.frayhip_shade_rays_device(self._dev, n, o.data_ptr(), d.data_ptr(), C.byref(req), rgb.data_ptr(), call.handle, C.byref(st)))
+        return (rgb, st.as_dict()) if stats else rgb
+
     def close(self):
         self.endRender()
         if self._hs:

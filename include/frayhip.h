@@ -412,6 +412,57 @@ int  frayhip_visible(frayhip_scene* s, int64_t n, const double* a, const double*
 int  frayhip_visible_device(frayhip_scene* s, int64_t n, const double* d_a, const double* d_b, int flags,
                             uint8_t* d_vis, void* hip_stream, frayhip_stats* st);
 
+/* ---- radiance queries (stand behind trace(ray, rnd), main.cpp:286-293: raytrace(ray) for Whitted scenes, pathtrace(ray, Color(1, 1, 1), rnd)
+ *      with `gi on`; and the integrator debugRayTrace fires through a clicked pixel, main.cpp:426-435) -----------------------------------------
+ * The colour of rays the caller chooses, under the scene's current settings and integrator (settings.gi, as frayhip_scene_set_view left it).
+ * Arrays as in the ray queries above: row-major, contiguous, n rows; the _device entry takes DEVICE pointers (keys included), enqueues on
+ * `hip_stream` (NULL = default stream) and returns after that stream has been synchronised; the host entry copies in, runs the same device path
+ * and copies out.  All work of a call runs on that one stream.
+ *
+ * The samples.  Ray i has samples k = sample_first .. sample_first + spp - 1.  Sample k uses the RNG contract's generators of pixel
+ *   index key_i = keys[i] (keys == NULL: key_i = i) and sample k: both are seeded with sample_seed(seed, key_i, k); the sample's own generator
+ *   (`rnd`, from which a frame draws its pixel jitter) is then advanced by rng_skip words, and the shaders' (getRandomGen(), from which a frame
+ *   draws the lens sample) starts at word 0.  The sample runs the scene's integrator on Ray{origin_i, dir_i, depth 0}.  raytrace() draws nothing
+ *   from `rnd`, so rng_skip does not change a Whitted colour.
+ * The result.  rgb[i][3] = (the FP32 sum of the sample colours, in sample order) / (float)spp: the frame's resolve (k_pt_resolve_terms).
+ *   Reproducing a frame: a non-DOF Whitted sample is the camera ray through its film position with rng_skip 0, sample_first = the sample and
+ *   key = y * frameWidth + x; a non-DOF path-traced sample the same with rng_skip 2 (the frame draws two jitter floats from `rnd`, then traces).
+ * Not applied: camera, AA offsets, jitter, lens, stereo eyes, saturation (the reference applies it only in the stereo blend, main.cpp:306-317) and
+ *   bucket selection.  The caller's ray is the sample's ray.  Directions are used as given, as frayhip_trace_rays uses them.
+ * Degenerate rays (frayhip_trace_rays' rule: a non-finite component, or a direction whose squared length is 0 or overflows) are answered without
+ *   tracing: rgb = 0, and their samples are not counted.  With maxTraceDepth < 0 every ray is black, as in the frame.
+ * Arithmetic is always the reference's (exact).  Option fp_contract does not apply: its kernels assume unit directions (dev_trace.hpp), and the
+ *   caller's need not be.  Speculative glossy fans are not used either.  Neither changes a result.
+ * A query changes no option of the scene and none of the last frame's figures that frayhip_scene_get_option reports (whitted_path,
+ *   contracted_launches, the fan counts, ...).
+ * flags: FRAYHIP_FRAME_STATS selects the counting kernel variants.  *st may be NULL; when given it holds ms_total, ms_kernels, samples (the samples
+ *   traced, with or without the flag), ms_trace / trace_launches (k_whitted_rays, or k_pt_bounce) and ms_shadow / shadow_launches (k_pt_shadow),
+ *   and with the flag the work counters closest_rays, shadow_rays, node_tests, kd_inner_visits, leaf_refs, tri_tests, prim_tests, smooth_hits,
+ *   texture_fetches.  The alg_* fields stay 0.
+ * FRAYHIP_E_ARG, before the device is touched, with the reason in frayhip_last_error(): a NULL scene, request or rgb; n < 0 or n > INT32_MAX, or a
+ *   NULL origin / dir with n > 0; spp < 1, sample_first < 0, or sample_first + spp > INT32_MAX; rng_skip outside 0..8; a device pointer that is
+ *   misaligned (8 bytes for origin / dir, 4 for keys and rgb); any call on a scene whose frame is being rendered (from inside its progress
+ *   callback).  n == 0 is a successful no-op.
+ * FRAYHIP_E_UNSUPPORTED: the envelope of frames (Whitted shade() nesting deeper than 40, a generator past 227 words, a CsgOp operand with more
+ *   intersections than the device path holds), and path tracing with maxTraceDepth >= 20: a frame's path generators then outgrow their
+ *   registers (8 + 10 * (maxTraceDepth + 2) > 227 words) and the kernel that carries them derives their seeds from the frame's pixels.
+ * Why rng_skip stops at 8: a frame reserves 8 words per sample for the camera when it picks its generator form, so a skip of up to 8 never
+ *   changes which form a scene uses. */
+typedef struct frayhip_shade_request {
+    uint32_t seed;          /* contract seed, as frayhip_frame.seed (the reference uses 42)                       */
+    int32_t  spp;           /* samples per ray, >= 1                                                               */
+    int32_t  sample_first;  /* index of the first sample, >= 0; sample_first + spp <= INT32_MAX                    */
+    int32_t  rng_skip;      /* words of the sample's own generator discarded before the trace, 0..8                */
+    int32_t  flags;         /* FRAYHIP_FRAME_STATS                                                                 */
+    int32_t  _pad;
+    const uint32_t* keys;   /* n keys (host memory for the host entry, device memory for _device); NULL: key = ray index */
+} frayhip_shade_request;
+
+int  frayhip_shade_rays(frayhip_scene* s, int64_t n, const double* origin, const double* dir,
+                        const frayhip_shade_request* r, float* rgb, frayhip_stats* st);
+int  frayhip_shade_rays_device(frayhip_scene* s, int64_t n, const double* d_origin, const double* d_dir,
+                               const frayhip_shade_request* r, float* d_rgb, void* hip_stream, frayhip_stats* st);
+
 /* Multi-GPU tile exchange helpers.  pack: gathers this rank's buckets from a
  * full-frame device buffer into a compact bucket-major buffer of
  * frayhip_bucket_count(W,H,first,stride) * 48*48*channels floats; unpack is the inverse and
