@@ -30,7 +30,10 @@ CONTRACT_OBJ := $(foreach st,0 1 4 5 8 9,fray_amd/csrc/variantC$(st).o)
 QUERY_OBJ := $(foreach st,0 1 2 3 4 5 8 9,fray_amd/csrc/query$(st).o)
 # shade_variant.hip: the radiance query (frayhip_shade_rays) per flag word, in objects of their own as well
 SHADE_OBJ := $(foreach st,0 1 2 3 4 5 8 9,fray_amd/csrc/shade$(st).o)
-HIP_OBJ  := fray_amd/csrc/capi.o fray_amd/csrc/capi_comm.o fray_amd/csrc/capi_query.o fray_amd/csrc/capi_shade.o $(VARIANT_OBJ) $(CONTRACT_OBJ) $(QUERY_OBJ) $(SHADE_OBJ)
+# adaptive_variant.hip: adaptive frames (frayhip_render_adaptive) per flag word, in objects of their own as well
+ADAPTIVE_OBJ := $(foreach st,0 1 2 3 4 5 8 9,fray_amd/csrc/adaptive$(st).o)
+HIP_OBJ  := fray_amd/csrc/capi.o fray_amd/csrc/capi_comm.o fray_amd/csrc/capi_query.o fray_amd/csrc/capi_shade.o fray_amd/csrc/capi_adaptive.o \
+            $(VARIANT_OBJ) $(CONTRACT_OBJ) $(QUERY_OBJ) $(SHADE_OBJ) $(ADAPTIVE_OBJ)
 HIP_HDR  := $(wildcard fray_amd/csrc/*.h) $(wildcard fray_amd/csrc/*.hpp) include/frayhip.h
 
 all: fray_amd/libfrayhip.so oracle/libfray_oracle.so examples/fray_render examples/fray_render_mgpu tests/native/librccl_loopback.so ref
@@ -51,6 +54,9 @@ fray_amd/csrc/query%.o: fray_amd/csrc/query_variant.hip $(HIP_HDR)
 
 fray_amd/csrc/shade%.o: fray_amd/csrc/shade_variant.hip $(HIP_HDR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -DFRAY_ST=$* -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> fray_amd/csrc/shade$*.resources.txt || (cat fray_amd/csrc/shade$*.resources.txt; false)
+
+fray_amd/csrc/adaptive%.o: fray_amd/csrc/adaptive_variant.hip $(HIP_HDR)
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -DFRAY_ST=$* -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> fray_amd/csrc/adaptive$*.resources.txt || (cat fray_amd/csrc/adaptive$*.resources.txt; false)
 
 # (the last -ffp-contract on the command line wins)
 fray_amd/csrc/variantC%.o: fray_amd/csrc/render_contract.hip $(HIP_HDR)
@@ -79,8 +85,8 @@ tests/native/librccl_loopback.so: tests/native/rccl_loopback.cpp
 ref:
 	@if [ -d /root/reference/src ]; then $(MAKE) -C oracle -f Makefile.ref; else echo "reference tree absent: oracle/_ref not rebuilt"; fi
 
-resources: $(VARIANT_OBJ) $(QUERY_OBJ) $(SHADE_OBJ)
-	python3 tools/kernel_resources.py fray_amd/csrc/variant*.resources.txt fray_amd/csrc/query*.resources.txt fray_amd/csrc/shade*.resources.txt
+resources: $(VARIANT_OBJ) $(QUERY_OBJ) $(SHADE_OBJ) $(ADAPTIVE_OBJ)
+	python3 tools/kernel_resources.py fray_amd/csrc/variant*.resources.txt fray_amd/csrc/query*.resources.txt fray_amd/csrc/shade*.resources.txt fray_amd/csrc/adaptive*.resources.txt
 
 clean:
 	rm -f fray_amd/csrc/*.o fray_amd/csrc/*.resources.txt fray_amd/libfrayhip.so oracle/libfray_oracle.so examples/fray_render examples/fray_render_mgpu tests/native/librccl_loopback.so

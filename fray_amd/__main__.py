@@ -1,7 +1,9 @@
 """File-only front end over the C ABI (the reference's main() opens an SDL window instead,
 src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --height H --spp N] [--progress] [--time-limit SECONDS]
                          python -m fray_amd scene.fray --probe X Y [--shade] [--width W --height H]   (one JSON line: what the camera ray through pixel X, Y hits;
-                                                                                          --shade: and its colour)"""
+                                                                                          --shade: and its colour)
+                         python -m fray_amd scene.fray -o out.bmp --adaptive THRESHOLD [--min-spp N] [--adaptive-floor F]   (an adaptive frame, and one
+                                                                                          JSON line: its rungs, mean spp and the share of pixels per rung)"""
 import argparse
 import json
 import sys
@@ -28,7 +30,20 @@ def build_parser():
                     help="trace the camera ray through pixel (X, Y) and print its hit record as one JSON line (the reference's debugRayTrace); no image is written")
     ap.add_argument("--shade", action="store_true",
                     help="with --probe: also fire the scene's integrator along that ray (one sample, key floor(Y) * width + floor(X), --seed) and add its \"rgb\"")
+    ap.add_argument("--adaptive", type=float, metavar="THRESHOLD",
+                    help="adaptive sampling (path-traced scenes): each pixel stops at the first rung of floor(N/2), N, 2N, ... spp whose noise estimate is "
+                         "<= THRESHOLD; prints one JSON line with the rungs, the mean spp and the fraction of pixels at each rung")
+    ap.add_argument("--min-spp", type=int, default=16, metavar="N", help="with --adaptive: the smallest sample count a pixel stops at (default 16)")
+    ap.add_argument("--adaptive-floor", type=float, default=0.01, metavar="F",
+                    help="with --adaptive: the floor added to the pixel's brightness in the error's denominator (default 0.01)")
     return ap
+
+
+def adaptive_summary(spp, info):
+    """The CLI's JSON line for an adaptive frame: rungs run, mean spp, and per sample count the fraction of pixels that stopped there."""
+    counts, n = np.unique(spp, return_counts=True)
+    return {"rungs": info["rungs"], "samples": int(info["samples"]), "mean_spp": float(spp.mean()),
+            "fraction_at": {str(int(c)): float(k) / spp.size for c, k in zip(counts, n)}}
 
 
 def probe(s, x, y, shade=False, seed=42):
@@ -63,7 +78,12 @@ def main(argv=None):
         print(json.dumps(probe(s, a.probe[0], a.probe[1], a.shade, a.seed)))
         return 0
     t0 = time.time()
-    if a.progress or a.time_limit is not None:
+    if a.adaptive is not None:
+        img, spp_map, _err, info = s.render_adaptive(a.adaptive, min_spp=a.min_spp, err_floor=a.adaptive_floor, seed=a.seed)
+        st = info["stats"]
+        print(json.dumps(adaptive_summary(spp_map, info)))
+        spp_text = "adaptive, mean %.2f spp" % spp_map.mean()
+    elif a.progress or a.time_limit is not None:
         def progress(info):
             if a.progress:
                 print("%s%d / %d spp, batch %d / %d, %.1f ms" % ("done: " if info["final"] else "", info["samples_done"], info["samples_total"],
@@ -75,13 +95,14 @@ def main(argv=None):
         cancel_at = []
         img, st = s.render(seed=a.seed, progress=progress)
         spp = st["samples_done"]
+        spp_text = "%d spp" % spp
         if st["cancelled"]:
             print("Time limit of %gs reached: the frame holds %d of %d samples per pixel (finished %.1f ms after the cancel)"
                   % (a.time_limit, spp, s.samples_per_pixel(), st["ms_total"] - cancel_at[0]))
     else:
         img, st = s.render(seed=a.seed)
-        spp = s.samples_per_pixel()
-    print("Render took %.2fs (%d x %d, %d spp, kernels %.1f ms)" % (time.time() - t0, img.shape[1], img.shape[0], spp, st["ms_kernels"]))
+        spp_text = "%d spp" % s.samples_per_pixel()
+    print("Render took %.2fs (%d x %d, %s, kernels %.1f ms)" % (time.time() - t0, img.shape[1], img.shape[0], spp_text, st["ms_kernels"]))
     rc = lib.frayhip_save_bmp(a.output.encode(), img.ctypes.data, img.shape[1], img.shape[0])
     if rc:
         print(lib.frayhip_last_error().decode(), file=sys.stderr)

@@ -164,6 +164,11 @@ class ShadeRequest(C.Structure):
                 ("keys", C.c_void_p)]
 
 
+class Adaptive(C.Structure):
+    _fields_ = [("min_spp", i32), ("_pad", i32), ("threshold", f64), ("err_floor", f64), ("rungs", i32), ("_pad2", i32),
+                ("samples", u64)]
+
+
 STRUCTS = {"frayhip_transform": Transform, "frayhip_geom_ref": GeomRef, "frayhip_node": Node,
            "frayhip_plane": Plane, "frayhip_sphere": Sphere, "frayhip_cube": Cube,
            "frayhip_csg": Csg, "frayhip_triangle": Triangle, "frayhip_kdnode": KDNode,
@@ -172,7 +177,7 @@ STRUCTS = {"frayhip_transform": Transform, "frayhip_geom_ref": GeomRef, "frayhip
            "frayhip_settings": Settings, "frayhip_environment": Environment,
            "frayhip_scene_desc": SceneDesc, "frayhip_frame": Frame, "frayhip_stats": Stats,
            "frayhip_progress": Progress, "frayhip_progressive": Progressive,
-           "frayhip_shade_request": ShadeRequest}
+           "frayhip_shade_request": ShadeRequest, "frayhip_adaptive": Adaptive}
 
 # Every symbol include/frayhip.h declares: name -> (restype, argtypes)
 VP = C.c_void_p
@@ -190,6 +195,8 @@ SYMBOLS = {
     "frayhip_render_device": (C.c_int, [VP, P(Frame), VP, VP, VP, VP, P(Stats)]),
     "frayhip_render_progressive": (C.c_int, [VP, P(Frame), P(Progressive), VP, VP, VP, P(Stats)]),
     "frayhip_render_device_progressive": (C.c_int, [VP, P(Frame), P(Progressive), VP, VP, VP, VP, P(Stats)]),
+    "frayhip_render_adaptive": (C.c_int, [VP, P(Frame), P(Adaptive), VP, VP, VP, P(Stats)]),
+    "frayhip_render_device_adaptive": (C.c_int, [VP, P(Frame), P(Adaptive), VP, VP, VP, VP, P(Stats)]),
     "frayhip_camera_rays": (C.c_int, [VP, i64, VP, C.c_int, VP, VP]),
     "frayhip_camera_rays_device": (C.c_int, [VP, i64, VP, C.c_int, VP, VP, VP]),
     "frayhip_trace_rays": (C.c_int, [VP, i64, VP, VP, C.c_int, VP, VP, VP, P(Stats)]),

@@ -1,5 +1,6 @@
 """Host-side mirror of the reference's Scene / render() interface over the C ABI."""
 import ctypes as C
+import math
 import os
 import sys
 
@@ -385,6 +386,55 @@ class Scene:
                 if n:                                   # (an empty tensor's data_ptr() is 0: nothing to call)
                     _check(lib.frayhip_shade_rays_device(self._dev, n, o.data_ptr(), d.data_ptr(), C.byref(req), rgb.data_ptr(), call.handle, C.byref(st)))
         return (rgb, st.as_dict()) if stats else rgb
+
+    # ---- adaptive frames (include/frayhip.h "adaptive frames") ----
+    def _adaptive_request(self, threshold, min_spp, err_floor):
+        """Checks the caller's values as the library does and clamps min_spp to the frame's spp."""
+        threshold, err_floor, min_spp = float(threshold), float(err_floor), int(min_spp)
+        if min_spp < 2:
+            raise ValueError("render_adaptive: min_spp must be >= 2, got %d" % min_spp)
+        if math.isnan(threshold) or threshold < 0:
+            raise ValueError("render_adaptive: threshold must be >= 0 (inf allowed), got %r" % threshold)
+        if not (math.isfinite(err_floor) and err_floor > 0):
+            raise ValueError("render_adaptive: err_floor must be finite and > 0, got %r" % err_floor)
+        return abi.Adaptive(min_spp=min(min_spp, self.samples_per_pixel()), threshold=threshold, err_floor=err_floor)
+
+    def render_adaptive(self, threshold, min_spp=16, err_floor=0.01, seed=42, bucket_first=0, bucket_stride=1, spp_chunk=0, stats=False, out=None):
+        """An adaptive path-traced frame (frayhip_render_adaptive): every pixel climbs the sample ladder floor(min_spp / 2), min_spp, 2 min_spp, ...,
+        spp and stops at the first rung from min_spp on whose noise estimate |m - h|_1 / (err_floor + sum(m)) is <= threshold (m, h: its mean at
+        this rung and the one before).  Each pixel equals, bit for bit, that pixel of the frame rendered at its final sample count.
+
+        Returns (rgb float32 [H, W, 3], spp int32 [H, W], err float32 [H, W], info); info holds "rungs" (ladder rungs run), "samples" (the sum
+        of spp over the call's pixels) and "stats" (the stats dict).  min_spp is clamped to the frame's spp.  out: (rgb, spp, err) arrays to fill
+        instead of new zeroed ones (pixels outside the call's buckets keep their values).  The defaults of min_spp and err_floor are starting
+        values, not tuned ones."""
+        a = self._adaptive_request(threshold, min_spp, err_floor)
+        self._need_dev()
+        W, H = self.frame_size
+        if out is None:
+            out = (np.zeros((H, W, 3), np.float32), np.zeros((H, W), np.int32), np.zeros((H, W), np.float32))
+        rgb, spp, err = out
+        for arr, shape, dt in ((rgb, (H, W, 3), np.float32), (spp, (H, W), np.int32), (err, (H, W), np.float32)):
+            if arr.shape != shape or arr.dtype != dt or not arr.flags.c_contiguous:
+                raise ValueError("render_adaptive: out arrays must be C-contiguous %s %s" % (shape, np.dtype(dt).name))
+        st = abi.Stats()
+        fr = self._frame(abi.MODE_RENDER, seed, bucket_first, bucket_stride, spp_chunk, stats)
+        _check(lib.frayhip_render_adaptive(self._dev, C.byref(fr), C.byref(a), rgb.ctypes.data, spp.ctypes.data, err.ctypes.data, C.byref(st)))
+        return rgb, spp, err, {"rungs": a.rungs, "samples": a.samples, "stats": st.as_dict()}
+
+    def render_adaptive_device(self, d_rgb_ptr, d_spp_ptr=None, d_err_ptr=None, *, threshold, min_spp=16, err_floor=0.01, seed=42,
+                               bucket_first=0, bucket_stride=1, spp_chunk=0, stats=False, stream=None):
+        """render_adaptive into caller-owned device memory (e.g. torch tensors' data_ptr(): rgb [H, W, 3] float32, spp [H, W] int32, err [H, W]
+        float32; spp / err may be None), enqueued on `stream` (a torch stream or a hipStream_t handle; None = the default stream) as render_device.
+        Returns the info dict of render_adaptive."""
+        a = self._adaptive_request(threshold, min_spp, err_floor)
+        self._need_dev()
+        if stream is not None and hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        st = abi.Stats()
+        fr = self._frame(abi.MODE_RENDER, seed, bucket_first, bucket_stride, spp_chunk, stats)
+        _check(lib.frayhip_render_device_adaptive(self._dev, C.byref(fr), C.byref(a), d_rgb_ptr, d_spp_ptr, d_err_ptr, stream, C.byref(st)))
+        return {"rungs": a.rungs, "samples": a.samples, "stats": st.as_dict()}
 
     def close(self):
         self.endRender()

@@ -463,6 +463,55 @@ int  frayhip_shade_rays(frayhip_scene* s, int64_t n, const double* origin, const
 int  frayhip_shade_rays_device(frayhip_scene* s, int64_t n, const double* d_origin, const double* d_dir,
                                const frayhip_shade_request* r, float* d_rgb, void* hip_stream, frayhip_stats* st);
 
+/* ---- adaptive frames (per-pixel sample counts for a path-traced frame) ---------------------------------------------------------------------
+ * A path-traced, mono frame (settings.gi on, camera.stereoSeparation == 0) over the call's buckets (frame.bucket_first / bucket_stride, as
+ * frayhip_render) in which every pixel takes only as many samples as its own noise estimate asks for.  spp is the frame's sample count
+ * (main.cpp:395-400: the largest of 5 with wantAA or 1, numDOFSamples with DOF, numPaths); min_spp is the caller's, 2 <= min_spp <= spp.
+ *
+ * Ladder.  Sample counts go up r_0 = floor(min_spp / 2), r_1 = min_spp, r_{j+1} = min(2 * r_j, spp), ending at the first rung equal to spp.
+ *   Every pixel runs rungs 0 and 1.  Sample i of a pixel is seeded independently of the frame's spp and the per-pixel FP32 sum runs in sample
+ *   order, so a pixel's mean after r samples IS that pixel of the frame of r samples per pixel, bit for bit.
+ * Error at rung j >= 1.  m = the pixel's mean after r_j samples, h = its mean after r_{j-1} samples (FP32 triples).  In double, no contraction,
+ *   each FP32 operand widened to double first:
+ *       num = (|m.r - h.r| + |m.g - h.g|) + |m.b - h.b|
+ *       den = err_floor + ((m.r + m.g) + m.b)
+ *       err = num / den
+ *   Below the cap r_j = 2 r_{j-1}, so m - h is half the difference of two independent half-estimates: the two-buffer noise estimate without
+ *   a second buffer.
+ * Stopping.  A pixel stops at the first rung j >= 1 where err <= threshold, or where r_j == spp.  A NaN error never stops a pixel early.
+ * Outputs, per pixel of the call's buckets: rgb[3] = the mean at the pixel's final rung (= frayhip_render of the same scene with spp := r_final,
+ *   bit for bit); spp_out = r_final; err_out = (float)err at the final rung.  Pixels outside the call's buckets are untouched in all three
+ *   buffers.  The decision is per pixel (no neighbourhood), so calls over disjoint buckets make up the whole frame's call exactly.
+ * Arithmetic: always the exact kernels.  Option fp_contract does not apply (its kernels are never launched, and "contracted_launches" reads 0
+ *   afterwards): with fp_contract = 1 the outputs equal those with fp_contract = 0.
+ * Black frames: with maxTraceDepth < 0 every pixel is 0, with spp_out = min_spp and err_out = 0 (rungs = 2).
+ * Batching: results do not depend on frame.spp_chunk (the most samples per pixel in one batch; 0 = auto), option pt_budget_mib or pt_lanes,
+ *   nor on the order of the active pixels.  All work of a call runs on one stream.
+ * frame: mode must be FRAYHIP_MODE_RENDER; FRAYHIP_FRAME_STATS selects the counting kernel variants.  *st may be NULL; when given it holds
+ *   ms_total, ms_kernels, samples (== a->samples, with or without the flag), ms_trace / trace_launches (k_pt_bounce), ms_shadow /
+ *   shadow_launches (k_pt_shadow) and, with the flag, the work counters.  The alg_* fields stay 0.
+ * rgb is required (W*H*3); spp_out (W*H int32) and err_out (W*H float) may be NULL.  The _device entry takes DEVICE pointers and follows
+ *   frayhip_render_device's stream contract (enqueued on hip_stream, NULL = default stream; returns after it has been synchronised).
+ * FRAYHIP_E_ARG, before the device is touched, with the reason in frayhip_last_error(): a NULL scene, frame, request or rgb; mode !=
+ *   FRAYHIP_MODE_RENDER; min_spp < 2 or min_spp > spp; a NaN or negative threshold; an err_floor that is not finite and positive; bucket
+ *   arguments that frayhip_render refuses; a call on a scene whose frame is being rendered.
+ * FRAYHIP_E_UNSUPPORTED: gi off (Whitted); stereo; long generators (8 + 10 * (maxTraceDepth + 2) > 227 words, i.e. maxTraceDepth >= 20),
+ *   refused for frayhip_shade_rays' reason: their kernel derives a path's seed from the frame's dense pixel slots. */
+typedef struct frayhip_adaptive {
+    int32_t  min_spp;        /* in:  2 <= min_spp <= the frame's spp                                  */
+    int32_t  _pad;
+    double   threshold;      /* in:  >= 0 (+inf allowed: every pixel stops at min_spp)               */
+    double   err_floor;      /* in:  > 0 and finite: the error's denominator floor                    */
+    int32_t  rungs;          /* out: ladder rungs run, r_0 included                                   */
+    int32_t  _pad2;
+    uint64_t samples;        /* out: sum of spp_out over the call's pixels                            */
+} frayhip_adaptive;
+
+int  frayhip_render_adaptive(frayhip_scene* s, const frayhip_frame* f, frayhip_adaptive* a,
+                             float* rgb, int32_t* spp_out, float* err_out, frayhip_stats* st);
+int  frayhip_render_device_adaptive(frayhip_scene* s, const frayhip_frame* f, frayhip_adaptive* a,
+                                    float* d_rgb, int32_t* d_spp, float* d_err, void* hip_stream, frayhip_stats* st);
+
 /* Multi-GPU tile exchange helpers.  pack: gathers this rank's buckets from a
  * full-frame device buffer into a compact bucket-major buffer of
  * frayhip_bucket_count(W,H,first,stride) * 48*48*channels floats; unpack is the inverse and
