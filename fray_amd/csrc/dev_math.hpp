@@ -54,8 +54,18 @@ FD void stamp_begin()
 
 // Division, reciprocal, square root.  FRAY_ARITH == 0 (every translation unit but render_contract.hip): IEEE, the reference's.  FRAY_ARITH == 1 (the
 // path tracer's kernels for rays after a sample's first closest hit, option "fp_contract"): the hardware's reciprocal / reciprocal square root with the two
-// refinement steps the IEEE expansions start with, but without their scaling, fix-up and final correction -- results within an ulp or two, 5 and 9
-// instructions instead of 13 and 17.  (Operands here are lengths, determinants and direction components: never subnormal, never huge.)
+// refinement steps the IEEE expansions start with, but without their scaling, fix-up and final correction, 5 and 9 instructions instead of 13 and 17.
+// What tests/test_gpu_contract.py pins (through frayhip_debug_arith, built with these kernels): on normal operands with normal results, over
+// [2^-1000, 2^1000], fray_rcp / fray_div / fray_rsqrt / fray_sqrt are within two ulps of the correctly rounded value (measured: one); normalized() and
+// visible()'s segment direction within two ulps per component and | |n|^2 - 1 | <= 2^-50 (the unit length node_intersect's untransformed-node shortcut
+// relies on); the relaxed sin / cos of dev_trig.hpp within 2^-51 absolute on [0, 2 pi).
+// Special operands differ from IEEE: fray_rcp / fray_div of +-0, +-inf or the smallest subnormal, fray_rsqrt of +-0 or +inf, fray_sqrt of +inf give NaN
+// (the refinement's -x * r is 0 * inf).  No call site reaches a difference that matters: the divisors are |Dcr| >= 1e-12 (tri_test masks the other lanes,
+// tri_bary only sees winners), |d| > 1e-12 (ray_rdir), a plane's |d.y| after the early returns (0 only when the numerator is 0 too: NaN either way), a
+// light's ldir.y > 0, max(1, q) and a solid angle != 0 (checked before fray_rcp) or a constant; visible()'s maxDist is 0 only for a == b, where
+// nothing can be closer than 0 whatever the direction; normalized(0) is NaN under IEEE as well (0 * inf); fray_sqrt keeps +-0 and its operands are
+// Disc >= 0, 1 - v^2 and squared lengths of finite scene vectors, never +inf.  Nonzero components of unit directions and scene-scale sums of products
+// are far above 2^-1022, so no operand is subnormal.
 #ifndef FRAY_ARITH
 #define FRAY_ARITH 0
 #endif

@@ -296,7 +296,11 @@ int  frayhip_scene_set_view(frayhip_scene* s, const frayhip_camera* camera, cons
  *                          -ffp-contract=fast, reciprocal / reciprocal-square-root with two refinement steps, plain-double sin / cos, and
  *                          sqrt(1 - c^2) for sin(acos c).  Primary hit records (MODE_PRIMARY_ID) and a sample's first bounce stay exact; shaded colour
  *                          stays inside 1e-4 RMS per channel (measured: 0 of 2 073 600 pixels of the 1080p x 64 spp Cornell frame differ at all, since
- *                          FP64 differences of 1e-16 vanish where geometry becomes an FP32 colour factor); cornell 1080p x 64 spp 92.4 -> 81.6 ms
+ *                          FP64 differences of 1e-16 vanish where geometry becomes an FP32 colour factor); cornell 1080p x 64 spp 92.4 -> 81.6 ms.
+ *                          Where the option does nothing: scenes with Cube / CSG geometry have no contracted kernels (their frames are the exact
+ *                          ones, "contracted_launches" 0), nor do Whitted frames (gi 0) or primary hit records; frames whose paths may draw more
+ *                          than 227 random words per generator (maxTraceDepth >= 20: per-path generator state) keep every bounce exact and run
+ *                          only the next-event visibility queries contracted.  tests/test_gpu_contract.py holds all of this and the primitives' bounds.
  * The environment variables FRAYHIP_PT_LANES / FRAYHIP_PT_BUDGET_MIB / FRAYHIP_SPECULATE_FANS / FRAYHIP_FP_CONTRACT preset them at frayhip_scene_create. */
 int  frayhip_scene_set_option(frayhip_scene* s, const char* name, int64_t value);
 /* Reads an option back, or one of the last frame's read-only figures: "fans_filed" (camera samples whose first fan was drawn ahead),
@@ -573,6 +577,17 @@ int  frayhip_debug_rng(uint32_t seed, int n, float* floats, double* doubles, int
  * equal the host's.  fold(x) = x - 2*floor(x/2) - 1 in [-1, 1) is returned in acos_arg.  Host buffers of n doubles,
  * any output may be NULL. */
 int  frayhip_debug_libm(int n, const double* x, double* sin_out, double* cos_out, double* acos_out, double* acos_arg);
+
+/* Test hook: the relaxed arithmetic of option "fp_contract" (the kernels of fray_amd/csrc/render_contract.hip, built with -ffp-contract=fast
+ * -DFRAY_ARITH=1; this entry lives in the same build and calls the same inline functions) on caller-supplied operands, item i < n:
+ *   op 0: out[i] = fray_rcp(a[i])          op 1: out[i] = fray_div(a[i], b[i])
+ *   op 2: out[i] = fray_rsqrt(a[i])        op 3: out[i] = fray_sqrt(a[i])
+ *   op 4: out[3i..3i+2] = normalized(a[3i..3i+2])
+ *   op 5: out[3i..3i+2] = the direction visible(a, b) traces along: d = b - a, d * fray_rcp(length(d)) (a, b: points of 3 doubles)
+ *   op 6: out[2i], out[2i+1] = the relaxed fray_sincos(a[i]): sin, cos
+ *   op 7: out[2i], out[2i+1] = fray_acos_sincos(a[i]): sin(acos v), cos(acos v)
+ * Host buffers; b is read by ops 1 and 5 only.  n <= 2^22.  FRAYHIP_E_ARG for a bad op, n or buffer. */
+int  frayhip_debug_arith(int op, int n, const double* a, const double* b, double* out);
 
 const char* frayhip_last_error(void);
 int  frayhip_abi_version(void);
