@@ -32,8 +32,11 @@ QUERY_OBJ := $(foreach st,0 1 2 3 4 5 8 9,fray_amd/csrc/query$(st).o)
 SHADE_OBJ := $(foreach st,0 1 2 3 4 5 8 9,fray_amd/csrc/shade$(st).o)
 # adaptive_variant.hip: adaptive frames (frayhip_render_adaptive) per flag word, in objects of their own as well
 ADAPTIVE_OBJ := $(foreach st,0 1 2 3 4 5 8 9,fray_amd/csrc/adaptive$(st).o)
+# features_variant.hip: feature frames (frayhip_render_features) per flag word, in objects of their own as well
+FEATURES_OBJ := $(foreach st,0 1 2 3 4 5 8 9,fray_amd/csrc/features$(st).o)
 HIP_OBJ  := fray_amd/csrc/capi.o fray_amd/csrc/capi_comm.o fray_amd/csrc/capi_query.o fray_amd/csrc/capi_shade.o fray_amd/csrc/capi_adaptive.o \
-            $(VARIANT_OBJ) $(CONTRACT_OBJ) $(QUERY_OBJ) $(SHADE_OBJ) $(ADAPTIVE_OBJ)
+            fray_amd/csrc/capi_features.o fray_amd/csrc/denoise.o \
+            $(VARIANT_OBJ) $(CONTRACT_OBJ) $(QUERY_OBJ) $(SHADE_OBJ) $(ADAPTIVE_OBJ) $(FEATURES_OBJ)
 HIP_HDR  := $(wildcard fray_amd/csrc/*.h) $(wildcard fray_amd/csrc/*.hpp) include/frayhip.h
 
 all: fray_amd/libfrayhip.so oracle/libfray_oracle.so examples/fray_render examples/fray_render_mgpu tests/native/librccl_loopback.so ref
@@ -57,6 +60,13 @@ fray_amd/csrc/shade%.o: fray_amd/csrc/shade_variant.hip $(HIP_HDR)
 
 fray_amd/csrc/adaptive%.o: fray_amd/csrc/adaptive_variant.hip $(HIP_HDR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -DFRAY_ST=$* -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> fray_amd/csrc/adaptive$*.resources.txt || (cat fray_amd/csrc/adaptive$*.resources.txt; false)
+
+fray_amd/csrc/features%.o: fray_amd/csrc/features_variant.hip $(HIP_HDR)
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -DFRAY_ST=$* -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> fray_amd/csrc/features$*.resources.txt || (cat fray_amd/csrc/features$*.resources.txt; false)
+
+# the denoiser (scene-free): FP32 without contraction whatever EXTRA_HIPFLAGS say (the last -ffp-contract on the command line wins)
+fray_amd/csrc/denoise.o: fray_amd/csrc/denoise.hip $(HIP_HDR)
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -ffp-contract=off -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> fray_amd/csrc/denoise.resources.txt || (cat fray_amd/csrc/denoise.resources.txt; false)
 
 # (the last -ffp-contract on the command line wins)
 fray_amd/csrc/variantC%.o: fray_amd/csrc/render_contract.hip $(HIP_HDR)
@@ -85,8 +95,9 @@ tests/native/librccl_loopback.so: tests/native/rccl_loopback.cpp
 ref:
 	@if [ -d /root/reference/src ]; then $(MAKE) -C oracle -f Makefile.ref; else echo "reference tree absent: oracle/_ref not rebuilt"; fi
 
-resources: $(VARIANT_OBJ) $(QUERY_OBJ) $(SHADE_OBJ) $(ADAPTIVE_OBJ)
-	python3 tools/kernel_resources.py fray_amd/csrc/variant*.resources.txt fray_amd/csrc/query*.resources.txt fray_amd/csrc/shade*.resources.txt fray_amd/csrc/adaptive*.resources.txt
+resources: $(VARIANT_OBJ) $(QUERY_OBJ) $(SHADE_OBJ) $(ADAPTIVE_OBJ) $(FEATURES_OBJ) fray_amd/csrc/denoise.o
+	python3 tools/kernel_resources.py fray_amd/csrc/variant*.resources.txt fray_amd/csrc/query*.resources.txt fray_amd/csrc/shade*.resources.txt fray_amd/csrc/adaptive*.resources.txt \
+	    fray_amd/csrc/features*.resources.txt fray_amd/csrc/denoise.resources.txt
 
 clean:
 	rm -f fray_amd/csrc/*.o fray_amd/csrc/*.resources.txt fray_amd/libfrayhip.so oracle/libfray_oracle.so examples/fray_render examples/fray_render_mgpu tests/native/librccl_loopback.so

@@ -3,7 +3,9 @@ src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --he
                          python -m fray_amd scene.fray --probe X Y [--shade] [--width W --height H]   (one JSON line: what the camera ray through pixel X, Y hits;
                                                                                           --shade: and its colour)
                          python -m fray_amd scene.fray -o out.bmp --adaptive THRESHOLD [--min-spp N] [--adaptive-floor F]   (an adaptive frame, and one
-                                                                                          JSON line: its rungs, mean spp and the share of pixels per rung)"""
+                                                                                          JSON line: its rungs, mean spp and the share of pixels per rung)
+                         python -m fray_amd scene.fray -o out.bmp --denoise [--feature-samples N] [--features-out FILE.npy]   (the frame denoised
+                                                                                          with its first-hit features; --features-out alone saves them)"""
 import argparse
 import json
 import sys
@@ -36,7 +38,22 @@ def build_parser():
     ap.add_argument("--min-spp", type=int, default=16, metavar="N", help="with --adaptive: the smallest sample count a pixel stops at (default 16)")
     ap.add_argument("--adaptive-floor", type=float, default=0.01, metavar="F",
                     help="with --adaptive: the floor added to the pixel's brightness in the error's denominator (default 0.01)")
+    ap.add_argument("--denoise", action="store_true",
+                    help="write the frame denoised (Scene.render_denoised: first-hit features, the half-spp frame as the noise estimate, "
+                         "the a-trous filter with its default parameters); not with --adaptive or --time-limit")
+    ap.add_argument("--feature-samples", type=int, default=4, metavar="N",
+                    help="camera samples per pixel of the feature frame (--denoise, --features-out; clamped to the frame's spp; default 4)")
+    ap.add_argument("--features-out", metavar="FILE.npy",
+                    help="also save the feature frame, float32 [H, W, 10]: position, normal, albedo, depth")
     return ap
+
+
+def check_args(ap, a):
+    """Refuses combinations the CLI does not render (before the scene is loaded)."""
+    if a.denoise and a.adaptive is not None:
+        ap.error("--denoise cannot be combined with --adaptive: denoising adaptive frames is not supported")
+    if a.denoise and a.time_limit is not None:
+        ap.error("--denoise cannot be combined with --time-limit: the denoiser needs the whole frame")
 
 
 def adaptive_summary(spp, info):
@@ -62,7 +79,9 @@ def probe(s, x, y, shade=False, seed=42):
 
 
 def main(argv=None):
-    a = build_parser().parse_args(argv)
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    check_args(ap, a)
     s = Scene.parseScene(a.scene)
     if a.width:
         s.settings.frameWidth = a.width
@@ -78,7 +97,15 @@ def main(argv=None):
         print(json.dumps(probe(s, a.probe[0], a.probe[1], a.shade, a.seed)))
         return 0
     t0 = time.time()
-    if a.adaptive is not None:
+    if a.denoise:
+        img, raw, info = s.render_denoised(seed=a.seed, feature_samples=a.feature_samples)
+        st = info["render"]
+        spp_text = "%d spp, denoised%s: features %.1f ms, filter %.1f ms" % (
+            s.samples_per_pixel(), "" if info["rgb_half"] is not None else " without the half-spp estimate",
+            info["features"]["ms_kernels"], info["denoise"]["ms_kernels"])
+        if a.features_out:
+            np.save(a.features_out, info["features_frame"])
+    elif a.adaptive is not None:
         img, spp_map, _err, info = s.render_adaptive(a.adaptive, min_spp=a.min_spp, err_floor=a.adaptive_floor, seed=a.seed)
         st = info["stats"]
         print(json.dumps(adaptive_summary(spp_map, info)))
@@ -103,6 +130,9 @@ def main(argv=None):
         img, st = s.render(seed=a.seed)
         spp_text = "%d spp" % s.samples_per_pixel()
     print("Render took %.2fs (%d x %d, %s, kernels %.1f ms)" % (time.time() - t0, img.shape[1], img.shape[0], spp_text, st["ms_kernels"]))
+    if a.features_out and not a.denoise:
+        np.save(a.features_out, s.render_features(min(a.feature_samples, s.samples_per_pixel()), seed=a.seed))
+        print("wrote", a.features_out)
     rc = lib.frayhip_save_bmp(a.output.encode(), img.ctypes.data, img.shape[1], img.shape[0])
     if rc:
         print(lib.frayhip_last_error().decode(), file=sys.stderr)

@@ -169,6 +169,15 @@ class Adaptive(C.Structure):
                 ("samples", u64)]
 
 
+# struct frayhip_denoise (a struct tag without a typedef: the name is also the entry point's, so it is not in STRUCTS, which mirrors the typedefs)
+class Denoise(C.Structure):
+    _fields_ = [("levels", i32), ("demodulate", i32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float)]
+
+
+FEAT_CHANNELS = 10      # FRAYHIP_FEAT_CHANNELS: position[3], normal[3], albedo[3], depth
+
+
 STRUCTS = {"frayhip_transform": Transform, "frayhip_geom_ref": GeomRef, "frayhip_node": Node,
            "frayhip_plane": Plane, "frayhip_sphere": Sphere, "frayhip_cube": Cube,
            "frayhip_csg": Csg, "frayhip_triangle": Triangle, "frayhip_kdnode": KDNode,
@@ -197,6 +206,11 @@ SYMBOLS = {
     "frayhip_render_device_progressive": (C.c_int, [VP, P(Frame), P(Progressive), VP, VP, VP, VP, P(Stats)]),
     "frayhip_render_adaptive": (C.c_int, [VP, P(Frame), P(Adaptive), VP, VP, VP, P(Stats)]),
     "frayhip_render_device_adaptive": (C.c_int, [VP, P(Frame), P(Adaptive), VP, VP, VP, VP, P(Stats)]),
+    "frayhip_render_features": (C.c_int, [VP, P(Frame), C.c_int, VP, P(Stats)]),
+    "frayhip_render_features_device": (C.c_int, [VP, P(Frame), C.c_int, VP, VP, P(Stats)]),
+    "frayhip_denoise_defaults": (C.c_int, [P(Denoise)]),
+    "frayhip_denoise": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(Denoise), VP, P(Stats)]),
+    "frayhip_denoise_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(Denoise), VP, VP, P(Stats)]),
     "frayhip_camera_rays": (C.c_int, [VP, i64, VP, C.c_int, VP, VP]),
     "frayhip_camera_rays_device": (C.c_int, [VP, i64, VP, C.c_int, VP, VP, VP]),
     "frayhip_trace_rays": (C.c_int, [VP, i64, VP, VP, C.c_int, VP, VP, VP, P(Stats)]),

@@ -1,0 +1,26 @@
+// Feature frames (include/frayhip.h: frayhip_render_features): what the C entry points (capi_features.hip) hand to the kernel of
+// features_variant.hip, which the Makefile compiles once per kernel flag word as it does query_variant.hip.
+#pragma once
+#include "render_state.hpp"
+
+namespace frayhip_detail {
+
+// One launch over the frame's work items (8x8 tiles of its buckets); n samples per pixel, averaged in sample order
+struct FeatureArgs {
+    DScene S;
+    DCamera C;
+    DFrame F;
+    int nItems;
+    int n;
+    float* feat;             // [H][W][FRAYHIP_FEAT_CHANNELS], device
+    DStats* st;
+    DCursors* cur;           // zeroed work cursors (claim_items)
+};
+
+template <int ST> void launch_features(hipStream_t stream, const FeatureArgs& A);
+#define FRAY_FEATURES_EXTERN(st) extern template void launch_features<st>(hipStream_t, const FeatureArgs&);
+FRAY_FEATURES_EXTERN(0) FRAY_FEATURES_EXTERN(1) FRAY_FEATURES_EXTERN(2) FRAY_FEATURES_EXTERN(3)
+FRAY_FEATURES_EXTERN(4) FRAY_FEATURES_EXTERN(5) FRAY_FEATURES_EXTERN(8) FRAY_FEATURES_EXTERN(9)
+#undef FRAY_FEATURES_EXTERN
+
+}  // namespace frayhip_detail

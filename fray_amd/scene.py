@@ -144,6 +144,65 @@ class _DeviceCall:
         return C.c_void_p(self.stream.cuda_stream)
 
 
+_DENOISE_FIELDS = ("levels", "demodulate", "sigma_luminance", "sigma_normal", "sigma_depth", "sigma_albedo")
+
+
+def denoise_params(**params):
+    """frayhip_denoise_defaults, with the named fields replaced (levels, demodulate, sigma_luminance, sigma_normal, sigma_depth, sigma_albedo)."""
+    p = abi.Denoise()
+    _check(lib.frayhip_denoise_defaults(C.byref(p)))
+    for k, v in params.items():
+        if k not in _DENOISE_FIELDS:
+            raise TypeError("denoise: unknown parameter %r (known: %s)" % (k, ", ".join(_DENOISE_FIELDS)))
+        setattr(p, k, v)
+    return p
+
+
+def denoise(rgb, feat, rgb_half=None, stats=False, stream=None, **params):
+    """The edge-avoiding a-trous filter of include/frayhip.h (frayhip_denoise): rgb [H, W, 3] float32, feat [H, W, 10] float32 (render_features),
+    rgb_half [H, W, 3] float32 or None (the frame of the first half of rgb's samples: the filter's noise estimate).  numpy arrays go through the
+    host entry; torch tensors on the GPU through the device entry, on `stream` (None: the current stream).  params: see denoise_params.
+    Returns the filtered frame (same kind as rgb), and with stats=True also the stats dict (ms_total, ms_kernels)."""
+    p = denoise_params(**params)
+    named = [("rgb", rgb, 3), ("feat", feat, abi.FEAT_CHANNELS)] + ([("rgb_half", rgb_half, 3)] if rgb_half is not None else [])
+    tensors = [_torch_tensor(v) for _, v, _ in named]
+    if any(tensors) and not all(tensors):
+        raise TypeError("denoise: pass numpy arrays or torch tensors, not a mix")
+    shape = None
+    ins = []
+    for name, v, width in named:
+        if tensors[0]:
+            import torch
+            if not v.is_cuda:
+                raise TypeError("denoise: %s is a CPU tensor; pass a tensor on the GPU (device entry) or a numpy array (host entry)" % name)
+            if v.dtype != torch.float32:
+                raise TypeError("denoise: %s must be float32, got %s" % (name, v.dtype))
+            v = v.contiguous()
+        else:
+            v = np.ascontiguousarray(v)
+            if v.dtype != np.float32:
+                raise TypeError("denoise: %s must be float32, got %s" % (name, v.dtype))
+        if v.ndim != 3 or v.shape[2] != width:
+            raise ValueError("denoise: %s must be shaped [H, W, %d], got %s" % (name, width, tuple(v.shape)))
+        if shape is not None and tuple(v.shape[:2]) != shape:
+            raise ValueError("denoise: the inputs' sizes differ: %s and %s" % (shape, tuple(v.shape[:2])))
+        shape = tuple(v.shape[:2])
+        ins.append(v)
+    H, W = shape
+    half = ins[2] if rgb_half is not None else None
+    st = abi.Stats()
+    if not tensors[0]:
+        out = np.empty((H, W, 3), np.float32)
+        _check(lib.frayhip_denoise(W, H, ins[0].ctypes.data, half.ctypes.data if half is not None else None, ins[1].ctypes.data, C.byref(p),
+                                   out.ctypes.data, C.byref(st)))
+    else:
+        with _DeviceCall(ins[0].device, stream) as call:
+            out = call.torch.empty((H, W, 3), dtype=call.torch.float32, device=ins[0].device)
+            _check(lib.frayhip_denoise_device(W, H, ins[0].data_ptr(), half.data_ptr() if half is not None else None, ins[1].data_ptr(), C.byref(p),
+                                              out.data_ptr(), call.handle, C.byref(st)))
+    return (out, st.as_dict()) if stats else out
+
+
 class Scene:
     """`Scene scene` of the reference (scene.h:280-299).
 
@@ -435,6 +494,50 @@ class Scene:
         fr = self._frame(abi.MODE_RENDER, seed, bucket_first, bucket_stride, spp_chunk, stats)
         _check(lib.frayhip_render_device_adaptive(self._dev, C.byref(fr), C.byref(a), d_rgb_ptr, d_spp_ptr, d_err_ptr, stream, C.byref(st)))
         return {"rungs": a.rungs, "samples": a.samples, "stats": st.as_dict()}
+
+    # ---- feature frames and denoising (include/frayhip.h "feature frames", "denoising") ----
+    def render_features(self, n_samples=4, seed=42, bucket_first=0, bucket_stride=1, stats=False, out=None):
+        """First-hit features of the frame's camera samples 0 .. n_samples-1 (frayhip_render_features): float32 [H, W, 10] -- position[3],
+        normal[3] (after the bump), albedo[3], depth -- the FP32 mean in sample order.  out: an array to fill instead of a new zeroed one (pixels
+        outside the call's buckets keep their values).  With stats=True returns (feat, stats dict)."""
+        self._need_dev()
+        W, H = self.frame_size
+        feat = out if out is not None else np.zeros((H, W, abi.FEAT_CHANNELS), np.float32)
+        if feat.shape != (H, W, abi.FEAT_CHANNELS) or feat.dtype != np.float32 or not feat.flags.c_contiguous:
+            raise ValueError("render_features: out must be a C-contiguous float32 array shaped %s" % ((H, W, abi.FEAT_CHANNELS),))
+        st = abi.Stats()
+        fr = self._frame(abi.MODE_RENDER, seed, bucket_first, bucket_stride, 0, stats)
+        _check(lib.frayhip_render_features(self._dev, C.byref(fr), int(n_samples), feat.ctypes.data, C.byref(st)))
+        return (feat, st.as_dict()) if stats else feat
+
+    def render_denoised(self, seed=42, feature_samples=4, **params):
+        """A denoised frame: (denoised, raw, stats).  raw is the ordinary frame (= render(seed), bit for bit), rendered progressively; with an even
+        spp >= 2 its preview at spp / 2 samples is the filter's rgb_half (the exact spp/2 frame, no second render), otherwise the filter runs without
+        it.  The features take min(feature_samples, spp) samples.  params: denoise_params.  stats: the "render", "features" and "denoise" stats dicts,
+        and the filter's inputs "rgb_half" (None without it) and "features_frame"."""
+        self._need_dev()
+        W, H = self.frame_size
+        spp = self.samples_per_pixel()
+        half = None
+        chunk = 0
+        if spp >= 2 and spp % 2 == 0:
+            hs = spp // 2
+            chunk = max(d for d in range(1, min(hs, 8) + 1) if hs % d == 0)     # batches end at spp / 2; at most 8 spp per batch
+        half_wanted = chunk > 0
+        keep = {}
+
+        def progress(info):
+            if half_wanted and info["preview"] and info["samples_done"] == spp // 2:
+                keep["half"] = info["image"].copy()
+            return False
+        raw, rst = self.render(seed=seed, spp_chunk=chunk, progress=progress, preview_ms=0 if half_wanted else -1)
+        if half_wanted:
+            half = keep.get("half")
+            if half is None:
+                raise FrayError(abi.E_HIP, "render_denoised: no preview at spp / 2 = %d samples" % (spp // 2))
+        feat, fst = self.render_features(min(int(feature_samples), spp), seed=seed, stats=True)
+        out, dst = denoise(raw, feat, half, stats=True, **params)
+        return out, raw, {"render": rst, "features": fst, "denoise": dst, "rgb_half": half, "features_frame": feat}
 
     def close(self):
         self.endRender()

@@ -516,6 +516,74 @@ int  frayhip_render_adaptive(frayhip_scene* s, const frayhip_frame* f, frayhip_a
 int  frayhip_render_device_adaptive(frayhip_scene* s, const frayhip_frame* f, frayhip_adaptive* a,
                                     float* d_rgb, int32_t* d_spp, float* d_err, void* hip_stream, frayhip_stats* st);
 
+/* ---- feature frames (first-hit guides for a denoiser) ---------------------------------------------------------------------------------------
+ * For every pixel of the call's buckets (frame.bucket_first / bucket_stride, as frayhip_render; other pixels untouched), the FP32 mean, in
+ * sample order, of the first-hit features of the frame's own camera samples 0 .. n_samples - 1: sample i is the film position and the pinhole
+ * or thin-lens ray that sample i of the MODE_RENDER frame traces, with the same seed (AA offsets for a Whitted frame with wantAA, jitter for gi
+ * or DOF).  Ten floats per pixel, feat[(y * W + x) * FRAYHIP_FEAT_CHANNELS + k]:
+ *   0..2 position, 3..5 normal, 6..8 albedo, 9 depth.
+ * Per sample:
+ *   node hit       position = IntersectionInfo.ip, normal = IntersectionInfo.norm after applyBumpMapping (not face-forwarded), depth = the
+ *                  world distance; albedo = the colour the shader starts from: Lambert / Phong color (times the diffuse texture's sample),
+ *                  Refl / Refr mult, Const color, Layered the blend of Layered::shade (shading.cpp:357-367) over its layers' albedos with the
+ *                  same opacities (opacity textures sampled as there; a Layered shader inside two enclosing Layered shaders counts as black)
+ *   rect-light hit position / normal as RectLight::intersect leaves them, depth = distance, albedo = the light's color
+ *   miss           position, normal, depth 0; albedo = the environment's colour in the ray's direction (black without an environment)
+ * Each feature is converted to float per sample and summed in float in sample order; the mean is sum / (float)n_samples.
+ * maxTraceDepth < 0: every feature of the call's pixels is 0.
+ * The call changes no option and none of the last frame's figures (contracted_launches, whitted_path, fan counters); fp_contract does not
+ *   apply.  *st may be NULL; when given it holds ms_total, ms_kernels, samples (n_samples per pixel of the call) and ms_trace /
+ *   trace_launches (k_features); with FRAYHIP_FRAME_STATS the counting kernel variant runs and the work counters are filled in.
+ * The _device entry takes a DEVICE pointer (4-byte aligned) and follows frayhip_render_device's stream contract.
+ * FRAYHIP_E_ARG, before the device is touched: a NULL scene, frame or feat; mode != FRAYHIP_MODE_RENDER; n_samples < 1 or > the frame's spp;
+ *   bucket arguments that frayhip_render refuses; a misaligned device pointer; a call on a scene whose frame is being rendered.
+ * FRAYHIP_E_UNSUPPORTED: stereo frames; path tracing with long generators (maxTraceDepth >= 20), refused for frayhip_shade_rays' reason --
+ *   the feature pass never answers for rays other than the frame's. */
+#define FRAYHIP_FEAT_CHANNELS 10   /* per pixel: position[3], normal[3], albedo[3], depth */
+int  frayhip_render_features(frayhip_scene* s, const frayhip_frame* f, int n_samples, float* feat, frayhip_stats* st);
+int  frayhip_render_features_device(frayhip_scene* s, const frayhip_frame* f, int n_samples, float* d_feat,
+                                    void* hip_stream, frayhip_stats* st);
+
+/* ---- denoising (edge-avoiding a-trous wavelet filter, scene-free) --------------------------------------------------------------------------
+ * A spatial SVGF-style filter of an rgb frame (W*H*3 floats) guided by a feature frame (W*H*FRAYHIP_FEAT_CHANNELS floats, as
+ * frayhip_render_features writes it), FP32 throughout, no contraction.  Level k = 0 .. levels - 1 takes the taps q = p + 2^k (i, j),
+ * i, j in -2..2 (j outer, i inner), skipping taps outside the image, with
+ *     w   = h * w_n * w_z * w_a * w_l          h: the B3-spline (1/16, 1/4, 3/8, 1/4, 1/16) outer product
+ *     w_n = max(0, n_p . n_q)^sigma_normal     on the normals scaled to unit length (a mean of several samples' normals is shorter);
+ *                                              0 when exactly one of the two normals is zero, 1 when both are
+ *     w_z = exp(-|z_p - z_q| / (sigma_depth * |grad z_p . (q - p)| + 1e-4))     z: depth; grad: central differences, one-sided at borders
+ *     w_a = exp(-|a_p - a_q|_1 / sigma_albedo)
+ *     w_l = exp(-|l_p - l_q| / (sigma_luminance * sqrt(max(0, var_p)) + 1e-4))  with rgb_half
+ *     w_l = exp(-|l_p - l_q| / (sigma_luminance * 2^-k))                        without it
+ * where l = (r + g + b) / 3 of the signal being filtered.  The level's output is c_p + sum(w (c_q - c_p)) / sum(w), which is
+ * sum(w c_q) / sum(w) written so that a flat region stays exactly flat; the centre tap is always included.
+ * Demodulation (demodulate = 1): the signal is rgb / max(albedo, 1e-3) per channel, and the last level multiplies max(albedo_p, 1e-3) back.
+ * Noise estimate with rgb_half (the frame of the first half of rgb's samples): var_p = (l(rgb_p) - l(rgb_half_p))^2, both sides demodulated
+ *   when demodulate is set, prefiltered with the 3x3 binomial kernel (1 2 1) x (1 2 1) / 16 normalised over the taps inside the image; after
+ *   each level var_p := sum(w^2 var_q) / (sum w)^2.
+ * Kernels: one launch that packs the guides, demodulates and prefilters the variance, then one launch per level (the last remodulates).
+ * Buffers: out (W*H*3) must not overlap rgb, rgb_half or feat.  Work buffers are allocated per call (FRAYHIP_E_NOMEM when that fails).  The
+ *   _device entry takes DEVICE pointers (4-byte aligned), enqueues on hip_stream and returns after synchronising it.
+ * *st may be NULL; when given it holds ms_total and ms_kernels (the other fields are 0).
+ * FRAYHIP_E_ARG, before the device is touched: width or height < 1 or W*H > 2^30; NULL rgb, feat, p or out; levels outside 1..10; demodulate
+ *   not 0 or 1; a NaN, infinite or negative sigma, or sigma_luminance, sigma_depth or sigma_albedo equal to 0; out overlapping an input. */
+/* A struct tag without a typedef: the name is also the entry point's, so C and C++ callers write `struct frayhip_denoise`. */
+struct frayhip_denoise {
+    int32_t levels;          /* a-trous iterations, step 2^k, k = 0..levels-1; 1..10, default 5                  */
+    int32_t demodulate;      /* 1: filter rgb / max(albedo, 1e-3) per channel and multiply back (default 1)       */
+    float   sigma_luminance; /* default 4                                                                          */
+    float   sigma_normal;    /* exponent on max(0, n_p . n_q), default 128                                         */
+    float   sigma_depth;     /* default 1                                                                          */
+    float   sigma_albedo;    /* default 0.1                                                                        */
+};
+int  frayhip_denoise_defaults(struct frayhip_denoise* p);
+int  frayhip_denoise(int width, int height, const float* rgb, const float* rgb_half, const float* feat,
+                     const struct frayhip_denoise* p, float* out, frayhip_stats* st);
+int  frayhip_denoise_device(int width, int height, const float* d_rgb, const float* d_rgb_half, const float* d_feat,
+                            const struct frayhip_denoise* p, float* d_out, void* hip_stream, frayhip_stats* st);
+/* Not covered: temporal reprojection, learned denoisers, adaptive and stereo frames, and denoising across ranks (gather the frame and its
+ * features first: frayhip_gather_buckets takes a channel count). */
+
 /* Multi-GPU tile exchange helpers.  pack: gathers this rank's buckets from a
  * full-frame device buffer into a compact bucket-major buffer of
  * frayhip_bucket_count(W,H,first,stride) * 48*48*channels floats; unpack is the inverse and
