@@ -21,22 +21,20 @@ CXXFLAGS := -O2 -std=c++17 -fPIC -ffp-contract=off $(INC)
 
 HOST_SRC := fray_amd/csrc/host_scene.cpp fray_amd/csrc/host_loaders.cpp fray_amd/csrc/host_exr.cpp fray_amd/csrc/capi_host.cpp
 HOST_OBJ := $(HOST_SRC:.cpp=.o)
-# render_variant.hip is compiled once per kernel flag word (render_impl<0..5, 8, 9>): eight independent translation
-# units that `make -j` builds side by side
-VARIANT_OBJ := $(foreach st,0 1 2 3 4 5 8 9,fray_amd/csrc/variant$(st).o)
+# One object per kernel flag word (FRAY_FOR_EACH_ST, entry_support.hpp) from each of these sources, so that `make -j` builds them side by side:
+#   variant<st>.o   render_variant.hip     render_impl<st>, the frame kernels
+#   query<st>.o     query_variant.hip      the ray query kernels (frayhip_trace_rays / frayhip_visible)
+#   shade<st>.o     shade_variant.hip      the radiance query (frayhip_shade_rays)
+#   adaptive<st>.o  adaptive_variant.hip   adaptive frames (frayhip_render_adaptive)
+#   features<st>.o  features_variant.hip   feature frames (frayhip_render_features)
+ST_WORDS := 0 1 2 3 4 5 8 9
+ST_SETS  := variant:render_variant query:query_variant shade:shade_variant adaptive:adaptive_variant features:features_variant
+ST_OBJ   := $(foreach set,$(ST_SETS),$(foreach st,$(ST_WORDS),fray_amd/csrc/$(firstword $(subst :, ,$(set)))$(st).o))
 # render_contract.hip: the path tracer's bounce / shadow kernels once more per flag word, built with fused multiply-adds (option "fp_contract")
 CONTRACT_OBJ := $(foreach st,0 1 4 5 8 9,fray_amd/csrc/variantC$(st).o)
-# query_variant.hip: the ray query kernels (frayhip_trace_rays / frayhip_visible) per flag word, in objects of their own beside the frame kernels
-QUERY_OBJ := $(foreach st,0 1 2 3 4 5 8 9,fray_amd/csrc/query$(st).o)
-# shade_variant.hip: the radiance query (frayhip_shade_rays) per flag word, in objects of their own as well
-SHADE_OBJ := $(foreach st,0 1 2 3 4 5 8 9,fray_amd/csrc/shade$(st).o)
-# adaptive_variant.hip: adaptive frames (frayhip_render_adaptive) per flag word, in objects of their own as well
-ADAPTIVE_OBJ := $(foreach st,0 1 2 3 4 5 8 9,fray_amd/csrc/adaptive$(st).o)
-# features_variant.hip: feature frames (frayhip_render_features) per flag word, in objects of their own as well
-FEATURES_OBJ := $(foreach st,0 1 2 3 4 5 8 9,fray_amd/csrc/features$(st).o)
 HIP_OBJ  := fray_amd/csrc/capi.o fray_amd/csrc/capi_comm.o fray_amd/csrc/capi_query.o fray_amd/csrc/capi_shade.o fray_amd/csrc/capi_adaptive.o \
             fray_amd/csrc/capi_features.o fray_amd/csrc/denoise.o \
-            $(VARIANT_OBJ) $(CONTRACT_OBJ) $(QUERY_OBJ) $(SHADE_OBJ) $(ADAPTIVE_OBJ) $(FEATURES_OBJ)
+            $(filter fray_amd/csrc/variant%,$(ST_OBJ)) $(CONTRACT_OBJ) $(filter-out fray_amd/csrc/variant%,$(ST_OBJ))
 HIP_HDR  := $(wildcard fray_amd/csrc/*.h) $(wildcard fray_amd/csrc/*.hpp) include/frayhip.h
 
 all: fray_amd/libfrayhip.so oracle/libfray_oracle.so examples/fray_render examples/fray_render_mgpu tests/native/librccl_loopback.so ref
@@ -47,22 +45,13 @@ fray_amd/csrc/%.o: fray_amd/csrc/%.cpp $(HIP_HDR)
 fray_amd/csrc/%.o: fray_amd/csrc/%.hip $(HIP_HDR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -c $< -o $@
 
-# -Rpass-analysis=kernel-resource-usage: registers, spills, scratch and LDS of every kernel of the variant (kept
-# next to the object; `make resources` gathers them into profiles/)
-fray_amd/csrc/variant%.o: fray_amd/csrc/render_variant.hip $(HIP_HDR)
-	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -DFRAY_ST=$* -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> fray_amd/csrc/variant$*.resources.txt || (cat fray_amd/csrc/variant$*.resources.txt; false)
-
-fray_amd/csrc/query%.o: fray_amd/csrc/query_variant.hip $(HIP_HDR)
-	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -DFRAY_ST=$* -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> fray_amd/csrc/query$*.resources.txt || (cat fray_amd/csrc/query$*.resources.txt; false)
-
-fray_amd/csrc/shade%.o: fray_amd/csrc/shade_variant.hip $(HIP_HDR)
-	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -DFRAY_ST=$* -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> fray_amd/csrc/shade$*.resources.txt || (cat fray_amd/csrc/shade$*.resources.txt; false)
-
-fray_amd/csrc/adaptive%.o: fray_amd/csrc/adaptive_variant.hip $(HIP_HDR)
-	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -DFRAY_ST=$* -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> fray_amd/csrc/adaptive$*.resources.txt || (cat fray_amd/csrc/adaptive$*.resources.txt; false)
-
-fray_amd/csrc/features%.o: fray_amd/csrc/features_variant.hip $(HIP_HDR)
-	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -DFRAY_ST=$* -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> fray_amd/csrc/features$*.resources.txt || (cat fray_amd/csrc/features$*.resources.txt; false)
+# The resource-usage remarks: registers, spills, scratch and LDS of every kernel of the object (kept next to the
+# object; `make resources` gathers them into profiles/).  $(1): object prefix, $(2): source
+define ST_RULE
+fray_amd/csrc/$(1)%.o: fray_amd/csrc/$(2).hip $$(HIP_HDR)
+	$$(HIPCC) $$(HIPFLAGS) $$(EXTRA_HIPFLAGS) -DFRAY_ST=$$* -Rpass-analysis=kernel-resource-usage -c $$< -o $$@ 2> fray_amd/csrc/$(1)$$*.resources.txt || (cat fray_amd/csrc/$(1)$$*.resources.txt; false)
+endef
+$(foreach set,$(ST_SETS),$(eval $(call ST_RULE,$(firstword $(subst :, ,$(set))),$(lastword $(subst :, ,$(set))))))
 
 # the denoiser (scene-free): FP32 without contraction whatever EXTRA_HIPFLAGS say (the last -ffp-contract on the command line wins)
 fray_amd/csrc/denoise.o: fray_amd/csrc/denoise.hip $(HIP_HDR)
@@ -95,9 +84,8 @@ tests/native/librccl_loopback.so: tests/native/rccl_loopback.cpp
 ref:
 	@if [ -d /root/reference/src ]; then $(MAKE) -C oracle -f Makefile.ref; else echo "reference tree absent: oracle/_ref not rebuilt"; fi
 
-resources: $(VARIANT_OBJ) $(QUERY_OBJ) $(SHADE_OBJ) $(ADAPTIVE_OBJ) $(FEATURES_OBJ) fray_amd/csrc/denoise.o
-	python3 tools/kernel_resources.py fray_amd/csrc/variant*.resources.txt fray_amd/csrc/query*.resources.txt fray_amd/csrc/shade*.resources.txt fray_amd/csrc/adaptive*.resources.txt \
-	    fray_amd/csrc/features*.resources.txt fray_amd/csrc/denoise.resources.txt
+resources: $(ST_OBJ) $(CONTRACT_OBJ) fray_amd/csrc/denoise.o
+	python3 tools/kernel_resources.py $(foreach set,$(ST_SETS),fray_amd/csrc/$(firstword $(subst :, ,$(set)))*.resources.txt) fray_amd/csrc/denoise.resources.txt
 
 clean:
 	rm -f fray_amd/csrc/*.o fray_amd/csrc/*.resources.txt fray_amd/libfrayhip.so oracle/libfray_oracle.so examples/fray_render examples/fray_render_mgpu tests/native/librccl_loopback.so

@@ -4,7 +4,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "render_state.hpp"
+#include "entry_support.hpp"
 
 namespace frayhip_detail {
 
@@ -33,9 +33,6 @@ inline std::vector<int> adaptive_ladder(int minSpp, int spp)
 }
 
 template <int ST> int adaptive_impl(frayhip_scene* sc, AdaptiveCall& q, hipStream_t stream, frayhip_stats* st);
-#define FRAY_ADAPTIVE_EXTERN(st) extern template int adaptive_impl<st>(frayhip_scene*, AdaptiveCall&, hipStream_t, frayhip_stats*);
-FRAY_ADAPTIVE_EXTERN(0) FRAY_ADAPTIVE_EXTERN(1) FRAY_ADAPTIVE_EXTERN(2) FRAY_ADAPTIVE_EXTERN(3)
-FRAY_ADAPTIVE_EXTERN(4) FRAY_ADAPTIVE_EXTERN(5) FRAY_ADAPTIVE_EXTERN(8) FRAY_ADAPTIVE_EXTERN(9)
-#undef FRAY_ADAPTIVE_EXTERN
+FRAY_EXTERN_ST(int adaptive_impl, (frayhip_scene*, AdaptiveCall&, hipStream_t, frayhip_stats*))
 
 }  // namespace frayhip_detail

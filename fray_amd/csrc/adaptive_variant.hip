@@ -275,8 +275,6 @@ static __global__ __launch_bounds__(256) void k_adaptive_black(DFrame F, int nIt
     if (n) atomicAdd(&st->samples, n);
 }
 
-size_t r256(size_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 
 namespace frayhip_detail {
@@ -289,23 +287,10 @@ int adaptive_impl(frayhip_scene* sc, AdaptiveCall& q, hipStream_t stream, frayhi
 {
     const auto t0 = std::chrono::steady_clock::now();
     const frayhip_settings& set = sc->settings;
-    const int W = set.frameWidth, H = set.frameHeight;
-    DFrame F{};
-    F.W = W; F.H = H;
-    F.BW = (W - 1) / 48 + 1; F.BH = (H - 1) / 48 + 1;
-    F.bucketStride = q.bucketStride;
-    F.bucketFirst = q.bucketFirst;
-    F.nBuckets = frayhip_bucket_count(W, H, F.bucketFirst, F.bucketStride);
-    F.spp = q.spp;
-    F.seed = q.seed;
-    F.jitter = 1;
+    const DFrame F = frame_record(sc, q.bucketFirst, q.bucketStride, q.seed);          // spp: q.spp, the frame's; jitter on (gi)
     const int nItems = F.nBuckets * 2304;
-    DScene S = sc->S;                                   // the frame's scene record (render_impl)
-    S.ambient[0] = set.ambientLight[0]; S.ambient[1] = set.ambientLight[1]; S.ambient[2] = set.ambientLight[2];
-    S.maxTraceDepth = set.maxTraceDepth;
-    S.gi = set.gi;
-    S.saturation = set.saturation;
-    const DCamera C = camera_begin_frame(sc->camera, W, H);
+    const DScene S = frame_scene(sc);
+    const DCamera C = camera_begin_frame(sc->camera, F.W, F.H);
     const std::vector<int> ladder = adaptive_ladder(q.minSpp, q.spp);
 
     // an adaptive frame is a frame: the last frame's figures are its own (it runs no contracted kernel and no speculative fan)
@@ -343,24 +328,23 @@ int adaptive_impl(frayhip_scene* sc, AdaptiveCall& q, hipStream_t stream, frayhi
             if (rc) return rc;
             break;
         }
-        unsigned char* p = (unsigned char*)sc->d_work;
-        auto take = [&](size_t b) { unsigned char* r = p; p += r256(b); return r; };
+        Carve work{(unsigned char*)sc->d_work};
         PixelState P;
-        P.sum = (float*)take((size_t)nItems * 12);
-        P.prev = (float*)take((size_t)nItems * 12);
-        int* list[2] = {(int*)take((size_t)nItems * 4), (int*)take((size_t)nItems * 4)};
-        P.flag = take((size_t)nItems);
-        int* tileCount = (int*)take((size_t)nTiles * 4);
-        int* tileOffset = (int*)take((size_t)nTiles * 4);
-        int* dCount = (int*)take(256);
+        P.sum = (float*)work.take((size_t)nItems * 12);
+        P.prev = (float*)work.take((size_t)nItems * 12);
+        int* list[2] = {(int*)work.take((size_t)nItems * 4), (int*)work.take((size_t)nItems * 4)};
+        P.flag = work.take((size_t)nItems);
+        int* tileCount = (int*)work.take((size_t)nTiles * 4);
+        int* tileOffset = (int*)work.take((size_t)nTiles * 4);
+        int* dCount = (int*)work.take(256);
         PathQueue Q[2];
         ShadowQueue SQ;
-        p = carve_queue(p, nQueue, Q[0]);
-        p = carve_queue(p, nQueue, Q[1]);
-        p = carve_shadow(p, nQueue, SQ);
-        uint32_t* x397 = (uint32_t*)take(slots * 4);
-        float* terms = (float*)take(slots * (size_t)nBounce * 12);
-        unsigned short* termCount = (unsigned short*)take(slots * 2);
+        work.p = carve_queue(work.p, nQueue, Q[0]);
+        work.p = carve_queue(work.p, nQueue, Q[1]);
+        work.p = carve_shadow(work.p, nQueue, SQ);
+        uint32_t* x397 = (uint32_t*)work.take(slots * 4);
+        float* terms = (float*)work.take(slots * (size_t)nBounce * 12);
+        unsigned short* termCount = (unsigned short*)work.take(slots * 2);
         QMeta* meta = sc->d_qmeta;
 
         // the list's new length, read back once per compaction
@@ -395,24 +379,8 @@ int adaptive_impl(frayhip_scene* sc, AdaptiveCall& q, hipStream_t stream, frayhi
                     hipLaunchKernelGGL(k_seed_list, dim3(seed_grid((m + FRAY_SEED_CHAINS - 1) / FRAY_SEED_CHAINS)), dim3(256), 0, stream, F, B, x397);
                     hipLaunchKernelGGL(k_meta_dense, dim3(1), dim3(64), 0, stream, meta, (uint32_t)m);
                     hipLaunchKernelGGL(k_pt_init_list<ST>, dim3(grid_for(m)), dim3(256), 0, stream, C, F, B, Q[0], termCount, (const uint32_t*)x397, sc->d_stats);
-                    const int grid = bounce_grid(m, alone);
-                    for (int b = 0; b < nBounce; b++) {                  // the frame's non-fused sequence (render_impl: stereo, long generators)
-                        const QMetaRO mIn{(const FRAY_RO QMeta*)(meta + (b & 1))}, mSh{(const FRAY_RO QMeta*)(meta + 2)};
-                        hipEvent_t ea = pool_event(sc->evPool, nTraceEvents), eb = pool_event(sc->evPool, nTraceEvents + 1);
-                        hipEvent_t ec = pool_event(sc->evPoolShadow, nShadowEvents), ed = pool_event(sc->evPoolShadow, nShadowEvents + 1);
-                        if (!ea || !eb || !ec || !ed) return FRAYHIP_E_NOMEM;
-                        const TermBuf TB{terms, termCount, (uint32_t)slots, b};
-                        const BounceArgs BA{S, Q[b & 1], Q[(b + 1) & 1], SQ, mIn, meta + ((b + 1) & 1), meta + 2, TB, StereoBuf{}, LongRng{}, sc->d_stats, FirstArgs{}};
-                        HIP_TRY(hipEventRecord(ea, stream));
-                        hipLaunchKernelGGL((k_pt_bounce<ST, false>), dim3(grid), dim3(256), 0, stream, BA);
-                        HIP_TRY(hipEventRecord(eb, stream));
-                        nTraceEvents += 2;
-                        hipLaunchKernelGGL(k_scan, dim3(2), dim3(1024), 0, stream, meta + ((b + 1) & 1), meta + 2);
-                        HIP_TRY(hipEventRecord(ec, stream));
-                        hipLaunchKernelGGL(k_pt_shadow<ST>, dim3(grid), dim3(256), 0, stream, ShadowArgs{S, SQ, mSh, TB, sc->d_stats + 1});
-                        HIP_TRY(hipEventRecord(ed, stream));
-                        nShadowEvents += 2;
-                    }
+                    if (const int rc = pt_bounces<ST>(sc, S, Q, SQ, TermBuf{terms, termCount, (uint32_t)slots, 0}, nBounce, bounce_grid(m, alone), stream, nTraceEvents, nShadowEvents))
+                        return rc;
                     const ResolveArgs RA{F, B, sLo + s, s + c >= rs, j == 0, r, q.spp, q.threshold, q.errFloor, TermBuf{terms, termCount, (uint32_t)slots, 0}, P,
                                          q.rgb, q.sppOut, q.errOut};
                     hipLaunchKernelGGL(k_adaptive_resolve, dim3(grid_for((size_t)mp)), dim3(256), 0, stream, RA);
@@ -434,32 +402,7 @@ int adaptive_impl(frayhip_scene* sc, AdaptiveCall& q, hipStream_t stream, frayhi
                   "intersections than the device path holds)");
         return FRAYHIP_E_UNSUPPORTED;
     }
-    if (st) {
-        frayhip_stats o{};
-        const DStats &a = dsv[0], &b = dsv[1];
-        o.closest_rays = a.closest + b.closest; o.shadow_rays = a.shadow + b.shadow; o.node_tests = a.node + b.node;
-        o.kd_inner_visits = a.kdInner + b.kdInner; o.leaf_refs = a.leafRefs + b.leafRefs; o.tri_tests = a.tri + b.tri;
-        o.prim_tests = a.prim + b.prim; o.smooth_hits = a.smooth + b.smooth; o.samples = a.samples + b.samples;
-        o.texture_fetches = a.tex + b.tex;
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, sc->evA, sc->evB);
-        o.ms_kernels = ms;
-        auto sumEvents = [&](std::vector<hipEvent_t>& pool, size_t k) {
-            double t = 0;
-            for (size_t i = 0; i + 1 < k; i += 2) {
-                float m2 = 0;
-                (void)hipEventElapsedTime(&m2, pool[i], pool[i + 1]);
-                t += m2;
-            }
-            return t;
-        };
-        o.ms_trace = sumEvents(sc->evPool, nTraceEvents);
-        o.trace_launches = nTraceEvents / 2;
-        o.ms_shadow = sumEvents(sc->evPoolShadow, nShadowEvents);
-        o.shadow_launches = nShadowEvents / 2;
-        o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        *st = o;
-    }
+    if (st) *st = finish_stats(sc, dsv, 2, nTraceEvents, nShadowEvents, t0);
     return FRAYHIP_OK;
 }
 

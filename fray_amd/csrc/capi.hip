@@ -12,7 +12,7 @@
 #include <cstdlib>
 
 
-#include "render_state.hpp"
+#include "entry_support.hpp"
 #include "dev_rng.hpp"
 #include "dev_pack.hpp"
 
@@ -208,6 +208,90 @@ hipEvent_t pool_event(std::vector<hipEvent_t>& pool, size_t i)
         pool.push_back(e);
     }
     return pool[i];
+}
+
+int bad(const char* who, const std::string& why)
+{
+    set_error(std::string(who) + ": " + why);
+    return FRAYHIP_E_ARG;
+}
+int unsupported(const char* who, const std::string& why)
+{
+    set_error(std::string(who) + ": " + why);
+    return FRAYHIP_E_UNSUPPORTED;
+}
+
+int frame_spp(const frayhip_scene* s)
+{
+    int spp = s->settings.wantAA ? 5 : 1;
+    if (s->camera.dof) spp = std::max(spp, s->camera.numDOFSamples);
+    if (s->settings.gi) spp = std::max(spp, s->settings.numPaths);
+    return spp;
+}
+
+DScene frame_scene(const frayhip_scene* s)
+{
+    const frayhip_settings& set = s->settings;
+    DScene S = s->S;
+    S.ambient[0] = set.ambientLight[0]; S.ambient[1] = set.ambientLight[1]; S.ambient[2] = set.ambientLight[2];
+    S.maxTraceDepth = set.maxTraceDepth;
+    S.gi = set.gi;
+    S.saturation = set.saturation;
+    return S;
+}
+
+DFrame frame_record(const frayhip_scene* s, int bucketFirst, int bucketStride, uint32_t seed)
+{
+    DFrame F = frame_grid(s->settings.frameWidth, s->settings.frameHeight);
+    F.bucketStride = bucketStride > 0 ? bucketStride : 1;
+    F.bucketFirst = bucketFirst;
+    F.nBuckets = frayhip_bucket_count(F.W, F.H, F.bucketFirst, F.bucketStride);
+    F.spp = frame_spp(s);
+    F.seed = seed;
+    F.jitter = (s->camera.dof || s->settings.gi) ? 1 : 0;
+    return F;
+}
+
+int check_bucket_range(const char* who, int nBuckets) { return nBuckets < 0 ? bad(who, "bad bucket_first / bucket_stride") : FRAYHIP_OK; }
+int check_pixel_cap(const char* who, int nBuckets)
+{
+    if ((long long)nBuckets * 2304 > (1ll << 30)) return unsupported(who, "more than 2^30 pixels in one call (shard the frame with bucket_first / bucket_stride)");
+    return FRAYHIP_OK;
+}
+int refuse_stereo(const char* who, const frayhip_scene* s) { return s->camera.stereoSeparation > 0 ? unsupported(who, "stereo frames are not supported") : FRAYHIP_OK; }
+int refuse_long_generators(const char* who, const frayhip_scene* s, const char* by)
+{
+    if (s->settings.gi && s->settings.maxTraceDepth >= 0 && long_generators(s->settings.maxTraceDepth))
+        return unsupported(who, std::string("path tracing with maxTraceDepth >= 20 (generators past 227 words) is not supported by ") + by);
+    return FRAYHIP_OK;
+}
+
+frayhip_stats finish_stats(frayhip_scene* sc, const DStats* blocks, int nBlocks, size_t nTraceEvents, size_t nShadowEvents, std::chrono::steady_clock::time_point t0)
+{
+    frayhip_stats o{};
+    for (int k = 0; k < nBlocks; k++) {
+        const DStats& d = blocks[k];
+        o.closest_rays += d.closest; o.shadow_rays += d.shadow; o.node_tests += d.node; o.kd_inner_visits += d.kdInner; o.leaf_refs += d.leafRefs;
+        o.tri_tests += d.tri; o.prim_tests += d.prim; o.smooth_hits += d.smooth; o.samples += d.samples; o.texture_fetches += d.tex;
+    }
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, sc->evA, sc->evB);
+    o.ms_kernels = ms;
+    auto sumEvents = [](const std::vector<hipEvent_t>& pool, size_t n) {
+        double t = 0;
+        for (size_t i = 0; i + 1 < n; i += 2) {
+            float m2 = 0;
+            (void)hipEventElapsedTime(&m2, pool[i], pool[i + 1]);
+            t += m2;
+        }
+        return t;
+    };
+    o.ms_trace = sumEvents(sc->evPool, nTraceEvents);
+    o.trace_launches = nTraceEvents / 2;
+    o.ms_shadow = sumEvents(sc->evPoolShadow, nShadowEvents);
+    o.shadow_launches = nShadowEvents / 2;
+    o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return o;
 }
 
 }  // namespace frayhip_detail
@@ -835,12 +919,10 @@ int render_dispatch(frayhip_scene* s, const frayhip_frame* f, float* d_rgb, int3
                     const frayhip_detail::Progress* prog)
 {
     if (s->rendering) { set_error("frayhip_render: the scene is already rendering a frame (a render call from inside a progress callback?)"); return FRAYHIP_E_ARG; }
-    struct Busy { frayhip_scene* s; Busy(frayhip_scene* x) : s(x) { s->rendering = true; } ~Busy() { s->rendering = false; } } busy(s);
-    const bool stats = (f->flags & FRAYHIP_FRAME_STATS) != 0;
-    if (s->extGeometry) return stats ? frayhip_detail::render_impl<3>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog) : frayhip_detail::render_impl<2>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog);
-    if (s->kdMeshes) return stats ? frayhip_detail::render_impl<5>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog) : frayhip_detail::render_impl<4>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog);
-    if (s->textured) return stats ? frayhip_detail::render_impl<9>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog) : frayhip_detail::render_impl<8>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog);
-    return stats ? frayhip_detail::render_impl<1>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog) : frayhip_detail::render_impl<0>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog);
+    frayhip_detail::Busy busy(s, stream, false);          // render_impl drains its lanes itself on an early return
+    return frayhip_detail::for_flag_word(frayhip_detail::flag_word(s, (f->flags & FRAYHIP_FRAME_STATS) != 0), [&](auto w) {
+        return frayhip_detail::render_impl<decltype(w)::value>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog);
+    });
 }
 
 int check_progressive(const frayhip_progressive* p, const char* who)
@@ -855,13 +937,11 @@ int check_progressive(const frayhip_progressive* p, const char* who)
 int render_host(frayhip_scene* s, const frayhip_frame* f, const frayhip_progressive* p, float* rgb, int32_t* hit_id, double* hit_dist, frayhip_stats* st)
 {
     const size_t n = (size_t)s->settings.frameWidth * s->settings.frameHeight;
-    float* d_rgb = nullptr; int32_t* d_id = nullptr; double* d_dist = nullptr;
-    int rc = FRAYHIP_OK;
-    auto cleanup = [&]() { if (d_rgb) (void)hipFree(d_rgb); if (d_id) (void)hipFree(d_id); if (d_dist) (void)hipFree(d_dist); };
-    if (rgb && hipMalloc((void**)&d_rgb, n * 12) != hipSuccess) rc = FRAYHIP_E_NOMEM;
-    if (!rc && hit_id && hipMalloc((void**)&d_id, n * 4) != hipSuccess) rc = FRAYHIP_E_NOMEM;
-    if (!rc && hit_dist && hipMalloc((void**)&d_dist, n * 8) != hipSuccess) rc = FRAYHIP_E_NOMEM;
-    if (rc) { set_error("frayhip_render: hipMalloc failed"); cleanup(); return rc; }
+    frayhip_detail::DeviceArrays B("frayhip_render: hipMalloc failed");
+    float* d_rgb; int32_t* d_id; double* d_dist;
+    if (int rc = B.alloc(d_rgb, 3 * n, rgb != nullptr)) return rc;
+    if (int rc = B.alloc(d_id, n, hit_id != nullptr)) return rc;
+    if (int rc = B.alloc(d_dist, n, hit_dist != nullptr)) return rc;
     // pixels outside this call's buckets keep what the caller had in the buffers: only a call that renders a SUBSET of the
     // buckets needs the caller's frame on the device first; a whole-frame call overwrites every pixel
     hipError_t ce = hipSuccess;
@@ -871,16 +951,15 @@ int render_host(frayhip_scene* s, const frayhip_frame* f, const frayhip_progress
         if (d_id && ce == hipSuccess) ce = hipMemcpy(d_id, hit_id, n * 4, hipMemcpyHostToDevice);
         if (d_dist && ce == hipSuccess) ce = hipMemcpy(d_dist, hit_dist, n * 8, hipMemcpyHostToDevice);
     }
-    if (ce != hipSuccess) { set_error(std::string("frayhip_render: host-to-device copy failed: ") + hipGetErrorString(ce)); cleanup(); return frayhip_detail::hip_error_code(ce); }
+    if (ce != hipSuccess) { set_error(std::string("frayhip_render: host-to-device copy failed: ") + hipGetErrorString(ce)); return frayhip_detail::hip_error_code(ce); }
     const frayhip_detail::Progress prog{p, rgb};
-    rc = render_dispatch(s, f, d_rgb, d_id, d_dist, nullptr, st, p ? &prog : nullptr);
+    int rc = render_dispatch(s, f, d_rgb, d_id, d_dist, nullptr, st, p ? &prog : nullptr);
     if (!rc || rc == FRAYHIP_E_CANCELLED) {
         if (d_rgb && !p && ce == hipSuccess) ce = hipMemcpy(rgb, d_rgb, n * 12, hipMemcpyDeviceToHost);
         if (d_id && ce == hipSuccess) ce = hipMemcpy(hit_id, d_id, n * 4, hipMemcpyDeviceToHost);
         if (d_dist && ce == hipSuccess) ce = hipMemcpy(hit_dist, d_dist, n * 8, hipMemcpyDeviceToHost);
         if (ce != hipSuccess) { set_error(std::string("frayhip_render: device-to-host copy failed: ") + hipGetErrorString(ce)); rc = frayhip_detail::hip_error_code(ce); }
     }
-    cleanup();
     return rc;
 }
 }  // namespace
@@ -983,8 +1062,7 @@ static int pack_impl(const float* d_frame, float* d_packed, int width, int heigh
     if (!d_frame || !d_packed || channels < 1) { set_error("frayhip_pack_buckets_device: bad argument"); return FRAYHIP_E_ARG; }
     int nb = frayhip_bucket_count(width, height, first, stride);
     if (nb < 0) { set_error("frayhip_pack_buckets_device: bad bucket range"); return FRAYHIP_E_ARG; }
-    DFrame F{};
-    F.W = width; F.H = height; F.BW = (width - 1) / 48 + 1; F.BH = (height - 1) / 48 + 1;
+    DFrame F = frayhip_detail::frame_grid(width, height);
     F.bucketFirst = first; F.bucketStride = stride; F.nBuckets = nb;
     int nItems = nb * 2304;
     if (nItems > 0) hipLaunchKernelGGL(k_pack, dim3(grid_for(nItems)), dim3(256), 0, (hipStream_t)hip_stream, F, nItems, channels, (float*)d_frame, d_packed, unpack);

@@ -12,23 +12,7 @@
 
 namespace {
 
-using frayhip_detail::set_error;
-using frayhip_detail::AdaptiveCall;
-
-int bad(const char* who, const std::string& why)
-{
-    set_error(std::string(who) + ": " + why);
-    return FRAYHIP_E_ARG;
-}
-
-// the frame's samples per pixel (main.cpp:395-400, render_impl)
-int frame_spp(const frayhip_scene* s)
-{
-    int spp = s->settings.wantAA ? 5 : 1;
-    if (s->camera.dof) spp = std::max(spp, s->camera.numDOFSamples);
-    if (s->settings.gi) spp = std::max(spp, s->settings.numPaths);
-    return spp;
-}
+using namespace frayhip_detail;
 
 // Every check of both entries, in this order; none touches the device.  FRAYHIP_E_ARG for the arguments, FRAYHIP_E_UNSUPPORTED for a frame the
 // adaptive path does not render (Whitted, stereo, long generators), then the sample counts against the frame's.
@@ -43,25 +27,12 @@ int check(const char* who, frayhip_scene* s, const frayhip_frame* f, const frayh
     if (!std::isfinite(a->err_floor) || !(a->err_floor > 0)) return bad(who, "err_floor must be finite and > 0");
     if (!s) return bad(who, "null scene");
     if (s->rendering) return bad(who, "the scene is rendering a frame (a call from inside its progress callback?)");
-    const int W = s->settings.frameWidth, H = s->settings.frameHeight;
-    const int nb = frayhip_bucket_count(W, H, f->bucket_first, f->bucket_stride > 0 ? f->bucket_stride : 1);
-    if (nb < 0) return bad(who, "bad bucket_first / bucket_stride");
-    if (!s->settings.gi) {
-        set_error(std::string(who) + ": adaptive frames are path-traced; a Whitted frame (gi off) is not supported");
-        return FRAYHIP_E_UNSUPPORTED;
-    }
-    if (s->camera.stereoSeparation > 0) {
-        set_error(std::string(who) + ": stereo frames are not supported");
-        return FRAYHIP_E_UNSUPPORTED;
-    }
-    if (s->settings.maxTraceDepth >= 0 && 8 + 10 * ((long long)s->settings.maxTraceDepth + 2) > 227) {
-        set_error(std::string(who) + ": path tracing with maxTraceDepth >= 20 (generators past 227 words) is not supported by adaptive frames");
-        return FRAYHIP_E_UNSUPPORTED;
-    }
-    if ((long long)nb * 2304 > (1ll << 30)) {
-        set_error(std::string(who) + ": more than 2^30 pixels in one call (shard the frame with bucket_first / bucket_stride)");
-        return FRAYHIP_E_UNSUPPORTED;
-    }
+    const int nb = frame_record(s, f->bucket_first, f->bucket_stride, f->seed).nBuckets;
+    if (const int rc = check_bucket_range(who, nb)) return rc;
+    if (!s->settings.gi) return unsupported(who, "adaptive frames are path-traced; a Whitted frame (gi off) is not supported");
+    if (const int rc = refuse_stereo(who, s)) return rc;
+    if (const int rc = refuse_long_generators(who, s, "adaptive frames")) return rc;
+    if (const int rc = check_pixel_cap(who, nb)) return rc;
     if (a->min_spp > frame_spp(s)) return bad(who, "min_spp must be <= the frame's spp (" + std::to_string(frame_spp(s)) + ")");
     return FRAYHIP_OK;
 }
@@ -82,43 +53,14 @@ AdaptiveCall call_of(frayhip_scene* s, const frayhip_frame* f, const frayhip_ada
     return q;
 }
 
-// the flag word the scene was created with (render_dispatch, capi.hip), with the counting bit from the frame.  The scene is held as a frame holds
-// it (`rendering`), so that nothing re-enters it; on an early return the stream is drained first.
+// The scene's flag word with the counting bit from the frame; the stream is drained on every return.
 int run(frayhip_scene* s, AdaptiveCall& q, hipStream_t stream, frayhip_adaptive* a, frayhip_stats* st)
 {
-    using namespace frayhip_detail;
-    struct Busy {
-        frayhip_scene* s;
-        hipStream_t stream;
-        Busy(frayhip_scene* x, hipStream_t y) : s(x), stream(y) { s->rendering = true; }
-        ~Busy() { (void)hipStreamSynchronize(stream); s->rendering = false; }
-    } busy(s, stream);
-    const int w = (s->extGeometry ? 2 : s->kdMeshes ? 4 : s->textured ? 8 : 0) | (q.stats ? 1 : 0);
-    int rc;
-    switch (w) {
-        case 0: rc = adaptive_impl<0>(s, q, stream, st); break;
-        case 1: rc = adaptive_impl<1>(s, q, stream, st); break;
-        case 2: rc = adaptive_impl<2>(s, q, stream, st); break;
-        case 3: rc = adaptive_impl<3>(s, q, stream, st); break;
-        case 4: rc = adaptive_impl<4>(s, q, stream, st); break;
-        case 5: rc = adaptive_impl<5>(s, q, stream, st); break;
-        case 8: rc = adaptive_impl<8>(s, q, stream, st); break;
-        default: rc = adaptive_impl<9>(s, q, stream, st); break;
-    }
+    Busy busy(s, stream);
+    const int rc = for_flag_word(flag_word(s, q.stats), [&](auto w) { return adaptive_impl<decltype(w)::value>(s, q, stream, st); });
     if (rc == FRAYHIP_OK) { a->rungs = q.rungs; a->samples = q.samples; }
     return rc;
 }
-
-// Device buffers of the host entry, freed on every return
-struct DeviceBuffer {
-    void* p = nullptr;
-    ~DeviceBuffer() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes)
-    {
-        if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr; set_error("frayhip_render_adaptive: out of device memory"); return FRAYHIP_E_NOMEM; }
-        return FRAYHIP_OK;
-    }
-};
 
 }  // namespace
 
@@ -137,11 +79,12 @@ int frayhip_render_adaptive(frayhip_scene* s, const frayhip_frame* f, frayhip_ad
     if (const int rc = check("frayhip_render_adaptive", s, f, a, rgb)) return rc;
     const size_t n = (size_t)s->settings.frameWidth * s->settings.frameHeight;
     // one allocation: colours, then sample counts and errors when asked for
-    DeviceBuffer B;
-    if (const int rc = B.alloc(n * (12 + (spp_out ? 4 : 0) + (err_out ? 4 : 0)))) return rc;
-    float* d_rgb = (float*)B.p;
+    DeviceArrays B("frayhip_render_adaptive: out of device memory");
+    unsigned char* base;
+    if (const int rc = B.alloc(base, n * (12 + (spp_out ? 4 : 0) + (err_out ? 4 : 0)))) return rc;
+    float* d_rgb = (float*)base;
     int32_t* d_spp = spp_out ? (int32_t*)(d_rgb + 3 * n) : nullptr;
-    float* d_err = err_out ? (float*)((char*)B.p + n * (12 + (spp_out ? 4 : 0))) : nullptr;
+    float* d_err = err_out ? (float*)(base + n * (12 + (spp_out ? 4 : 0))) : nullptr;
     // pixels outside this call's buckets keep what the caller had in the buffers (render_host's rule)
     if (f->bucket_stride > 1 || f->bucket_first != 0) {
         HIP_TRY(hipMemcpy(d_rgb, rgb, n * 12, hipMemcpyHostToDevice));

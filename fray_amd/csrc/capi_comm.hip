@@ -15,7 +15,7 @@
 #include <string>
 #include <vector>
 
-#include "render_state.hpp"
+#include "entry_support.hpp"
 #include "dev_pack.hpp"
 
 namespace {
@@ -166,8 +166,7 @@ int frayhip_gather_buckets(frayhip_comm* c, float* d_frame, int width, int heigh
     Rccl* R = rccl();
     if (!R) { set_error("frayhip_gather_buckets: RCCL is not available on this host"); return FRAYHIP_E_UNSUPPORTED; }
     hipStream_t stream = (hipStream_t)hip_stream;
-    DFrame F{};
-    F.W = width; F.H = height; F.BW = (width - 1) / 48 + 1; F.BH = (height - 1) / 48 + 1;
+    DFrame F = frayhip_detail::frame_grid(width, height);
     F.bucketStride = c->world;
     auto floats_of = [&](int r) { return (size_t)frayhip_bucket_count(width, height, r, c->world) * 2304 * (size_t)channels; };
     size_t need = 0;

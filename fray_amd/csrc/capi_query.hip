@@ -16,8 +16,7 @@
 
 namespace {
 
-using frayhip_detail::set_error;
-using frayhip_detail::QueryArgs;
+using namespace frayhip_detail;
 
 // Camera::getScreenRay for film positions xy[n][2], or for every integer pixel in row-major order (xy null): the frame's screen_ray on the frame's camera record
 __global__ __launch_bounds__(256) void k_camera_rays(DCamera C, long long n, int W, const double* __restrict__ xy, int eye, double* __restrict__ org,
@@ -33,13 +32,6 @@ __global__ __launch_bounds__(256) void k_camera_rays(DCamera C, long long n, int
         if (dir) { dir[3 * i] = d.x; dir[3 * i + 1] = d.y; dir[3 * i + 2] = d.z; }
     }
 }
-
-int bad(const char* who, const std::string& why)
-{
-    set_error(std::string(who) + ": " + why);
-    return FRAYHIP_E_ARG;
-}
-bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
 
 // The checks of every entry, in the order they are made (none touches the device): count and inputs, then the scene.
 int check_count(const char* who, int64_t n, std::initializer_list<const void*> inputs)
@@ -60,28 +52,13 @@ int check_doubles(const char* who, std::initializer_list<const void*> ps)
     return FRAYHIP_OK;
 }
 
-// A query holds the scene as a frame does (`rendering`), so that nothing re-enters it; on an early return the stream is drained first.
-struct Busy {
-    frayhip_scene* s;
-    hipStream_t stream;
-    bool armed = true;
-    Busy(frayhip_scene* x, hipStream_t st) : s(x), stream(st) { s->rendering = true; }
-    ~Busy() { if (armed) (void)hipStreamSynchronize(stream); s->rendering = false; }
-};
-
 enum Kind { CLOSEST = 0, VISIBLE = 1 };
 
-// the flag word the scene was created with (render_dispatch, capi.hip), with the counting bit from `flags`
 void launch(const frayhip_scene* s, Kind kind, bool stats, hipStream_t stream, const QueryArgs& A)
 {
-    using namespace frayhip_detail;
-    const int st = (s->extGeometry ? 2 : s->kdMeshes ? 4 : s->textured ? 8 : 0) | (stats ? 1 : 0);
-#define FRAY_QUERY_CASE(k) case k: if (kind == CLOSEST) launch_query_closest<k>(stream, A); else launch_query_visible<k>(stream, A); break;
-    switch (st) {
-        FRAY_QUERY_CASE(0) FRAY_QUERY_CASE(1) FRAY_QUERY_CASE(2) FRAY_QUERY_CASE(3)
-        FRAY_QUERY_CASE(4) FRAY_QUERY_CASE(5) FRAY_QUERY_CASE(8) FRAY_QUERY_CASE(9)
-    }
-#undef FRAY_QUERY_CASE
+    for_flag_word(flag_word(s, stats), [&](auto w) {
+        if (kind == CLOSEST) launch_query_closest<decltype(w)::value>(stream, A); else launch_query_visible<decltype(w)::value>(stream, A);
+    });
 }
 
 constexpr int64_t kLaunchRays = (int64_t)1 << 30;      // rays per launch (claim_items counts items in an int)
@@ -90,7 +67,6 @@ constexpr int64_t kLaunchRays = (int64_t)1 << 30;      // rays per launch (claim
 int run_query(frayhip_scene* sc, Kind kind, int64_t n, const double* a, const double* b, int32_t* id, double* dist, double* rec, uint8_t* vis, int flags,
               hipStream_t stream, frayhip_stats* st)
 {
-    using namespace frayhip_detail;
     const auto t0 = std::chrono::steady_clock::now();
     Busy busy(sc, stream);
     std::vector<hipEvent_t>& pool = kind == CLOSEST ? sc->evPool : sc->evPoolShadow;
@@ -118,21 +94,8 @@ int run_query(frayhip_scene* sc, Kind kind, int64_t n, const double* a, const do
     HIP_TRY(hipMemcpy(&d, sc->d_stats, sizeof d, hipMemcpyDeviceToHost));
     if (d.rngOverflow) { set_error("frayhip_trace_rays / frayhip_visible: a CsgOp operand produced more intersections than the device path holds"); return FRAYHIP_E_UNSUPPORTED; }
     if (st) {
-        frayhip_stats o{};
-        o.closest_rays = d.closest; o.shadow_rays = d.shadow; o.node_tests = d.node; o.kd_inner_visits = d.kdInner; o.leaf_refs = d.leafRefs;
-        o.tri_tests = d.tri; o.prim_tests = d.prim; o.smooth_hits = d.smooth;
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, sc->evA, sc->evB);
-        o.ms_kernels = ms;
-        double kernel = 0;
-        for (size_t i = 0; i + 1 < nEvents; i += 2) {
-            float m2 = 0;
-            (void)hipEventElapsedTime(&m2, pool[i], pool[i + 1]);
-            kernel += m2;
-        }
-        if (kind == CLOSEST) { o.ms_trace = kernel; o.trace_launches = nEvents / 2; }
-        else { o.ms_shadow = kernel; o.shadow_launches = nEvents / 2; }
-        o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        frayhip_stats o = finish_stats(sc, &d, 1, kind == CLOSEST ? nEvents : 0, kind == VISIBLE ? nEvents : 0, t0);
+        o.samples = o.texture_fetches = 0;          // a query takes no camera sample and shades nothing
         *st = o;
     }
     return FRAYHIP_OK;
@@ -140,7 +103,6 @@ int run_query(frayhip_scene* sc, Kind kind, int64_t n, const double* a, const do
 
 int run_camera(frayhip_scene* s, int64_t n, const double* xy, int eye, double* org, double* dir, hipStream_t stream)
 {
-    using namespace frayhip_detail;
     Busy busy(s, stream);
     const DCamera C = camera_begin_frame(s->camera, s->settings.frameWidth, s->settings.frameHeight);
     hipLaunchKernelGGL(k_camera_rays, dim3(grid_for((size_t)n)), dim3(256), 0, stream, C, (long long)n, s->settings.frameWidth, xy, eye, org, dir);
@@ -150,31 +112,10 @@ int run_camera(frayhip_scene* s, int64_t n, const double* xy, int eye, double* o
     return FRAYHIP_OK;
 }
 
-// Device buffers of a host entry, freed on every return
-struct DeviceBuffers {
-    std::vector<void*> ptrs;
-    ~DeviceBuffers() { for (void* p : ptrs) (void)hipFree(p); }
-    template <class T> int alloc(T*& p, size_t count, bool want)
-    {
-        p = nullptr;
-        if (!want || count == 0) return FRAYHIP_OK;
-        void* q = nullptr;
-        if (hipMalloc(&q, count * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); set_error("ray query: out of device memory"); return FRAYHIP_E_NOMEM; }
-        ptrs.push_back(q);
-        p = (T*)q;
-        return FRAYHIP_OK;
-    }
-};
 int copy(void* dst, const void* src, size_t bytes, hipMemcpyKind k)
 {
     if (!bytes || !dst) return FRAYHIP_OK;
     HIP_TRY(hipMemcpy(dst, src, bytes, k));
-    return FRAYHIP_OK;
-}
-
-int no_work(frayhip_stats* st)
-{
-    if (st) *st = frayhip_stats{};
     return FRAYHIP_OK;
 }
 
@@ -205,7 +146,7 @@ int frayhip_camera_rays(frayhip_scene* s, int64_t n, const double* xy, int eye, 
     if (!xy && n != (int64_t)s->settings.frameWidth * s->settings.frameHeight) return bad(who, "xy == NULL needs n == frameWidth * frameHeight");
     if (n == 0) return FRAYHIP_OK;
     const size_t N = (size_t)n;
-    DeviceBuffers B;
+    DeviceArrays B("ray query: out of device memory");
     double *d_xy, *d_o, *d_d;
     if (int rc = B.alloc(d_xy, 2 * N, xy != nullptr)) return rc;
     if (int rc = B.alloc(d_o, 3 * N, origin != nullptr)) return rc;
@@ -238,7 +179,7 @@ int frayhip_trace_rays(frayhip_scene* s, int64_t n, const double* origin, const 
     if (const int rc = check_scene(who, s)) return rc;
     if (n == 0) return no_work(st);
     const size_t N = (size_t)n;
-    DeviceBuffers B;
+    DeviceArrays B("ray query: out of device memory");
     double *d_in, *d_dist, *d_rec;
     int32_t* d_id;
     if (int rc = B.alloc(d_in, 6 * N, true)) return rc;
@@ -272,7 +213,7 @@ int frayhip_visible(frayhip_scene* s, int64_t n, const double* a, const double* 
     if (const int rc = check_scene(who, s)) return rc;
     if (n == 0) return no_work(st);
     const size_t N = (size_t)n;
-    DeviceBuffers B;
+    DeviceArrays B("ray query: out of device memory");
     double* d_in;
     uint8_t* d_vis;
     if (int rc = B.alloc(d_in, 6 * N, true)) return rc;

@@ -16,7 +16,7 @@
 #include <cstdint>
 #include <string>
 
-#include "render_state.hpp"
+#include "entry_support.hpp"
 
 // the B3-spline taps (1/16, 1/4, 3/8, 1/4, 1/16): all exact in FP32
 static __constant__ float kB3[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
@@ -161,13 +161,7 @@ static __global__ __launch_bounds__(256) void k_dn_level(DenoiseLevel L)
 
 namespace {
 
-using frayhip_detail::set_error;
-
-int bad(const char* who, const std::string& why)
-{
-    set_error(std::string(who) + ": " + why);
-    return FRAYHIP_E_ARG;
-}
+using namespace frayhip_detail;
 
 bool overlaps(const void* a, size_t an, const void* b, size_t bn)
 {
@@ -187,7 +181,7 @@ int check(const char* who, int W, int H, const float* rgb, const float* half, co
     if (!out) return bad(who, "null out");
     if (device)
         for (const void* q : {(const void*)rgb, (const void*)half, (const void*)feat, (const void*)out})
-            if ((uintptr_t)q & 3) return bad(who, "device pointer to floats not 4-byte aligned");
+            if (misaligned(q, 4)) return bad(who, "device pointer to floats not 4-byte aligned");
     if (p->levels < 1 || p->levels > 10) return bad(who, "levels must be 1..10");
     if (p->demodulate != 0 && p->demodulate != 1) return bad(who, "demodulate must be 0 or 1");
     const float sig[4] = {p->sigma_luminance, p->sigma_normal, p->sigma_depth, p->sigma_albedo};
@@ -202,15 +196,6 @@ int check(const char* who, int W, int H, const float* rgb, const float* half, co
     return FRAYHIP_OK;
 }
 
-struct DeviceMem {
-    void* p = nullptr;
-    ~DeviceMem() { if (p) (void)hipFree(p); }
-    int alloc(const char* who, size_t bytes)
-    {
-        if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr; set_error(std::string(who) + ": out of device memory"); return FRAYHIP_E_NOMEM; }
-        return FRAYHIP_OK;
-    }
-};
 struct Events {
     hipEvent_t a = nullptr, b = nullptr;
     ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
@@ -221,9 +206,10 @@ int run(const char* who, int W, int H, const float* rgb, const float* half, cons
         frayhip_stats* st, std::chrono::steady_clock::time_point t0)
 {
     const size_t n = (size_t)W * H;
-    DeviceMem M;
-    if (const int rc = M.alloc(who, n * (16 + 16 + 8 + 16 + 16))) return rc;
-    float4* g0 = (float4*)M.p;
+    DeviceArrays M(std::string(who) + ": out of device memory");
+    unsigned char* work;
+    if (const int rc = M.alloc(work, n * (16 + 16 + 8 + 16 + 16))) return rc;
+    float4* g0 = (float4*)work;
     float4* g1 = g0 + n;
     float4* cvA = g1 + n;
     float4* cvB = cvA + n;
@@ -291,9 +277,9 @@ int frayhip_denoise(int width, int height, const float* rgb, const float* rgb_ha
     if (const int rc = check(who, width, height, rgb, rgb_half, feat, p, out, false)) return rc;
     const size_t n = (size_t)width * height;
     // one allocation: rgb, out, feat, then rgb_half when given
-    DeviceMem B;
-    if (const int rc = B.alloc(who, n * 4 * (3 + 3 + FRAYHIP_FEAT_CHANNELS + (rgb_half ? 3 : 0)))) return rc;
-    float* d_rgb = (float*)B.p;
+    DeviceArrays B(std::string(who) + ": out of device memory");
+    float* d_rgb;
+    if (const int rc = B.alloc(d_rgb, n * (3 + 3 + FRAYHIP_FEAT_CHANNELS + (rgb_half ? 3 : 0)))) return rc;
     float* d_out = d_rgb + 3 * n;
     float* d_feat = d_out + 3 * n;
     float* d_half = rgb_half ? d_feat + FRAYHIP_FEAT_CHANNELS * n : nullptr;

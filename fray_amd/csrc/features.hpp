@@ -1,7 +1,7 @@
 // Feature frames (include/frayhip.h: frayhip_render_features): what the C entry points (capi_features.hip) hand to the kernel of
 // features_variant.hip, which the Makefile compiles once per kernel flag word as it does query_variant.hip.
 #pragma once
-#include "render_state.hpp"
+#include "entry_support.hpp"
 
 namespace frayhip_detail {
 
@@ -18,9 +18,6 @@ struct FeatureArgs {
 };
 
 template <int ST> void launch_features(hipStream_t stream, const FeatureArgs& A);
-#define FRAY_FEATURES_EXTERN(st) extern template void launch_features<st>(hipStream_t, const FeatureArgs&);
-FRAY_FEATURES_EXTERN(0) FRAY_FEATURES_EXTERN(1) FRAY_FEATURES_EXTERN(2) FRAY_FEATURES_EXTERN(3)
-FRAY_FEATURES_EXTERN(4) FRAY_FEATURES_EXTERN(5) FRAY_FEATURES_EXTERN(8) FRAY_FEATURES_EXTERN(9)
-#undef FRAY_FEATURES_EXTERN
+FRAY_EXTERN_ST(void launch_features, (hipStream_t, const FeatureArgs&))
 
 }  // namespace frayhip_detail

@@ -1,7 +1,7 @@
 // The ray queries (include/frayhip.h: frayhip_trace_rays, frayhip_visible): what the C entry points (capi_query.hip) hand to the kernels of
 // query_variant.hip, which the Makefile compiles once per kernel flag word as it does render_variant.hip.
 #pragma once
-#include "render_state.hpp"
+#include "entry_support.hpp"
 
 namespace frayhip_detail {
 
@@ -21,10 +21,7 @@ struct QueryArgs {
 
 template <int ST> void launch_query_closest(hipStream_t stream, const QueryArgs& A);
 template <int ST> void launch_query_visible(hipStream_t stream, const QueryArgs& A);
-#define FRAY_QUERY_EXTERN(st) extern template void launch_query_closest<st>(hipStream_t, const QueryArgs&); \
-                              extern template void launch_query_visible<st>(hipStream_t, const QueryArgs&);
-FRAY_QUERY_EXTERN(0) FRAY_QUERY_EXTERN(1) FRAY_QUERY_EXTERN(2) FRAY_QUERY_EXTERN(3)
-FRAY_QUERY_EXTERN(4) FRAY_QUERY_EXTERN(5) FRAY_QUERY_EXTERN(8) FRAY_QUERY_EXTERN(9)
-#undef FRAY_QUERY_EXTERN
+FRAY_EXTERN_ST(void launch_query_closest, (hipStream_t, const QueryArgs&))
+FRAY_EXTERN_ST(void launch_query_visible, (hipStream_t, const QueryArgs&))
 
 }  // namespace frayhip_detail

@@ -8,7 +8,7 @@
 #include <cstring>
 #include <cstdio>
 
-#include "render_state.hpp"
+#include "entry_support.hpp"
 #include "kernels.hpp"
 
 namespace frayhip_detail {
@@ -17,30 +17,50 @@ namespace {
 // Carves a path queue / a shadow queue of n entries out of the workspace.
 unsigned char* carve_queue(unsigned char* p, size_t n, PathQueue& Q)
 {
-    auto take = [&](size_t bytes) { unsigned char* r = p; p += (bytes + 255) / 256 * 256; return r; };
-    Q.rec = (PathRec*)take(n * sizeof(PathRec));
-    Q.cls = take(n);
-    return p;
+    Carve c{p};
+    Q.rec = (PathRec*)c.take(n * sizeof(PathRec));
+    Q.cls = c.take(n);
+    return c.p;
 }
-size_t queue_bytes(size_t n)
-{
-    auto r = [](size_t b) { return (b + 255) / 256 * 256; };
-    return r(n * sizeof(PathRec)) + r(n);
-}
+size_t queue_bytes(size_t n) { return r256(n * sizeof(PathRec)) + r256(n); }
 unsigned char* carve_shadow(unsigned char* p, size_t n, ShadowQueue& Q)
 {
-    auto take = [&](size_t bytes) { unsigned char* r = p; p += (bytes + 255) / 256 * 256; return r; };
-    Q.ax = (double*)take(n * 8); Q.ay = (double*)take(n * 8); Q.az = (double*)take(n * 8);
-    Q.bx = (double*)take(n * 8); Q.by = (double*)take(n * 8); Q.bz = (double*)take(n * 8);
-    Q.cr = (float*)take(n * 4); Q.cg = (float*)take(n * 4); Q.cb = (float*)take(n * 4);
-    Q.slot = (uint32_t*)take(n * 4);
-    Q.cls = take(n);
-    return p;
+    Carve c{p};
+    Q.ax = (double*)c.take(n * 8); Q.ay = (double*)c.take(n * 8); Q.az = (double*)c.take(n * 8);
+    Q.bx = (double*)c.take(n * 8); Q.by = (double*)c.take(n * 8); Q.bz = (double*)c.take(n * 8);
+    Q.cr = (float*)c.take(n * 4); Q.cg = (float*)c.take(n * 4); Q.cb = (float*)c.take(n * 4);
+    Q.slot = (uint32_t*)c.take(n * 4);
+    Q.cls = c.take(n);
+    return c.p;
 }
-size_t shadow_bytes(size_t n)
+size_t shadow_bytes(size_t n) { return 6 * r256(n * 8) + 4 * r256(n * 4) + r256(n); }
+
+// The path tracer's non-fused bounce sequence for a dense batch on one stream (the radiance queries and adaptive frames; render_impl runs it for stereo
+// frames and long generators, with its own arguments): per bounce k_pt_bounce<ST, false>, k_scan and k_pt_shadow<ST>, timed by an event pair of each pool.
+// Q[0] holds the batch's paths, TB its terms (TB.b is set per bounce); the event counts advance by two per bounce.
+template <int ST>
+int pt_bounces(frayhip_scene* sc, const DScene& S, const PathQueue (&Q)[2], const ShadowQueue& SQ, TermBuf TB, int nBounce, int grid, hipStream_t stream,
+               size_t& nTraceEvents, size_t& nShadowEvents)
 {
-    auto r = [](size_t b) { return (b + 255) / 256 * 256; };
-    return 6 * r(n * 8) + 4 * r(n * 4) + r(n);
+    QMeta* meta = sc->d_qmeta;
+    for (int b = 0; b < nBounce; b++) {
+        const QMetaRO mIn{(const FRAY_RO QMeta*)(meta + (b & 1))}, mSh{(const FRAY_RO QMeta*)(meta + 2)};
+        hipEvent_t ea = pool_event(sc->evPool, nTraceEvents), eb = pool_event(sc->evPool, nTraceEvents + 1);
+        hipEvent_t ec = pool_event(sc->evPoolShadow, nShadowEvents), ed = pool_event(sc->evPoolShadow, nShadowEvents + 1);
+        if (!ea || !eb || !ec || !ed) return FRAYHIP_E_NOMEM;
+        TB.b = b;
+        const BounceArgs BA{S, Q[b & 1], Q[(b + 1) & 1], SQ, mIn, meta + ((b + 1) & 1), meta + 2, TB, StereoBuf{}, LongRng{}, sc->d_stats, FirstArgs{}};
+        HIP_TRY(hipEventRecord(ea, stream));
+        hipLaunchKernelGGL((k_pt_bounce<ST, false>), dim3(grid), dim3(256), 0, stream, BA);
+        HIP_TRY(hipEventRecord(eb, stream));
+        nTraceEvents += 2;
+        hipLaunchKernelGGL(k_scan, dim3(2), dim3(1024), 0, stream, meta + ((b + 1) & 1), meta + 2);
+        HIP_TRY(hipEventRecord(ec, stream));
+        hipLaunchKernelGGL(k_pt_shadow<ST>, dim3(grid), dim3(256), 0, stream, ShadowArgs{S, SQ, mSh, TB, sc->d_stats + 1});
+        HIP_TRY(hipEventRecord(ed, stream));
+        nShadowEvents += 2;
+    }
+    return FRAYHIP_OK;
 }
 
 // The batch loop of every integrator that renders a frame in batches of `chunk` samples per pixel.  trace(j) enqueues batch j up to its resolve,
@@ -143,26 +163,11 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
     const auto t0 = std::chrono::steady_clock::now();
     const frayhip_settings& set = sc->settings;
     const int W = set.frameWidth, H = set.frameHeight;
-    DFrame F{};
-    F.W = W; F.H = H;
-    F.BW = (W - 1) / 48 + 1; F.BH = (H - 1) / 48 + 1;
-    F.bucketStride = f->bucket_stride > 0 ? f->bucket_stride : 1;
-    F.bucketFirst = f->bucket_first;
-    F.nBuckets = frayhip_bucket_count(W, H, F.bucketFirst, F.bucketStride);
-    if (F.nBuckets < 0) { set_error("frayhip_render: bad bucket_first / bucket_stride"); return FRAYHIP_E_ARG; }
-    if ((long long)F.nBuckets * 2304 > (1ll << 30)) { set_error("frayhip_render: more than 2^30 pixels in one call (shard the frame with bucket_first / bucket_stride)"); return FRAYHIP_E_UNSUPPORTED; }
-    int spp = set.wantAA ? 5 : 1;                                   // main.cpp:395-400
-    if (sc->camera.dof) spp = std::max(spp, sc->camera.numDOFSamples);
-    if (set.gi) spp = std::max(spp, set.numPaths);
-    F.spp = spp;
-    F.seed = f->seed;
-    F.jitter = (sc->camera.dof || set.gi) ? 1 : 0;
-    const int nItems = F.nBuckets * 2304;
-    DScene S = sc->S;
-    S.ambient[0] = set.ambientLight[0]; S.ambient[1] = set.ambientLight[1]; S.ambient[2] = set.ambientLight[2];
-    S.maxTraceDepth = set.maxTraceDepth;
-    S.gi = set.gi;
-    S.saturation = set.saturation;
+    const DFrame F = frame_record(sc, f->bucket_first, f->bucket_stride, f->seed);
+    if (const int rc = check_bucket_range("frayhip_render", F.nBuckets)) return rc;
+    if (const int rc = check_pixel_cap("frayhip_render", F.nBuckets)) return rc;
+    const int spp = F.spp, nItems = F.nBuckets * 2304;
+    const DScene S = frame_scene(sc);
     DCamera C = camera_begin_frame(sc->camera, W, H);
     Batches B;
     B.sc = sc; B.prog = prog; B.t0 = t0; B.F = F; B.nItems = nItems; B.d_rgb = d_rgb;
@@ -198,7 +203,6 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 // workspace: per-thread mt19937 state columns for samples that draw more than 227 words, the pixels' running sums, then per
                 // (pixel, sample) of a batch the sample's colour and x[397] of its seed.  A work item of k_whitted is one camera sample, so the
                 // grid is sized by the samples, and a frame whose samples do not fit the budget (or 2^31 items) is rendered in batches of `chunk` samples per pixel.
-                auto r256 = [](size_t b) { return (b + 255) / 256 * 256; };
                 const int grid = persistent_grid((size_t)nItems * spp, whitted_waves(ST));                 // one pass
                 const int gridAC = persistent_grid((size_t)nItems * spp, whitted_waves(ST, 1));            // passes A and C of the speculative fans
                 const size_t colBytes = r256((size_t)std::max(grid, gridAC) * 256 * 624 * sizeof(uint32_t));
@@ -294,7 +298,6 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 const int T = sc->lightSampleCount;
                 const bool stereo = sc->camera.stereoSeparation > 0;
                 const size_t eyes = stereo ? 2 : 1;
-                auto r256 = [](size_t b) { return (b + 255) / 256 * 256; };
                 const int grid = persistent_grid((size_t)nItems * spp, waves_for(ST, FRAY_WH_SHADE_WAVES));
                 const size_t colBytes = r256((size_t)grid * 256 * 624 * sizeof(uint32_t));
                 // per (pixel, sample): base 12 + a 24 + hit 1 + radiance 12 per eye, 37 per light sample and eye, 4 for the seed
@@ -379,7 +382,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
             if (set.maxTraceDepth > 2000) { set_error("frayhip_render: maxTraceDepth above 2000 is not supported (three launches per level and batch)"); return FRAYHIP_E_UNSUPPORTED; }
             // Random words a camera sample may draw from one generator: lens samples (DOF, both eyes) and ten per Lambert bounce (main.cpp:219-236,
             // lights.cpp:62-63).  Up to 227 the generators are three registers; beyond that every path gets two 624-word columns (MtPath).
-            const bool longRng = 8 + 10 * (set.maxTraceDepth + 2) > 227;
+            const bool longRng = long_generators(set.maxTraceDepth);
             const size_t termBytes = (size_t)(set.maxTraceDepth + 2) * 12 + 2;       // one FP32 RGB term per bounce and sample, and their count
             const size_t perPath = 240 + termBytes + (longRng ? 2 * 624 * sizeof(uint32_t) : 0);
             // Batches of `chunk` samples per pixel; up to FRAY_PT_LANES batches are in flight at once, each on its own
@@ -398,7 +401,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
             // with an empty launch of each kernel of the set, one stream after the other, so that no queue has to enlarge its scratch arena while another
             // lane's waves are resident.
             if (ST & 1) maxLanes = 1;
-            const bool longRngW = 8 + 10 * (set.maxTraceDepth + 2) > 227;
+            const bool longRngW = long_generators(set.maxTraceDepth);
             const unsigned warmKey = 1u << ((longRngW ? 1 : 0) | (sc->fpContract ? 2 : 0) | (sc->camera.stereoSeparation > 0 ? 4 : 0));
             if (maxLanes > 1 && !(sc->warmMask & warmKey) && !getenv("FRAYHIP_NO_PRIME")) {
                 HIP_TRY(hipMemsetAsync(sc->d_qmeta, 0, 3 * FRAY_PT_LANES * sizeof(QMeta), stream));
@@ -622,29 +625,9 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
             return 88.0 * (double)d.closest + 73.0 * (double)d.shadow + 168.0 * (double)d.node + 16.0 * (double)d.kdInner + 4.0 * (double)d.leafRefs +
                    120.0 * (double)d.tri + 32.0 * (double)d.prim + 144.0 * (double)d.smooth + 12.0 * (double)d.tex;
         };
-        frayhip_stats o{};
+        frayhip_stats o = finish_stats(sc, dsv, 2, nTraceEvents, nShadowEvents, t0);
         const DStats &a = dsv[0], &b = dsv[1];
-        o.closest_rays = a.closest + b.closest; o.shadow_rays = a.shadow + b.shadow; o.node_tests = a.node + b.node;
-        o.kd_inner_visits = a.kdInner + b.kdInner; o.leaf_refs = a.leafRefs + b.leafRefs; o.tri_tests = a.tri + b.tri;
-        o.prim_tests = a.prim + b.prim; o.smooth_hits = a.smooth + b.smooth; o.samples = a.samples + b.samples;
-        o.texture_fetches = a.tex + b.tex;
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, sc->evA, sc->evB);
-        o.ms_kernels = ms;
-        auto sumEvents = [&](std::vector<hipEvent_t>& pool, size_t n) {
-            double t = 0;
-            for (size_t i = 0; i + 1 < n; i += 2) {
-                float m2 = 0;
-                (void)hipEventElapsedTime(&m2, pool[i], pool[i + 1]);
-                t += m2;
-            }
-            return t;
-        };
-        o.ms_trace = sumEvents(sc->evPool, nTraceEvents);
-        o.trace_launches = nTraceEvents / 2;
         o.alg_bytes_trace = model(a);
-        o.ms_shadow = sumEvents(sc->evPoolShadow, nShadowEvents);
-        o.shadow_launches = nShadowEvents / 2;
         o.alg_bytes_shadow = model(b);
         // SURVEY 8(d) operation counts: Node::intersect ~90, triangle test ~45, primitive ~30, box test ~30 (one per node, two per inner KD node)
         auto flops = [](const DStats& d) {
@@ -652,7 +635,6 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
         };
         o.alg_flops_trace = flops(a);
         o.alg_flops_shadow = flops(b);
-        o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         *st = o;
     }
     if (prog) {

@@ -1,6 +1,6 @@
-// Host-side state behind a frayhip_scene handle and the helpers shared by the translation units of
-// the library: capi.hip (scene upload, C entry points) and render_variant.hip (render_impl<ST>, compiled
-// once per kernel flag word so the eight variants build in parallel).
+// Host-side state behind a frayhip_scene handle and the workspace / grid helpers shared by the translation
+// units of the library (defined in capi.hip).  What sits between a C entry point and its kernels -- the kernel
+// flag word and its dispatch, the frame's records, the counters -- is entry_support.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -105,16 +105,5 @@ struct Progress {
 };
 // i-th event of a pool, created on first use; nullptr (and the error text set) when hipEventCreate fails
 hipEvent_t pool_event(std::vector<hipEvent_t>& pool, size_t i);
-
-template <int ST>
-int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t* d_id, double* d_dist, hipStream_t stream, frayhip_stats* st, const Progress* prog);
-extern template int render_impl<0>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
-extern template int render_impl<1>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
-extern template int render_impl<2>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
-extern template int render_impl<3>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
-extern template int render_impl<4>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
-extern template int render_impl<5>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
-extern template int render_impl<8>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
-extern template int render_impl<9>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
 
 }  // namespace frayhip_detail

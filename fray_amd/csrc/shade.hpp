@@ -1,7 +1,7 @@
 // The radiance queries (include/frayhip.h: frayhip_shade_rays): what the C entry points (capi_shade.hip) hand to shade_impl<ST> of
 // shade_variant.hip, which the Makefile compiles once per kernel flag word as it does render_variant.hip and query_variant.hip.
 #pragma once
-#include "render_state.hpp"
+#include "entry_support.hpp"
 
 namespace frayhip_detail {
 
@@ -19,9 +19,6 @@ struct ShadeCall {
 };
 
 template <int ST> int shade_impl(frayhip_scene* sc, const ShadeCall& q, hipStream_t stream, frayhip_stats* st);
-#define FRAY_SHADE_EXTERN(st) extern template int shade_impl<st>(frayhip_scene*, const ShadeCall&, hipStream_t, frayhip_stats*);
-FRAY_SHADE_EXTERN(0) FRAY_SHADE_EXTERN(1) FRAY_SHADE_EXTERN(2) FRAY_SHADE_EXTERN(3)
-FRAY_SHADE_EXTERN(4) FRAY_SHADE_EXTERN(5) FRAY_SHADE_EXTERN(8) FRAY_SHADE_EXTERN(9)
-#undef FRAY_SHADE_EXTERN
+FRAY_EXTERN_ST(int shade_impl, (frayhip_scene*, const ShadeCall&, hipStream_t, frayhip_stats*))
 
 }  // namespace frayhip_detail

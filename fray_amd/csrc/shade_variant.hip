@@ -221,8 +221,6 @@ static __global__ __launch_bounds__(256) void k_shade_black(ShadeRays R, float* 
     if (n) atomicAdd(&st->samples, n);
 }
 
-size_t r256(size_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 
 namespace frayhip_detail {
@@ -235,19 +233,12 @@ int shade_impl(frayhip_scene* sc, const ShadeCall& q, hipStream_t stream, frayhi
 {
     const auto t0 = std::chrono::steady_clock::now();
     const frayhip_settings& set = sc->settings;
-    DScene S = sc->S;                                   // the frame's scene record (render_impl)
-    S.ambient[0] = set.ambientLight[0]; S.ambient[1] = set.ambientLight[1]; S.ambient[2] = set.ambientLight[2];
-    S.maxTraceDepth = set.maxTraceDepth;
-    S.gi = set.gi;
-    S.saturation = set.saturation;
+    const DScene S = frame_scene(sc);
     const int n = q.n, spp = q.spp;
     ShadeRays R0{q.org, q.dir, q.keys, q.seed, 0, n, q.sampleFirst, spp, q.rngSkip};
 
     // Long generators (render_impl's longRng): k_pt_bounce<ST, true> derives a path's seed from its frame pixel (LongRng), which a keyed sample does not have
-    if (set.gi && set.maxTraceDepth >= 0 && 8 + 10 * (set.maxTraceDepth + 2) > 227) {
-        set_error("frayhip_shade_rays: path tracing with maxTraceDepth >= 20 (generators past 227 words) is not supported by radiance queries");
-        return FRAYHIP_E_UNSUPPORTED;
-    }
+    if (const int rc = refuse_long_generators("frayhip_shade_rays", sc, "radiance queries")) return rc;
     HIP_TRY(hipMemsetAsync(sc->d_stats, 0, kStatsBytes, stream));
     DCursors* cursors = (DCursors*)((unsigned char*)sc->d_stats + kCursorOffset);
     HIP_TRY(hipEventRecord(sc->evA, stream));
@@ -272,12 +263,11 @@ int shade_impl(frayhip_scene* sc, const ShadeCall& q, hipStream_t stream, frayhi
             if (rc) return rc;
             break;
         }
-        unsigned char* p = (unsigned char*)sc->d_work;
-        auto take = [&](size_t b) { unsigned char* r = p; p += r256(b); return r; };
-        uint32_t* mtWork = (uint32_t*)take(colBytes);
-        float* sum = (float*)take((size_t)nr * 12);
-        float* rad = (float*)take((size_t)nr * cn * 12);
-        uint32_t* x397 = (uint32_t*)take((size_t)nr * cn * 4);
+        Carve work{(unsigned char*)sc->d_work};
+        uint32_t* mtWork = (uint32_t*)work.take(colBytes);
+        float* sum = (float*)work.take((size_t)nr * 12);
+        float* rad = (float*)work.take((size_t)nr * cn * 12);
+        uint32_t* x397 = (uint32_t*)work.take((size_t)nr * cn * 4);
         bool first = true;
         for (int r0 = 0; r0 < n; r0 += nr) {
             const int mr = std::min(nr, n - r0);
@@ -339,24 +329,8 @@ int shade_impl(frayhip_scene* sc, const ShadeCall& q, hipStream_t stream, frayhi
                 hipLaunchKernelGGL(k_seed_keyed, dim3(seed_grid((m + FRAY_SEED_CHAINS - 1) / FRAY_SEED_CHAINS)), dim3(256), 0, stream, R, x397);
                 hipLaunchKernelGGL(k_meta_dense, dim3(1), dim3(64), 0, stream, meta, (uint32_t)m);
                 hipLaunchKernelGGL(k_pt_init_rays<ST>, dim3(grid_for(m)), dim3(256), 0, stream, R, Q[0], termCount, (const uint32_t*)x397, sc->d_stats);
-                const int grid = bounce_grid(m, alone);
-                for (int b = 0; b < nBounce; b++) {                      // the frame's non-fused sequence (render_impl: stereo, long generators)
-                    const QMetaRO mIn{(const FRAY_RO QMeta*)(meta + (b & 1))}, mSh{(const FRAY_RO QMeta*)(meta + 2)};
-                    hipEvent_t ea = pool_event(sc->evPool, nTraceEvents), eb = pool_event(sc->evPool, nTraceEvents + 1);
-                    hipEvent_t ec = pool_event(sc->evPoolShadow, nShadowEvents), ed = pool_event(sc->evPoolShadow, nShadowEvents + 1);
-                    if (!ea || !eb || !ec || !ed) return FRAYHIP_E_NOMEM;
-                    const TermBuf TB{terms, termCount, (uint32_t)nPaths, b};
-                    const BounceArgs BA{S, Q[b & 1], Q[(b + 1) & 1], SQ, mIn, meta + ((b + 1) & 1), meta + 2, TB, StereoBuf{}, LongRng{}, sc->d_stats, FirstArgs{}};
-                    HIP_TRY(hipEventRecord(ea, stream));
-                    hipLaunchKernelGGL((k_pt_bounce<ST, false>), dim3(grid), dim3(256), 0, stream, BA);
-                    HIP_TRY(hipEventRecord(eb, stream));
-                    nTraceEvents += 2;
-                    hipLaunchKernelGGL(k_scan, dim3(2), dim3(1024), 0, stream, meta + ((b + 1) & 1), meta + 2);
-                    HIP_TRY(hipEventRecord(ec, stream));
-                    hipLaunchKernelGGL(k_pt_shadow<ST>, dim3(grid), dim3(256), 0, stream, ShadowArgs{S, SQ, mSh, TB, sc->d_stats + 1});
-                    HIP_TRY(hipEventRecord(ed, stream));
-                    nShadowEvents += 2;
-                }
+                if (const int rc = pt_bounces<ST>(sc, S, Q, SQ, TermBuf{terms, termCount, (uint32_t)nPaths, 0}, nBounce, bounce_grid(m, alone), stream, nTraceEvents, nShadowEvents))
+                    return rc;
                 // a sample's radiance from its terms, innermost first (k_pt_resolve_terms' order), then the per-ray sum in sample order
                 hipLaunchKernelGGL(k_pt_fold, dim3(grid_for(m)), dim3(256), 0, stream, TermBuf{terms, termCount, (uint32_t)nPaths, 0}, (uint32_t)m, rad);
                 hipLaunchKernelGGL(k_shade_resolve, dim3(grid_for((size_t)mr)), dim3(256), 0, stream, mr, s, c, spp, (const float*)rad, sum, q.rgb + 3 * (size_t)r0);
@@ -373,32 +347,7 @@ int shade_impl(frayhip_scene* sc, const ShadeCall& q, hipStream_t stream, frayhi
                   "a CsgOp operand with more intersections than the device path holds)");
         return FRAYHIP_E_UNSUPPORTED;
     }
-    if (st) {
-        frayhip_stats o{};
-        const DStats &a = dsv[0], &b = dsv[1];
-        o.closest_rays = a.closest + b.closest; o.shadow_rays = a.shadow + b.shadow; o.node_tests = a.node + b.node;
-        o.kd_inner_visits = a.kdInner + b.kdInner; o.leaf_refs = a.leafRefs + b.leafRefs; o.tri_tests = a.tri + b.tri;
-        o.prim_tests = a.prim + b.prim; o.smooth_hits = a.smooth + b.smooth; o.samples = a.samples + b.samples;
-        o.texture_fetches = a.tex + b.tex;
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, sc->evA, sc->evB);
-        o.ms_kernels = ms;
-        auto sumEvents = [&](std::vector<hipEvent_t>& pool, size_t k) {
-            double t = 0;
-            for (size_t i = 0; i + 1 < k; i += 2) {
-                float m2 = 0;
-                (void)hipEventElapsedTime(&m2, pool[i], pool[i + 1]);
-                t += m2;
-            }
-            return t;
-        };
-        o.ms_trace = sumEvents(sc->evPool, nTraceEvents);
-        o.trace_launches = nTraceEvents / 2;
-        o.ms_shadow = sumEvents(sc->evPoolShadow, nShadowEvents);
-        o.shadow_launches = nShadowEvents / 2;
-        o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        *st = o;
-    }
+    if (st) *st = finish_stats(sc, dsv, 2, nTraceEvents, nShadowEvents, t0);
     return FRAYHIP_OK;
 }
 
