@@ -5,15 +5,18 @@ src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --he
                          python -m fray_amd scene.fray -o out.bmp --adaptive THRESHOLD [--min-spp N] [--adaptive-floor F]   (an adaptive frame, and one
                                                                                           JSON line: its rungs, mean spp and the share of pixels per rung)
                          python -m fray_amd scene.fray -o out.bmp --denoise [--feature-samples N] [--features-out FILE.npy]   (the frame denoised
-                                                                                          with its first-hit features; --features-out alone saves them)"""
+                                                                                          with its first-hit features; --features-out alone saves them)
+                         python -m fray_amd scene.fray -o out.bmp --denoise --frames N [--yaw-step DEG]   (N frames with temporal accumulation, the scene
+                                                                                          file's camera turned by DEG per frame: out_0000.bmp ...)"""
 import argparse
 import json
+import os
 import sys
 import time
 
 import numpy as np
 
-from . import Scene, lib
+from . import Scene, abi, lib
 
 
 def build_parser():
@@ -45,7 +48,26 @@ def build_parser():
                     help="camera samples per pixel of the feature frame (--denoise, --features-out; clamped to the frame's spp; default 4)")
     ap.add_argument("--features-out", metavar="FILE.npy",
                     help="also save the feature frame, float32 [H, W, 10]: position, normal, albedo, depth")
+    ap.add_argument("--frames", type=int, metavar="N",
+                    help="with --denoise: render N frames with temporal accumulation (Scene.render_sequence; frame k has seed SEED + k) and write "
+                         "OUTPUT's name with _0000, _0001, ... before the extension")
+    ap.add_argument("--yaw-step", type=float, default=1.0, metavar="DEG",
+                    help="with --frames: frame k sees the scene file's camera with its yaw turned by k * DEG degrees (default 1)")
     return ap
+
+
+def sequence_path(output, k):
+    """The file of frame k of a sequence: out.bmp -> out_0000.bmp."""
+    stem, ext = os.path.splitext(output)
+    return "%s_%04d%s" % (stem, k, ext)
+
+
+def orbit(camera, frames, yaw_step):
+    """The cameras of --frames: copies of `camera` with yaw + k * yaw_step."""
+    for k in range(frames):
+        c = abi.Camera.from_buffer_copy(camera)
+        c.yaw = camera.yaw + k * yaw_step
+        yield c
 
 
 def check_args(ap, a):
@@ -54,6 +76,12 @@ def check_args(ap, a):
         ap.error("--denoise cannot be combined with --adaptive: denoising adaptive frames is not supported")
     if a.denoise and a.time_limit is not None:
         ap.error("--denoise cannot be combined with --time-limit: the denoiser needs the whole frame")
+    if a.frames is not None and not a.denoise:
+        ap.error("--frames needs --denoise: a sequence is rendered with temporal accumulation and the filter")
+    if a.frames is not None and a.frames < 1:
+        ap.error("--frames must be >= 1")
+    if a.frames is not None and a.features_out:
+        ap.error("--frames cannot be combined with --features-out")
 
 
 def adaptive_summary(spp, info):
@@ -97,6 +125,19 @@ def main(argv=None):
         print(json.dumps(probe(s, a.probe[0], a.probe[1], a.shade, a.seed)))
         return 0
     t0 = time.time()
+    if a.frames is not None:
+        start = abi.Camera.from_buffer_copy(s.camera)
+        for k, (img, _raw, info) in enumerate(s.render_sequence(orbit(start, a.frames, a.yaw_step), seed=a.seed, feature_samples=a.feature_samples)):
+            path = sequence_path(a.output, k)
+            img = img.cpu().numpy()
+            if lib.frayhip_save_bmp(path.encode(), img.ctypes.data, img.shape[1], img.shape[0]):
+                print(lib.frayhip_last_error().decode(), file=sys.stderr)
+                return 1
+            print("frame %d: yaw %+.2f, frame %.1f ms, features %.1f ms, accumulation %.2f ms, filter %.2f ms (kernels); wrote %s"
+                  % (k, k * a.yaw_step, info["render"]["ms_kernels"], info["features"]["ms_kernels"], info["temporal"]["ms_kernels"],
+                     info["denoise"]["ms_kernels"], path), flush=True)
+        print("Rendered %d frames in %.2fs" % (a.frames, time.time() - t0))
+        return 0
     if a.denoise:
         img, raw, info = s.render_denoised(seed=a.seed, feature_samples=a.feature_samples)
         st = info["render"]

@@ -178,6 +178,20 @@ class Denoise(C.Structure):
 FEAT_CHANNELS = 10      # FRAYHIP_FEAT_CHANNELS: position[3], normal[3], albedo[3], depth
 
 
+class View(C.Structure):
+    _fields_ = [("pos", f32 * 3), ("right", f32 * 3), ("up", f32 * 3), ("front", f32 * 3), ("tan_x", C.c_float), ("tan_y", C.c_float),
+                ("width", i32), ("height", i32)]
+
+
+# struct frayhip_temporal (a struct tag without a typedef, as frayhip_denoise)
+class Temporal(C.Structure):
+    _fields_ = [("demodulate", i32), ("max_history", i32), ("variance_history", i32), ("alpha_min", C.c_float), ("film_offset", C.c_float),
+                ("plane_tolerance", C.c_float), ("normal_min_dot", C.c_float)]
+
+
+HISTORY_CHANNELS = 12   # FRAYHIP_HISTORY_CHANNELS: {acc.rgb, N}, {P.xyz, m1}, {n.xyz, m2}
+
+
 STRUCTS = {"frayhip_transform": Transform, "frayhip_geom_ref": GeomRef, "frayhip_node": Node,
            "frayhip_plane": Plane, "frayhip_sphere": Sphere, "frayhip_cube": Cube,
            "frayhip_csg": Csg, "frayhip_triangle": Triangle, "frayhip_kdnode": KDNode,
@@ -186,7 +200,7 @@ STRUCTS = {"frayhip_transform": Transform, "frayhip_geom_ref": GeomRef, "frayhip
            "frayhip_settings": Settings, "frayhip_environment": Environment,
            "frayhip_scene_desc": SceneDesc, "frayhip_frame": Frame, "frayhip_stats": Stats,
            "frayhip_progress": Progress, "frayhip_progressive": Progressive,
-           "frayhip_shade_request": ShadeRequest, "frayhip_adaptive": Adaptive}
+           "frayhip_shade_request": ShadeRequest, "frayhip_adaptive": Adaptive, "frayhip_view": View}
 
 # Every symbol include/frayhip.h declares: name -> (restype, argtypes)
 VP = C.c_void_p
@@ -211,6 +225,12 @@ SYMBOLS = {
     "frayhip_denoise_defaults": (C.c_int, [P(Denoise)]),
     "frayhip_denoise": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(Denoise), VP, P(Stats)]),
     "frayhip_denoise_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(Denoise), VP, VP, P(Stats)]),
+    "frayhip_denoise_signal": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(Denoise), VP, P(Stats)]),
+    "frayhip_denoise_signal_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(Denoise), VP, VP, P(Stats)]),
+    "frayhip_view_from_camera": (C.c_int, [P(Camera), C.c_int, C.c_int, P(View)]),
+    "frayhip_temporal_defaults": (C.c_int, [P(Temporal)]),
+    "frayhip_temporal_accumulate": (C.c_int, [C.c_int, C.c_int, VP, VP, P(View), VP, P(Temporal), VP, VP, VP, P(Stats)]),
+    "frayhip_temporal_accumulate_device": (C.c_int, [C.c_int, C.c_int, VP, VP, P(View), VP, P(Temporal), VP, VP, VP, VP, P(Stats)]),
     "frayhip_camera_rays": (C.c_int, [VP, i64, VP, C.c_int, VP, VP]),
     "frayhip_camera_rays_device": (C.c_int, [VP, i64, VP, C.c_int, VP, VP, VP]),
     "frayhip_trace_rays": (C.c_int, [VP, i64, VP, VP, C.c_int, VP, VP, VP, P(Stats)]),

@@ -1,11 +1,11 @@
-// C ABI, denoising (include/frayhip.h "denoising"): frayhip_denoise_defaults, frayhip_denoise and frayhip_denoise_device.  A spatial,
+// C ABI, denoising (include/frayhip.h "denoising"): frayhip_denoise_defaults, frayhip_denoise, frayhip_denoise_signal and their _device entries.  A spatial,
 // SVGF-style edge-avoiding a-trous wavelet filter of an rgb frame guided by a feature frame (frayhip_render_features).  Scene-free: it needs no
 // frayhip_scene and touches none.  FP32 throughout; the Makefile builds this object with -ffp-contract=off, so every product and sum below is
 // rounded where it is written (tests/denoise_ref.py restates it in numpy).
 //
 //   k_dn_prepare   per pixel: the guides packed for the levels (unit normal and depth; albedo; the depth gradient by central differences,
 //                  one-sided at borders), the signal (rgb, or rgb / max(albedo, 1e-3) per channel) and, with rgb_half, the variance
-//                  (l(c) - l(c_half))^2 prefiltered with the 3x3 binomial kernel
+//                  (l(c) - l(c_half))^2 prefiltered with the 3x3 binomial kernel; for frayhip_denoise_signal the caller's signal and variance as they are
 //   k_dn_level     one a-trous level at step 2^k: 25 taps, edge-stopping weights, the filtered signal and its variance; the last level
 //                  multiplies max(albedo, 1e-3) back and writes the output frame
 // Every tap is read through L1 / L2 (no LDS tiling): at 1080p a level reads 48 bytes per tap from buffers that the neighbouring waves read too.
@@ -28,6 +28,7 @@ struct DenoisePrep {
     int W, H;
     const float* rgb;
     const float* half;          // null: no noise estimate
+    const float* variance;      // frayhip_denoise_signal: rgb is the signal as the levels take it, this its variance; else null
     const float* feat;
     int demodulate;
     float4* g0;                 // unit normal (or 0), depth
@@ -72,9 +73,11 @@ static __global__ __launch_bounds__(256) void k_dn_prepare(DenoisePrep P)
     P.grad[p] = make_float2(gx, gy);
     const float* c = P.rgb + 3 * p;
     float cr = c[0], cg = c[1], cb = c[2];
-    if (P.demodulate) { cr = demod1(cr, ar); cg = demod1(cg, ag); cb = demod1(cb, ab); }
+    if (P.demodulate && !P.variance) { cr = demod1(cr, ar); cg = demod1(cg, ag); cb = demod1(cb, ab); }
     float var = 0.0f;
-    if (P.half) {
+    if (P.variance) {
+        var = P.variance[p];
+    } else if (P.half) {
         // 3x3 binomial (1 2 1) x (1 2 1), normalised over the taps inside the image
         float sw = 0.0f, sv = 0.0f;
         for (int j = -1; j <= 1; j++) {
@@ -171,11 +174,14 @@ bool overlaps(const void* a, size_t an, const void* b, size_t bn)
 }
 
 // Every check of both entries, in this order; none touches the device.
-int check(const char* who, int W, int H, const float* rgb, const float* half, const float* feat, const struct frayhip_denoise* p, const float* out, bool device)
+// `variance`: the frayhip_denoise_signal entries, whose rgb is the signal and whose second buffer (W*H floats, required) is its variance.
+int check(const char* who, int W, int H, const float* rgb, const float* half, const float* feat, const struct frayhip_denoise* p, const float* out, bool device,
+          bool variance = false)
 {
     if (W < 1 || H < 1) return bad(who, "width and height must be >= 1");
     if ((long long)W * H > (1ll << 30)) return bad(who, "more than 2^30 pixels");
-    if (!rgb) return bad(who, "null rgb");
+    if (!rgb) return bad(who, variance ? "null signal" : "null rgb");
+    if (variance && !half) return bad(who, "null variance");
     if (!feat) return bad(who, "null feat");
     if (!p) return bad(who, "null parameters");
     if (!out) return bad(who, "null out");
@@ -191,7 +197,7 @@ int check(const char* who, int W, int H, const float* rgb, const float* half, co
         if (i != 1 && !(sig[i] > 0)) return bad(who, std::string(names[i]) + " must be > 0");
     }
     const size_t n = (size_t)W * H;
-    if (overlaps(out, 12 * n, rgb, 12 * n) || overlaps(out, 12 * n, half, 12 * n) || overlaps(out, 12 * n, feat, 4 * FRAYHIP_FEAT_CHANNELS * n))
+    if (overlaps(out, 12 * n, rgb, 12 * n) || overlaps(out, 12 * n, half, (variance ? 4 : 12) * n) || overlaps(out, 12 * n, feat, 4 * FRAYHIP_FEAT_CHANNELS * n))
         return bad(who, "out must not overlap an input");
     return FRAYHIP_OK;
 }
@@ -202,8 +208,9 @@ struct Events {
 };
 
 // The device path of both entries (device pointers, checked).  Work buffers: guides, gradient and two ping-pong signal buffers, one allocation.
+// `variance` as in check(): rgb and half are then the signal and its variance.
 int run(const char* who, int W, int H, const float* rgb, const float* half, const float* feat, const struct frayhip_denoise* prm, float* out, hipStream_t stream,
-        frayhip_stats* st, std::chrono::steady_clock::time_point t0)
+        frayhip_stats* st, std::chrono::steady_clock::time_point t0, bool variance = false)
 {
     const size_t n = (size_t)W * H;
     DeviceArrays M(std::string(who) + ": out of device memory");
@@ -220,7 +227,7 @@ int run(const char* who, int W, int H, const float* rgb, const float* half, cons
     struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{stream};
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     HIP_TRY(hipEventRecord(E.a, stream));
-    hipLaunchKernelGGL(k_dn_prepare, grid, block, 0, stream, DenoisePrep{W, H, rgb, half, feat, prm->demodulate, g0, g1, grad, cvA});
+    hipLaunchKernelGGL(k_dn_prepare, grid, block, 0, stream, DenoisePrep{W, H, rgb, variance ? nullptr : half, variance ? half : nullptr, feat, prm->demodulate, g0, g1, grad, cvA});
     HIP_TRY(hipGetLastError());
     for (int k = 0; k < prm->levels; k++) {
         const bool last = k == prm->levels - 1;
@@ -241,6 +248,30 @@ int run(const char* who, int W, int H, const float* rgb, const float* half, cons
         o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         *st = o;
     }
+    return FRAYHIP_OK;
+}
+
+// The host entries: host buffers copied to the device and back around run().  `variance` as in check().
+int host_entry(const char* who, int width, int height, const float* rgb, const float* half, const float* feat, const struct frayhip_denoise* p, float* out,
+               frayhip_stats* st, bool variance)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (const int rc = check(who, width, height, rgb, half, feat, p, out, false, variance)) return rc;
+    const size_t n = (size_t)width * height;
+    const size_t nHalf = half ? (variance ? 1 : 3) : 0;
+    // one allocation: rgb, out, feat, then rgb_half (or the variance) when given
+    DeviceArrays B(std::string(who) + ": out of device memory");
+    float* d_rgb;
+    if (const int rc = B.alloc(d_rgb, n * (3 + 3 + FRAYHIP_FEAT_CHANNELS + nHalf))) return rc;
+    float* d_out = d_rgb + 3 * n;
+    float* d_feat = d_out + 3 * n;
+    float* d_half = half ? d_feat + FRAYHIP_FEAT_CHANNELS * n : nullptr;
+    HIP_TRY(hipMemcpy(d_rgb, rgb, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_feat, feat, n * 4 * FRAYHIP_FEAT_CHANNELS, hipMemcpyHostToDevice));
+    if (d_half) HIP_TRY(hipMemcpy(d_half, half, n * 4 * nHalf, hipMemcpyHostToDevice));
+    if (const int rc = run(who, width, height, d_rgb, d_half, d_feat, p, d_out, nullptr, st, t0, variance)) return rc;
+    HIP_TRY(hipMemcpy(out, d_out, n * 12, hipMemcpyDeviceToHost));
+    if (st) st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return FRAYHIP_OK;
 }
 
@@ -272,24 +303,22 @@ int frayhip_denoise_device(int width, int height, const float* d_rgb, const floa
 int frayhip_denoise(int width, int height, const float* rgb, const float* rgb_half, const float* feat, const struct frayhip_denoise* p, float* out,
                     frayhip_stats* st)
 {
+    return host_entry("frayhip_denoise", width, height, rgb, rgb_half, feat, p, out, st, false);
+}
+
+int frayhip_denoise_signal_device(int width, int height, const float* d_signal, const float* d_variance, const float* d_feat, const struct frayhip_denoise* p,
+                                  float* d_out, void* hip_stream, frayhip_stats* st)
+{
     const auto t0 = std::chrono::steady_clock::now();
-    const char* who = "frayhip_denoise";
-    if (const int rc = check(who, width, height, rgb, rgb_half, feat, p, out, false)) return rc;
-    const size_t n = (size_t)width * height;
-    // one allocation: rgb, out, feat, then rgb_half when given
-    DeviceArrays B(std::string(who) + ": out of device memory");
-    float* d_rgb;
-    if (const int rc = B.alloc(d_rgb, n * (3 + 3 + FRAYHIP_FEAT_CHANNELS + (rgb_half ? 3 : 0)))) return rc;
-    float* d_out = d_rgb + 3 * n;
-    float* d_feat = d_out + 3 * n;
-    float* d_half = rgb_half ? d_feat + FRAYHIP_FEAT_CHANNELS * n : nullptr;
-    HIP_TRY(hipMemcpy(d_rgb, rgb, n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_feat, feat, n * 4 * FRAYHIP_FEAT_CHANNELS, hipMemcpyHostToDevice));
-    if (d_half) HIP_TRY(hipMemcpy(d_half, rgb_half, n * 12, hipMemcpyHostToDevice));
-    if (const int rc = run(who, width, height, d_rgb, d_half, d_feat, p, d_out, nullptr, st, t0)) return rc;
-    HIP_TRY(hipMemcpy(out, d_out, n * 12, hipMemcpyDeviceToHost));
-    if (st) st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return FRAYHIP_OK;
+    const char* who = "frayhip_denoise_signal_device";
+    if (const int rc = check(who, width, height, d_signal, d_variance, d_feat, p, d_out, true, true)) return rc;
+    return run(who, width, height, d_signal, d_variance, d_feat, p, d_out, (hipStream_t)hip_stream, st, t0, true);
+}
+
+int frayhip_denoise_signal(int width, int height, const float* signal, const float* variance, const float* feat, const struct frayhip_denoise* p, float* out,
+                           frayhip_stats* st)
+{
+    return host_entry("frayhip_denoise_signal", width, height, signal, variance, feat, p, out, st, true);
 }
 
 }  // extern "C"

@@ -1,0 +1,356 @@
+// C ABI, temporal accumulation (include/frayhip.h "temporal accumulation"): frayhip_view_from_camera, frayhip_temporal_defaults,
+// frayhip_temporal_accumulate and frayhip_temporal_accumulate_device.  The temporal stage of SVGF: the previous frame's accumulated signal and
+// luminance moments reprojected through the feature frame's world positions, surface tests on the four bilinear taps, the exponential blend,
+// and the variance the a-trous levels take (frayhip_denoise_signal).  Scene-free, FP32 throughout; the Makefile builds this object as it builds
+// denoise.o (-ffp-contract=off, correctly rounded divide and sqrt), so every product and sum below is rounded where it is written
+// (tests/temporal_ref.py restates it in numpy, and the two agree bit for bit).
+//
+//   k_tp_accumulate  per pixel: the signal, the projection into the previous view, four taps of three float4 rows each, the blend; writes the
+//                    three history rows, the signal, and the temporal variance where N >= variance_history
+//   k_tp_variance    per pixel with N < variance_history: the 7x7 window of the finished history (rows 1 and 2: position, normal, m1, m2),
+//                    taken from an LDS tile that the 16x16 block stages first; a block without such a pixel stages nothing
+// k_tp_accumulate's taps are read through L1 / L2, as the filter's.  k_tp_variance with the same direct reads took 0.214 ms at 1080p where
+// every pixel takes the window, against 0.074 ms from the tile ("Temporal accumulation").
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "entry_support.hpp"
+
+static __device__ __forceinline__ float tp_lum(float r, float g, float b) { return ((r + g) + b) / 3.0f; }
+static __device__ __forceinline__ float tp_dot(float a0, float a1, float a2, float b0, float b1, float b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
+
+struct TemporalCall {
+    int W, H;
+    const float* rgb;
+    const float* feat;
+    const float4* histIn;       // null: first frame
+    float4* histOut;
+    float* signal;
+    float* variance;
+    frayhip_view view;          // read only with histIn
+    int demodulate, varianceHistory;
+    float maxHistory, alphaMin, filmOffset, planeTolerance, normalMinDot;
+};
+
+static __global__ __launch_bounds__(256) void k_tp_accumulate(TemporalCall T)
+{
+    const int W = T.W, H = T.H;
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (size_t)W * H) return;
+    const float* f = T.feat + p * FRAYHIP_FEAT_CHANNELS;
+    const float Px = f[0], Py = f[1], Pz = f[2];
+    float nx = f[3], ny = f[4], nz = f[5];
+    const float nn = nx * nx + ny * ny + nz * nz;
+    if (nn > 0.0f) {                       // k_dn_prepare's unit normal
+        const float s = sqrtf(nn);
+        nx = nx / s; ny = ny / s; nz = nz / s;
+    }
+    const float* c = T.rgb + 3 * p;
+    float cr = c[0], cg = c[1], cb = c[2];
+    if (T.demodulate) { cr = cr / fmaxf(f[6], 1e-3f); cg = cg / fmaxf(f[7], 1e-3f); cb = cb / fmaxf(f[8], 1e-3f); }
+    const float l = tp_lum(cr, cg, cb);
+    const float l2 = l * l;
+
+    float sb = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hn = 0.0f, h1 = 0.0f, h2 = 0.0f;
+    const bool miss = nx == 0.0f && ny == 0.0f && nz == 0.0f;
+    if (T.histIn && !miss) {
+        const frayhip_view& V = T.view;
+        const float dx = Px - V.pos[0], dy = Py - V.pos[1], dz = Pz - V.pos[2];
+        const float zc = tp_dot(dx, dy, dz, V.front[0], V.front[1], V.front[2]);
+        if (zc > 0.0f) {
+            const float xc = tp_dot(dx, dy, dz, V.right[0], V.right[1], V.right[2]);
+            const float yc = tp_dot(dx, dy, dz, V.up[0], V.up[1], V.up[2]);
+            const float fx = ((xc / zc / V.tan_x + 1.0f) * 0.5f) * (float)W;
+            const float fy = ((1.0f - yc / zc / V.tan_y) * 0.5f) * (float)H;
+            const float u = fx - T.filmOffset, v = fy - T.filmOffset;
+            const float x0f = floorf(u), y0f = floorf(v);
+            // a footprint that touches the image (the comparisons are false for a NaN): only then do the floats fit an int
+            if (x0f >= -1.0f && x0f <= (float)(W - 1) && y0f >= -1.0f && y0f <= (float)(H - 1)) {
+                const int x0 = (int)x0f, y0 = (int)y0f;
+                const float tx = u - x0f, ty = v - y0f;
+                const float tol = T.planeTolerance * sqrtf(tp_dot(dx, dy, dz, dx, dy, dz));
+                for (int j = 0; j < 2; j++) {
+                    const int yq = y0 + j;
+                    if (yq < 0 || yq >= H) continue;
+                    for (int i = 0; i < 2; i++) {
+                        const int xq = x0 + i;
+                        if (xq < 0 || xq >= W) continue;
+                        const float4* hq = T.histIn + ((size_t)yq * W + xq) * 3;
+                        const float4 q0 = hq[0], q1 = hq[1], q2 = hq[2];
+                        if (q2.x == 0.0f && q2.y == 0.0f && q2.z == 0.0f) continue;
+                        if (!(tp_dot(nx, ny, nz, q2.x, q2.y, q2.z) >= T.normalMinDot)) continue;
+                        if (!(fabsf(tp_dot(q1.x - Px, q1.y - Py, q1.z - Pz, nx, ny, nz)) <= tol)) continue;
+                        const float b = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty);
+                        sb += b;
+                        hr += b * q0.x; hg += b * q0.y; hb += b * q0.z; hn += b * q0.w;
+                        h1 += b * q1.w; h2 += b * q2.w;
+                    }
+                }
+            }
+        }
+    }
+    float ar = cr, ag = cg, ab = cb, m1 = l, m2 = l2, N = 1.0f;
+    if (sb > 0.0f) {
+        hr = hr / sb; hg = hg / sb; hb = hb / sb; hn = hn / sb; h1 = h1 / sb; h2 = h2 / sb;
+        N = fminf(hn + 1.0f, T.maxHistory);
+        const float alpha = fmaxf(T.alphaMin, 1.0f / N);
+        ar = hr + alpha * (cr - hr); ag = hg + alpha * (cg - hg); ab = hb + alpha * (cb - hb);
+        m1 = h1 + alpha * (l - h1);
+        m2 = h2 + alpha * (l2 - h2);
+    }
+    float4* ho = T.histOut + p * 3;
+    ho[0] = make_float4(ar, ag, ab, N);
+    ho[1] = make_float4(Px, Py, Pz, m1);
+    ho[2] = make_float4(nx, ny, nz, m2);
+    float* s = T.signal + 3 * p;
+    s[0] = ar; s[1] = ag; s[2] = ab;
+    if (N >= (float)T.varianceHistory) T.variance[p] = fmaxf(0.0f, m2 - m1 * m1);
+}
+
+// A 16x16 block and the 22x22 texels its 7x7 windows reach: rows 1 and 2 of the history, 32 bytes a texel, 15.5 KB of LDS
+#define FRAY_TP_TILE_SIDE 22            // 16 + 2 * 3
+
+static __global__ __launch_bounds__(256) void k_tp_variance(TemporalCall T)
+{
+    const int W = T.W, H = T.H;
+    __shared__ float4 tile[FRAY_TP_TILE_SIDE * FRAY_TP_TILE_SIDE * 2];
+    const int tilesX = (W + 15) / 16;                // the tiles in row-major order along grid x (grid y would cap a tall image at 2^20 rows)
+    const int bx = (int)(blockIdx.x % (unsigned)tilesX) * 16, by = (int)(blockIdx.x / (unsigned)tilesX) * 16;
+    const int lx = (int)threadIdx.x & 15, ly = (int)threadIdx.x >> 4;
+    const int x = bx + lx, y = by + ly;
+    const bool inside = x < W && y < H;
+    const size_t p = inside ? (size_t)y * W + x : 0;
+    const float4* hp = T.histOut + p * 3;
+    const float N = hp[0].w;
+    const bool young = inside && N < (float)T.varianceHistory;
+    if (!__syncthreads_or(young)) return;            // a block whose pixels all have their history stages nothing
+    for (int t = (int)threadIdx.x; t < FRAY_TP_TILE_SIDE * FRAY_TP_TILE_SIDE; t += 256) {
+        const int ty = t / FRAY_TP_TILE_SIDE, tx = t - ty * FRAY_TP_TILE_SIDE;
+        const int xq = bx + tx - 3, yq = by + ty - 3;
+        if (xq >= 0 && xq < W && yq >= 0 && yq < H) {
+            const float4* hq = T.histOut + ((size_t)yq * W + xq) * 3;
+            tile[2 * t] = hq[1];
+            tile[2 * t + 1] = hq[2];
+        }
+    }
+    __syncthreads();
+    if (!young) return;
+    const float4 p1 = hp[1], p2 = hp[2];
+    const bool pZero = p2.x == 0.0f && p2.y == 0.0f && p2.z == 0.0f;
+    const float tol = T.planeTolerance * T.feat[p * FRAYHIP_FEAT_CHANNELS + 9];
+    float s1 = 0.0f, s2 = 0.0f, cnt = 0.0f;
+    for (int j = -3; j <= 3; j++) {
+        const int yq = y + j;
+        if (yq < 0 || yq >= H) continue;
+        for (int i = -3; i <= 3; i++) {
+            const int xq = x + i;
+            if (xq < 0 || xq >= W) continue;
+            const int t = (ly + 3 + j) * FRAY_TP_TILE_SIDE + (lx + 3 + i);
+            const float4 q1 = tile[2 * t], q2 = tile[2 * t + 1];
+            const bool qZero = q2.x == 0.0f && q2.y == 0.0f && q2.z == 0.0f;
+            if (pZero || qZero) {
+                if (!(pZero && qZero)) continue;
+            } else {
+                if (!(tp_dot(p2.x, p2.y, p2.z, q2.x, q2.y, q2.z) >= T.normalMinDot)) continue;
+                if (!(fabsf(tp_dot(q1.x - p1.x, q1.y - p1.y, q1.z - p1.z, p2.x, p2.y, p2.z)) <= tol)) continue;
+            }
+            s1 += q1.w; s2 += q2.w; cnt += 1.0f;
+        }
+    }
+    float mean1 = p1.w, mean2 = p2.w;
+    if (cnt > 0.0f) { mean1 = s1 / cnt; mean2 = s2 / cnt; }
+    T.variance[p] = fmaxf(0.0f, mean2 - mean1 * mean1) * ((float)T.varianceHistory / N);
+}
+
+namespace {
+
+using namespace frayhip_detail;
+
+bool overlaps(const void* a, size_t an, const void* b, size_t bn)
+{
+    if (!a || !b) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bn && y < x + an;
+}
+
+bool finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+
+// Every check of both entries, in this order; none touches the device.
+int check(const char* who, int W, int H, const float* rgb, const float* feat, const frayhip_view* view, const float* histIn, const struct frayhip_temporal* p,
+          const float* histOut, const float* signal, const float* variance, bool device)
+{
+    if (W < 1 || H < 1) return bad(who, "width and height must be >= 1");
+    if ((long long)W * H > (1ll << 30)) return bad(who, "more than 2^30 pixels");
+    if (!rgb) return bad(who, "null rgb");
+    if (!feat) return bad(who, "null feat");
+    if (!p) return bad(who, "null parameters");
+    if (!histOut) return bad(who, "null hist_out");
+    if (!signal) return bad(who, "null signal");
+    if (!variance) return bad(who, "null variance");
+    if (!histIn != !view) return bad(who, "hist_in and prev_view must both be given or both be null");
+    if (device) {
+        for (const void* q : {(const void*)rgb, (const void*)feat, (const void*)signal, (const void*)variance})
+            if (misaligned(q, 4)) return bad(who, "device pointer to floats not 4-byte aligned");
+        if (misaligned(histIn, 16) || misaligned(histOut, 16)) return bad(who, "device pointer to a history not 16-byte aligned");
+    }
+    if (view) {
+        if (view->width != W || view->height != H) return bad(who, "prev_view's size is not the frame's");
+        if (!finite3(view->pos) || !finite3(view->right) || !finite3(view->up) || !finite3(view->front) || !std::isfinite(view->tan_x) || !std::isfinite(view->tan_y))
+            return bad(who, "prev_view has a non-finite field");
+        if (!(view->tan_x > 0) || !(view->tan_y > 0)) return bad(who, "prev_view's tan_x and tan_y must be > 0");
+    }
+    if (p->demodulate != 0 && p->demodulate != 1) return bad(who, "demodulate must be 0 or 1");
+    if (p->max_history < 1 || p->max_history > 4096) return bad(who, "max_history must be 1..4096");
+    if (p->variance_history < 1 || p->variance_history > 4096) return bad(who, "variance_history must be 1..4096");
+    if (!(p->alpha_min >= 0 && p->alpha_min <= 1)) return bad(who, "alpha_min must be 0..1");
+    if (!std::isfinite(p->film_offset)) return bad(who, "film_offset must be finite");
+    if (!std::isfinite(p->plane_tolerance) || p->plane_tolerance < 0) return bad(who, "plane_tolerance must be finite and >= 0");
+    if (!(p->normal_min_dot >= -1 && p->normal_min_dot <= 1)) return bad(who, "normal_min_dot must be -1..1");
+    const size_t n = (size_t)W * H;
+    const struct { const void* q; size_t bytes; } ins[3] = {{rgb, 12 * n}, {feat, 4 * FRAYHIP_FEAT_CHANNELS * n}, {histIn, 4 * FRAYHIP_HISTORY_CHANNELS * n}};
+    const struct { const void* q; size_t bytes; const char* name; } outs[3] = {{histOut, 4 * FRAYHIP_HISTORY_CHANNELS * n, "hist_out"}, {signal, 12 * n, "signal"},
+                                                                                 {variance, 4 * n, "variance"}};
+    for (int o = 0; o < 3; o++) {
+        for (const auto& in : ins)
+            if (overlaps(outs[o].q, outs[o].bytes, in.q, in.bytes)) return bad(who, std::string(outs[o].name) + " must not overlap an input");
+        for (int k = 0; k < o; k++)
+            if (overlaps(outs[o].q, outs[o].bytes, outs[k].q, outs[k].bytes)) return bad(who, std::string(outs[o].name) + " must not overlap " + outs[k].name);
+    }
+    return FRAYHIP_OK;
+}
+
+struct Events {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
+
+// The device path of both entries (device pointers, checked)
+int run(int W, int H, const float* rgb, const float* feat, const frayhip_view* view, const float* histIn, const struct frayhip_temporal* prm, float* histOut,
+        float* signal, float* variance, hipStream_t stream, frayhip_stats* st, std::chrono::steady_clock::time_point t0)
+{
+    const size_t n = (size_t)W * H;
+    TemporalCall T{};
+    T.W = W; T.H = H;
+    T.rgb = rgb; T.feat = feat;
+    T.histIn = (const float4*)histIn; T.histOut = (float4*)histOut;
+    T.signal = signal; T.variance = variance;
+    if (view) T.view = *view;
+    T.demodulate = prm->demodulate; T.varianceHistory = prm->variance_history;
+    T.maxHistory = (float)prm->max_history; T.alphaMin = prm->alpha_min; T.filmOffset = prm->film_offset;
+    T.planeTolerance = prm->plane_tolerance; T.normalMinDot = prm->normal_min_dot;
+    Events E;
+    HIP_TRY(hipEventCreate(&E.a));
+    HIP_TRY(hipEventCreate(&E.b));
+    struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{stream};
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    HIP_TRY(hipEventRecord(E.a, stream));
+    hipLaunchKernelGGL(k_tp_accumulate, grid, block, 0, stream, T);
+    HIP_TRY(hipGetLastError());
+    if (prm->variance_history > 1) {         // N >= 1 always: with variance_history 1 no pixel takes the spatial estimate
+        hipLaunchKernelGGL(k_tp_variance, dim3((unsigned)((W + 15) / 16) * (unsigned)((H + 15) / 16)), block, 0, stream, T);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(E.b, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.armed = false;
+    if (st) {
+        frayhip_stats o{};
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, E.a, E.b);
+        o.ms_kernels = ms;
+        o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        *st = o;
+    }
+    return FRAYHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int frayhip_view_from_camera(const frayhip_camera* c, int width, int height, frayhip_view* out)
+{
+    const char* who = "frayhip_view_from_camera";
+    if (!c) return bad(who, "null camera");
+    if (!out) return bad(who, "null view");
+    if (width < 1 || height < 1) return bad(who, "width and height must be >= 1");
+    for (const double v : {c->pos[0], c->pos[1], c->pos[2], c->yaw, c->pitch, c->roll, c->fov, c->aspectRatio})
+        if (!std::isfinite(v)) return bad(who, "pos, yaw, pitch, roll, fov and aspectRatio must be finite");
+    if (!(c->fov > 0 && c->fov < 180)) return bad(who, "fov must be inside (0, 180)");
+    if (!(c->aspectRatio > 0)) return bad(who, "aspectRatio must be > 0");
+    const DCamera f = camera_begin_frame(*c, width, height);
+    // m of Camera::beginFrame, as camera_begin_frame derives it: the corners are rotations of (+-aspect * m, +-m, 1)
+    const double PI = 3.141592653589793238;
+    const double aspect = c->aspectRatio;
+    const double m = tan(c->fov / 2 / 180.0 * PI) / sqrt(aspect * aspect + 1.0);
+    frayhip_view v{};
+    for (int k = 0; k < 3; k++) {
+        v.pos[k] = (float)f.pos[k];
+        v.right[k] = (float)f.rightDir[k];
+        v.up[k] = (float)f.upDir[k];
+        v.front[k] = (float)f.frontDir[k];
+    }
+    v.tan_x = (float)(aspect * m);
+    v.tan_y = (float)m;
+    v.width = width; v.height = height;
+    if (!finite3(v.pos) || !(v.tan_x > 0) || !(v.tan_y > 0) || !std::isfinite(v.tan_x) || !std::isfinite(v.tan_y))
+        return bad(who, "the camera does not round to a finite FP32 view");
+    *out = v;
+    return FRAYHIP_OK;
+}
+
+int frayhip_temporal_defaults(struct frayhip_temporal* p)
+{
+    if (!p) return bad("frayhip_temporal_defaults", "null parameters");
+    p->demodulate = 1;
+    p->max_history = 32;
+    p->variance_history = 4;
+    p->alpha_min = 0.05f;
+    p->film_offset = 0.5f;
+    p->plane_tolerance = 0.02f;
+    p->normal_min_dot = 0.9f;
+    return FRAYHIP_OK;
+}
+
+int frayhip_temporal_accumulate_device(int width, int height, const float* d_rgb, const float* d_feat, const frayhip_view* prev_view, const float* d_hist_in,
+                                       const struct frayhip_temporal* p, float* d_hist_out, float* d_signal, float* d_variance, void* hip_stream, frayhip_stats* st)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (const int rc = check("frayhip_temporal_accumulate_device", width, height, d_rgb, d_feat, prev_view, d_hist_in, p, d_hist_out, d_signal, d_variance, true))
+        return rc;
+    return run(width, height, d_rgb, d_feat, prev_view, d_hist_in, p, d_hist_out, d_signal, d_variance, (hipStream_t)hip_stream, st, t0);
+}
+
+int frayhip_temporal_accumulate(int width, int height, const float* rgb, const float* feat, const frayhip_view* prev_view, const float* hist_in,
+                                const struct frayhip_temporal* p, float* hist_out, float* signal, float* variance, frayhip_stats* st)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const char* who = "frayhip_temporal_accumulate";
+    if (const int rc = check(who, width, height, rgb, feat, prev_view, hist_in, p, hist_out, signal, variance, false)) return rc;
+    const size_t n = (size_t)width * height;
+    const size_t HC = FRAYHIP_HISTORY_CHANNELS;
+    // one allocation, the histories first (16-byte rows): hist_out, hist_in when given, then rgb, feat, signal, variance
+    DeviceArrays B(std::string(who) + ": out of device memory");
+    float* d_hout;
+    if (const int rc = B.alloc(d_hout, n * (HC + (hist_in ? HC : 0) + 3 + FRAYHIP_FEAT_CHANNELS + 3 + 1))) return rc;
+    float* d_hin = hist_in ? d_hout + HC * n : nullptr;
+    float* d_rgb = d_hout + HC * n * (hist_in ? 2 : 1);
+    float* d_feat = d_rgb + 3 * n;
+    float* d_signal = d_feat + FRAYHIP_FEAT_CHANNELS * n;
+    float* d_var = d_signal + 3 * n;
+    HIP_TRY(hipMemcpy(d_rgb, rgb, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_feat, feat, n * 4 * FRAYHIP_FEAT_CHANNELS, hipMemcpyHostToDevice));
+    if (d_hin) HIP_TRY(hipMemcpy(d_hin, hist_in, n * 4 * HC, hipMemcpyHostToDevice));
+    if (const int rc = run(width, height, d_rgb, d_feat, prev_view, d_hin, p, d_hout, d_signal, d_var, nullptr, st, t0)) return rc;
+    HIP_TRY(hipMemcpy(hist_out, d_hout, n * 4 * HC, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(signal, d_signal, n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(variance, d_var, n * 4, hipMemcpyDeviceToHost));
+    if (st) st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return FRAYHIP_OK;
+}
+
+}  // extern "C"

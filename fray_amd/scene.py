@@ -158,6 +158,44 @@ def denoise_params(**params):
     return p
 
 
+def _frame_inputs(who, named):
+    """The per-pixel inputs of a scene-free entry, [(name, value, channels)] (channels 0: a plane shaped [H, W]): numpy arrays or device torch
+    tensors (not a mix), float32, all of one size.  Returns (contiguous inputs, (H, W), whether they are tensors)."""
+    tensors = [_torch_tensor(v) for _, v, _ in named]
+    if any(tensors) and not all(tensors):
+        raise TypeError("%s: pass numpy arrays or torch tensors, not a mix" % who)
+    shape = None
+    ins = []
+    for name, v, width in named:
+        if tensors[0]:
+            import torch
+            if not v.is_cuda:
+                raise TypeError("%s: %s is a CPU tensor; pass a tensor on the GPU (device entry) or a numpy array (host entry)" % (who, name))
+            if v.dtype != torch.float32:
+                raise TypeError("%s: %s must be float32, got %s" % (who, name, v.dtype))
+            if ins and v.device != ins[0].device:
+                raise ValueError("%s: the inputs are on different devices" % who)
+            v = v.contiguous()
+        else:
+            v = np.ascontiguousarray(v)
+            if v.dtype != np.float32:
+                raise TypeError("%s: %s must be float32, got %s" % (who, name, v.dtype))
+        if width == 0:
+            if v.ndim != 2:
+                raise ValueError("%s: %s must be shaped [H, W], got %s" % (who, name, tuple(v.shape)))
+        elif v.ndim != 3 or v.shape[2] != width:
+            raise ValueError("%s: %s must be shaped [H, W, %d], got %s" % (who, name, width, tuple(v.shape)))
+        if shape is not None and tuple(v.shape[:2]) != shape:
+            raise ValueError("%s: the inputs' sizes differ: %s and %s" % (who, shape, tuple(v.shape[:2])))
+        shape = tuple(v.shape[:2])
+        ins.append(v)
+    return ins, shape, tensors[0]
+
+
+def _ptr(v):
+    return None if v is None else v.data_ptr() if _torch_tensor(v) else v.ctypes.data
+
+
 def denoise(rgb, feat, rgb_half=None, stats=False, stream=None, **params):
     """The edge-avoiding a-trous filter of include/frayhip.h (frayhip_denoise): rgb [H, W, 3] float32, feat [H, W, 10] float32 (render_features),
     rgb_half [H, W, 3] float32 or None (the frame of the first half of rgb's samples: the filter's noise estimate).  numpy arrays go through the
@@ -165,42 +203,89 @@ def denoise(rgb, feat, rgb_half=None, stats=False, stream=None, **params):
     Returns the filtered frame (same kind as rgb), and with stats=True also the stats dict (ms_total, ms_kernels)."""
     p = denoise_params(**params)
     named = [("rgb", rgb, 3), ("feat", feat, abi.FEAT_CHANNELS)] + ([("rgb_half", rgb_half, 3)] if rgb_half is not None else [])
-    tensors = [_torch_tensor(v) for _, v, _ in named]
-    if any(tensors) and not all(tensors):
-        raise TypeError("denoise: pass numpy arrays or torch tensors, not a mix")
-    shape = None
-    ins = []
-    for name, v, width in named:
-        if tensors[0]:
-            import torch
-            if not v.is_cuda:
-                raise TypeError("denoise: %s is a CPU tensor; pass a tensor on the GPU (device entry) or a numpy array (host entry)" % name)
-            if v.dtype != torch.float32:
-                raise TypeError("denoise: %s must be float32, got %s" % (name, v.dtype))
-            v = v.contiguous()
-        else:
-            v = np.ascontiguousarray(v)
-            if v.dtype != np.float32:
-                raise TypeError("denoise: %s must be float32, got %s" % (name, v.dtype))
-        if v.ndim != 3 or v.shape[2] != width:
-            raise ValueError("denoise: %s must be shaped [H, W, %d], got %s" % (name, width, tuple(v.shape)))
-        if shape is not None and tuple(v.shape[:2]) != shape:
-            raise ValueError("denoise: the inputs' sizes differ: %s and %s" % (shape, tuple(v.shape[:2])))
-        shape = tuple(v.shape[:2])
-        ins.append(v)
-    H, W = shape
+    ins, (H, W), tensors = _frame_inputs("denoise", named)
     half = ins[2] if rgb_half is not None else None
     st = abi.Stats()
-    if not tensors[0]:
+    if not tensors:
         out = np.empty((H, W, 3), np.float32)
-        _check(lib.frayhip_denoise(W, H, ins[0].ctypes.data, half.ctypes.data if half is not None else None, ins[1].ctypes.data, C.byref(p),
-                                   out.ctypes.data, C.byref(st)))
+        _check(lib.frayhip_denoise(W, H, _ptr(ins[0]), _ptr(half), _ptr(ins[1]), C.byref(p), out.ctypes.data, C.byref(st)))
     else:
         with _DeviceCall(ins[0].device, stream) as call:
             out = call.torch.empty((H, W, 3), dtype=call.torch.float32, device=ins[0].device)
-            _check(lib.frayhip_denoise_device(W, H, ins[0].data_ptr(), half.data_ptr() if half is not None else None, ins[1].data_ptr(), C.byref(p),
-                                              out.data_ptr(), call.handle, C.byref(st)))
+            _check(lib.frayhip_denoise_device(W, H, _ptr(ins[0]), _ptr(half), _ptr(ins[1]), C.byref(p), out.data_ptr(), call.handle, C.byref(st)))
     return (out, st.as_dict()) if stats else out
+
+
+def denoise_signal(signal, variance, feat, stats=False, stream=None, **params):
+    """The a-trous levels on a given signal and variance (frayhip_denoise_signal): signal [H, W, 3] and variance [H, W] as temporal_accumulate
+    returns them, feat [H, W, 10]; float32.  With demodulate (the default) the signal is taken as already demodulated and the albedo is
+    multiplied back.  numpy arrays or GPU torch tensors, `stream`, params and the return value as denoise()."""
+    p = denoise_params(**params)
+    ins, (H, W), tensors = _frame_inputs("denoise_signal", [("signal", signal, 3), ("variance", variance, 0), ("feat", feat, abi.FEAT_CHANNELS)])
+    st = abi.Stats()
+    if not tensors:
+        out = np.empty((H, W, 3), np.float32)
+        _check(lib.frayhip_denoise_signal(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), C.byref(p), out.ctypes.data, C.byref(st)))
+    else:
+        with _DeviceCall(ins[0].device, stream) as call:
+            out = call.torch.empty((H, W, 3), dtype=call.torch.float32, device=ins[0].device)
+            _check(lib.frayhip_denoise_signal_device(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), C.byref(p), out.data_ptr(), call.handle, C.byref(st)))
+    return (out, st.as_dict()) if stats else out
+
+
+_denoise_params = denoise_params         # Scene.render_sequence takes **denoise_params
+_TEMPORAL_FIELDS = ("demodulate", "max_history", "variance_history", "alpha_min", "film_offset", "plane_tolerance", "normal_min_dot")
+
+
+def temporal_params(**params):
+    """frayhip_temporal_defaults, with the named fields replaced (demodulate, max_history, variance_history, alpha_min, film_offset,
+    plane_tolerance, normal_min_dot)."""
+    p = abi.Temporal()
+    _check(lib.frayhip_temporal_defaults(C.byref(p)))
+    for k, v in params.items():
+        if k not in _TEMPORAL_FIELDS:
+            raise TypeError("temporal: unknown parameter %r (known: %s)" % (k, ", ".join(_TEMPORAL_FIELDS)))
+        setattr(p, k, v)
+    return p
+
+
+def view_from_camera(camera, width, height):
+    """frayhip_view_from_camera: the abi.View of an abi.Camera (Scene.camera) on a width x height film -- the previous view that
+    temporal_accumulate reprojects into."""
+    if not isinstance(camera, abi.Camera):
+        raise TypeError("view_from_camera: camera must be an abi.Camera, got %s" % type(camera).__name__)
+    v = abi.View()
+    _check(lib.frayhip_view_from_camera(C.byref(camera), int(width), int(height), C.byref(v)))
+    return v
+
+
+def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, stream=None, **params):
+    """The temporal stage of include/frayhip.h (frayhip_temporal_accumulate): rgb [H, W, 3] and feat [H, W, 10] of the current frame, prev_view
+    (view_from_camera of the previous frame's camera) and hist_in [H, W, 12] (the previous call's history), both None for the first frame;
+    float32.  numpy arrays go through the host entry; torch tensors on the GPU through the device entry, on `stream` (None: the current
+    stream).  params: see temporal_params.  Returns (hist_out [H, W, 12], signal [H, W, 3], variance [H, W]) of the inputs' kind -- signal and
+    variance are denoise_signal's inputs -- and with stats=True also the stats dict (ms_total, ms_kernels)."""
+    p = temporal_params(**params)
+    if (prev_view is None) != (hist_in is None):
+        raise ValueError("temporal_accumulate: prev_view and hist_in must both be given or both be None")
+    if prev_view is not None and not isinstance(prev_view, abi.View):
+        raise TypeError("temporal_accumulate: prev_view must be an abi.View (view_from_camera), got %s" % type(prev_view).__name__)
+    named = [("rgb", rgb, 3), ("feat", feat, abi.FEAT_CHANNELS)] + ([("hist_in", hist_in, abi.HISTORY_CHANNELS)] if hist_in is not None else [])
+    ins, (H, W), tensors = _frame_inputs("temporal_accumulate", named)
+    hin = ins[2] if hist_in is not None else None
+    view = C.byref(prev_view) if prev_view is not None else None
+    st = abi.Stats()
+    if not tensors:
+        hist, signal, var = (np.empty((H, W, abi.HISTORY_CHANNELS), np.float32), np.empty((H, W, 3), np.float32), np.empty((H, W), np.float32))
+        _check(lib.frayhip_temporal_accumulate(W, H, _ptr(ins[0]), _ptr(ins[1]), view, _ptr(hin), C.byref(p), hist.ctypes.data, signal.ctypes.data,
+                                               var.ctypes.data, C.byref(st)))
+    else:
+        with _DeviceCall(ins[0].device, stream) as call:
+            new = lambda *shape: call.torch.empty(shape, dtype=call.torch.float32, device=ins[0].device)
+            hist, signal, var = new(H, W, abi.HISTORY_CHANNELS), new(H, W, 3), new(H, W)
+            _check(lib.frayhip_temporal_accumulate_device(W, H, _ptr(ins[0]), _ptr(ins[1]), view, _ptr(hin), C.byref(p), hist.data_ptr(),
+                                                          signal.data_ptr(), var.data_ptr(), call.handle, C.byref(st)))
+    return (hist, signal, var, st.as_dict()) if stats else (hist, signal, var)
 
 
 class Scene:
@@ -538,6 +623,57 @@ class Scene:
         feat, fst = self.render_features(min(int(feature_samples), spp), seed=seed, stats=True)
         out, dst = denoise(raw, feat, half, stats=True, **params)
         return out, raw, {"render": rst, "features": fst, "denoise": dst, "rgb_half": half, "features_frame": feat}
+
+    def render_sequence(self, cameras, seed=42, feature_samples=4, temporal=None, **denoise_params):
+        """A generator over a fly-through of a static scene with temporal accumulation (include/frayhip.h "temporal accumulation"): for the k-th
+        abi.Camera of `cameras` it sets the view, renders the feature frame and the frame with seed + k (equal seeds would accumulate the same
+        noise every frame), accumulates onto the previous frame's history reprojected into this view, runs the a-trous levels on the accumulated
+        signal and its variance, and yields (denoised, raw, info): torch tensors on the GPU, float32 [H, W, 3]; raw is render(seed + k) of that
+        view, bit for bit.  Every buffer stays on the device.  info: "features_frame", "history" [H, W, 12], "signal", "variance", "view"
+        (this frame's abi.View), "film_offset", and the "render", "features", "temporal" and "denoise" stats dicts.
+        temporal: a dict of temporal_params fields.  film_offset defaults to where a pixel's samples lie on average: 0.5 for gi and DOF frames
+        (uniform jitter), 0.3 for a Whitted frame with wantAA (the mean of the five AA offsets), 0 for a plain Whitted frame.  The filter and
+        the accumulation share `demodulate` (denoise_params; default 1).  Stereo frames and long generators are refused (FrayError) as
+        render_features refuses them.  The scene's camera is restored when the generator ends or is closed."""
+        self._need_dev()
+        import torch
+        W, H = self.frame_size
+        spp = self.samples_per_pixel()
+        tparams = dict(temporal or {})
+        if "film_offset" not in tparams:
+            tparams["film_offset"] = 0.5 if (self.settings.gi or self.camera.dof) else 0.3 if self.settings.wantAA else 0.0
+        dparams = _denoise_params(**denoise_params)
+        if tparams.setdefault("demodulate", dparams.demodulate) != dparams.demodulate:
+            raise ValueError("render_sequence: the accumulation and the filter must agree on demodulate")
+        temporal_params(**tparams)                      # unknown fields are refused before anything is rendered
+        n_feat = min(int(feature_samples), spp)
+        saved = abi.Camera.from_buffer_copy(self.desc.camera)
+        stream = torch.cuda.current_stream()
+        handle = C.c_void_p(stream.cuda_stream)
+        hist, view = None, None
+        try:
+            for k, cam in enumerate(cameras):
+                if not isinstance(cam, abi.Camera):
+                    raise TypeError("render_sequence: cameras must yield abi.Camera records, got %s" % type(cam).__name__)
+                C.memmove(C.byref(self.desc.camera), C.byref(cam), C.sizeof(abi.Camera))
+                self.beginFrame()
+                feat = torch.empty((H, W, abi.FEAT_CHANNELS), dtype=torch.float32, device="cuda")
+                raw = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+                fst, rst = abi.Stats(), abi.Stats()
+                fr = self._frame(abi.MODE_RENDER, (seed + k) & 0xFFFFFFFF, 0, 1, 0, False)
+                _check(lib.frayhip_render_features_device(self._dev, C.byref(fr), n_feat, feat.data_ptr(), handle, C.byref(fst)))
+                _check(lib.frayhip_render_device(self._dev, C.byref(fr), raw.data_ptr(), None, None, handle, C.byref(rst)))
+                hist, signal, var, tst = temporal_accumulate(raw, feat, view, hist, stats=True, stream=stream, **tparams)
+                out, dst = denoise_signal(signal, var, feat, stats=True, stream=stream, **denoise_params)
+                view = view_from_camera(self.desc.camera, W, H)
+                yield out, raw, {"features_frame": feat, "history": hist, "signal": signal, "variance": var, "view": view,
+                                 "film_offset": tparams["film_offset"], "render": rst.as_dict(), "features": fst.as_dict(), "temporal": tst,
+                                 "denoise": dst}
+        finally:
+            if self.desc is not None:
+                C.memmove(C.byref(self.desc.camera), C.byref(saved), C.sizeof(abi.Camera))
+                if self._dev:
+                    self.beginFrame()
 
     def close(self):
         self.endRender()

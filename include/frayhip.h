@@ -581,8 +581,88 @@ int  frayhip_denoise(int width, int height, const float* rgb, const float* rgb_h
                      const struct frayhip_denoise* p, float* out, frayhip_stats* st);
 int  frayhip_denoise_device(int width, int height, const float* d_rgb, const float* d_rgb_half, const float* d_feat,
                             const struct frayhip_denoise* p, float* d_out, void* hip_stream, frayhip_stats* st);
-/* Not covered: temporal reprojection, learned denoisers, adaptive and stereo frames, and denoising across ranks (gather the frame and its
- * features first: frayhip_gather_buckets takes a channel count). */
+/* The a-trous levels alone, on a signal and a variance the caller already has (frayhip_temporal_accumulate's outputs): signal (W*H*3) takes the
+ * place of the signal k_dn_prepare derives from rgb, variance (W*H) that of the prefiltered estimate, and the levels run as they do with
+ * rgb_half (w_l from the variance).  With demodulate the signal is taken as already demodulated, and the last level multiplies
+ * max(albedo_p, 1e-3) back.  Guides, buffers, stream contract, *st and the FRAYHIP_E_ARG cases as frayhip_denoise (signal for rgb; a NULL
+ * variance is refused; out must not overlap signal, variance or feat). */
+int  frayhip_denoise_signal(int width, int height, const float* signal, const float* variance, const float* feat,
+                            const struct frayhip_denoise* p, float* out, frayhip_stats* st);
+int  frayhip_denoise_signal_device(int width, int height, const float* d_signal, const float* d_variance, const float* d_feat,
+                                   const struct frayhip_denoise* p, float* d_out, void* hip_stream, frayhip_stats* st);
+
+/* ---- temporal accumulation (the temporal stage of SVGF, scene-free) --------------------------------------------------------------------------
+ * Reprojects the previous frame's accumulated colour and luminance moments into the current view through the feature frame's world positions,
+ * rejects history that belongs to another surface, blends the new frame in, and hands frayhip_denoise_signal a per-pixel variance that comes
+ * from the moments.  FP32 throughout, no contraction, every sum in the order written here (tests/temporal_ref.py restates it in numpy).
+ *
+ * frayhip_view: a camera as the kernel reads it.  frayhip_view_from_camera derives the frame of Camera::beginFrame (FP64, as the renderer
+ * does) for a W x H film and rounds it to FP32.  getScreenRay(x, y) is parallel to front + right * tan_x * (2x/W - 1) + up * tan_y * (1 - 2y/H),
+ * so a world point P lands on the film of that view at
+ *     d  = P - pos;  zc = d . front;  xc = d . right;  yc = d . up              dots as (a0*b0 + a1*b1) + a2*b2
+ *     fx = (xc / zc / tan_x + 1) * 0.5 * W
+ *     fy = (1 - yc / zc / tan_y) * 0.5 * H                                       (behind the camera when zc <= 0)
+ * Stereo and DOF play no part: the view is the centre camera's pinhole.  Host arithmetic only; no device is touched.
+ * FRAYHIP_E_ARG: a NULL pointer, width or height < 1, a non-finite pos, yaw, pitch, roll, fov or aspectRatio, fov outside (0, 180),
+ *   aspectRatio <= 0.
+ *
+ * History: FRAYHIP_HISTORY_CHANNELS = 12 floats per pixel, three 16-byte rows: {acc.rgb, N}, {P.xyz, m1}, {n.xyz, m2} -- the accumulated
+ * signal and its sample count N (a float: a bilinear fetch may return a fractional count), the pixel's world position and unit normal (the
+ * feature frame's normal scaled to unit length as the filter does; zero for a miss), and the running means m1, m2 of the signal's luminance
+ * l = (r + g + b) / 3 and of its square.  hist_in and prev_view are both NULL (first frame) or both given; hist_out must not overlap hist_in
+ * (the caller ping-pongs two buffers).  signal (W*H*3) is the accumulated colour in the filter's domain, variance (W*H) its luminance variance.
+ *
+ * Per pixel p:
+ *  1. c = rgb_p, or rgb_p / max(albedo_p, 1e-3) per channel with demodulate; l = l(c); P, n, z from feat.  A pixel whose normal is exactly
+ *     zero takes no history.
+ *  2. P is projected into prev_view; u = fx - film_offset, v = fy - film_offset (film_offset: where inside pixel i its samples lie on average,
+ *     0.5 for jittered samples, 0 for rays through the integer film position); x0 = floor(u), y0 = floor(v); the four taps (x0 + i, y0 + j),
+ *     j outer, with the bilinear weights b.  A tap counts when it lies inside the image, its stored normal is not zero,
+ *     n . n_q >= normal_min_dot, and its stored position lies on p's surface: |(P_q - P) . n| <= plane_tolerance * sqrt(d . d).  With
+ *     sum(b) > 0 over the counted taps the history is sum(b h_q) / sum(b) for acc, m1, m2 and N; otherwise there is none.
+ *  3. N = min(N_hist + 1, max_history), alpha = max(alpha_min, 1 / N); acc = h + alpha (c - h) per channel, likewise m1 with l and m2 with
+ *     l * l.  Without history: acc = c, m1 = l, m2 = l * l, N = 1.
+ *  4. Variance.  N >= variance_history: max(0, m2 - m1 * m1).  Below it, a second kernel over the finished hist_out: the 7 x 7 window around
+ *     p, j outer, i inner, the taps inside the image whose stored normal is not zero, with n . n_q >= normal_min_dot and
+ *     |(P_q - P) . n| <= plane_tolerance * z_p (for a p whose normal is zero: the taps whose normal is zero too); mean1, mean2 the unweighted
+ *     means of their m1 and m2 (p's own m1, m2 when no tap counts); max(0, mean2 - mean1 * mean1) * (variance_history / N).
+ * Kernels: k_tp_accumulate, then k_tp_variance when variance_history > 1.  No work buffers.  The _device entry takes DEVICE pointers (the two
+ *   histories 16-byte aligned, the rest 4-byte; prev_view and p stay HOST pointers), enqueues on hip_stream and returns after synchronising it.
+ * *st may be NULL; when given it holds ms_total and ms_kernels (the other fields are 0).
+ * FRAYHIP_E_ARG, before the device is touched: width or height < 1 or W*H > 2^30; NULL rgb, feat, p, hist_out, signal or variance; one of
+ *   hist_in / prev_view without the other; a view whose size is not W x H or with a non-finite field or a tan <= 0; demodulate not 0 or 1;
+ *   max_history outside 1..4096; variance_history outside 1..4096; alpha_min outside 0..1; a non-finite film_offset; plane_tolerance negative
+ *   or not finite; normal_min_dot outside -1..1; NaNs in any of them; an output overlapping an input or another output; a misaligned device
+ *   pointer. */
+#define FRAYHIP_HISTORY_CHANNELS 12
+typedef struct frayhip_view {
+    float   pos[3], right[3], up[3], front[3];   /* Camera::pos, rightDir, upDir, frontDir                                 */
+    float   tan_x, tan_y;                        /* aspectRatio * m and m of Camera::beginFrame                            */
+    int32_t width, height;
+} frayhip_view;
+int  frayhip_view_from_camera(const frayhip_camera* camera, int width, int height, frayhip_view* out);
+
+/* A struct tag without a typedef, as frayhip_denoise. */
+struct frayhip_temporal {
+    int32_t demodulate;        /* 1: accumulate rgb / max(albedo, 1e-3), as the filter does (default 1)                      */
+    int32_t max_history;       /* N is clamped to this; 1..4096, default 32                                                  */
+    int32_t variance_history;  /* below this N the variance is the spatial estimate; 1..4096, default 4                      */
+    float   alpha_min;         /* blend factor is max(alpha_min, 1 / N); 0..1, default 0.05                                  */
+    float   film_offset;       /* pixel i was sampled around film x = i + film_offset; default 0.5                           */
+    float   plane_tolerance;   /* |(P_q - P) . n| <= plane_tolerance * |P - pos_prev| keeps a tap; default 0.02              */
+    float   normal_min_dot;    /* n . n_q >= this keeps a tap; default 0.9                                                   */
+};
+int  frayhip_temporal_defaults(struct frayhip_temporal* p);
+int  frayhip_temporal_accumulate(int width, int height, const float* rgb, const float* feat, const frayhip_view* prev_view,
+                                 const float* hist_in, const struct frayhip_temporal* p, float* hist_out, float* signal, float* variance,
+                                 frayhip_stats* st);
+int  frayhip_temporal_accumulate_device(int width, int height, const float* d_rgb, const float* d_feat, const frayhip_view* prev_view,
+                                        const float* d_hist_in, const struct frayhip_temporal* p, float* d_hist_out, float* d_signal,
+                                        float* d_variance, void* hip_stream, frayhip_stats* st);
+/* Not covered: SVGF's wider 3 x 3 retry when no bilinear tap counts, feeding a filtered level back into the history, moving objects (the scene
+ * is static between frames), specular motion vectors (what a mirror shows moves with the camera while its first hit does not), learned
+ * denoisers, adaptive and stereo frames, and denoising across ranks (gather the frame and its features first: frayhip_gather_buckets takes a
+ * channel count). */
 
 /* Multi-GPU tile exchange helpers.  pack: gathers this rank's buckets from a
  * full-frame device buffer into a compact bucket-major buffer of
