@@ -237,6 +237,7 @@ DScene frame_scene(const frayhip_scene* s)
     S.maxTraceDepth = set.maxTraceDepth;
     S.gi = set.gi;
     S.saturation = set.saturation;
+    S.skipNullSegments = s->skipNullSegments ? 1 : 0;
     return S;
 }
 
@@ -827,6 +828,7 @@ int frayhip_scene_create(const frayhip_scene_desc* desc, frayhip_scene** out)
     if (const char* e = getenv("FRAYHIP_PT_LANES")) { long v = atol(e); if (v >= 1 && v <= FRAY_PT_LANES) sc->ptLanes = (int)v; }
     if (const char* e = getenv("FRAYHIP_SPECULATE_FANS")) sc->speculateFans = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_FP_CONTRACT")) sc->fpContract = atol(e) == 1;
+    if (const char* e = getenv("FRAYHIP_SKIP_NULL_SEGMENTS")) sc->skipNullSegments = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_FUSED_WHITTED_MAX")) { long v = atol(e); if (v >= 0 && v <= 1024) sc->fusedWhittedMax = (int)v; }
     if (const char* e = getenv("FRAYHIP_CSG_LANES")) { long v = atol(e); if (v >= 1 && v <= FRAY_PT_LANES) sc->csgLanes = (int)v; }
     if (const char* e = getenv("FRAYHIP_PT_BUDGET_MIB")) { long v = atol(e); if (v >= 1 && v <= (1 << 20)) { sc->ptBudgetBytes = (size_t)v << 20; sc->ptBudgetEff = 0; } }
@@ -843,6 +845,8 @@ int frayhip_scene_get_option(frayhip_scene* s, const char* name, int64_t* value)
     else if (n == "speculate_fans") *value = s->speculateFans ? 1 : 0;
     else if (n == "fp_contract") *value = s->fpContract ? 1 : 0;
     else if (n == "contracted_launches") *value = s->lastContracted;
+    else if (n == "skip_null_segments") *value = s->skipNullSegments ? 1 : 0;
+    else if (n == "shadow_segments") *value = s->lastShadowSegments;
     else if (n == "whitted_path") *value = s->lastWhittedPath;
     else if (n == "fused_whitted_max") *value = s->fusedWhittedMax;
     else if (n == "pt_budget_effective_mib") *value = (int64_t)(frayhip_detail::work_budget(s) >> 20);
@@ -875,6 +879,9 @@ int frayhip_scene_set_option(frayhip_scene* s, const char* name, int64_t value)
     } else if (n == "fp_contract") {
         if (value != 0 && value != 1) { set_error("frayhip_scene_set_option: fp_contract must be 0 or 1"); return FRAYHIP_E_ARG; }
         s->fpContract = value != 0;
+    } else if (n == "skip_null_segments") {
+        if (value != 0 && value != 1) { set_error("frayhip_scene_set_option: skip_null_segments must be 0 or 1"); return FRAYHIP_E_ARG; }
+        s->skipNullSegments = value != 0;
     } else {
         set_error("frayhip_scene_set_option: unknown option " + n);
         return FRAYHIP_E_ARG;

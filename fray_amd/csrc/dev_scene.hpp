@@ -194,6 +194,7 @@ struct DScene {
     float ambient[3];
     int32_t maxTraceDepth, gi;
     float saturation;
+    int32_t skipNullSegments;      // option "skip_null_segments": the timed path-tracing kernels do not queue a next-event segment whose contribution is +0 in all three channels (dev_shade.hpp nee_prepare)
 };
 
 // Work decomposition of a frame: the reference's 48x48 buckets (sdl.cpp:243-262), of which this

@@ -352,8 +352,13 @@ FD void spawn_ray(const FRAY_RO DShader& sh, const HitInfo& x, const PathRay& w_
 // random numbers or evaluates the BRDF happens here; the returned segment a->b and the contribution
 // go to the shadow queue, and k_pt_shadow adds `contrib` iff visible(a, b).  The reference asks
 // visible() before eval(); neither draws random numbers, so the order does not matter.
+// skipNull (wave-uniform; the timed kernels under option "skip_null_segments"): a sample whose contribution is +0.0f in all three channels BY BIT
+// PATTERN is reported as "no segment".  k_pt_shadow would store `visible ? contrib : c3(0, 0, 0)` for it, i.e. three +0 words whatever the
+// search answers, and that is the black term path_shade stores itself when nothing was queued -- so the any-hit search, the gate classification and
+// the queue entry are dropped and no stored word changes.  A -0.0f or NaN channel is NOT such a sample (visible would store it, hidden would store +0).
+// Every random draw happens before the first skip, so the generators leave in the same state either way.
 template <class GR, class GT>
-FD bool nee_prepare(const DScene& S, V3 rayDir, const HitInfo& info, C3 pm, const FRAY_RO DShader& sh, GR& rnd, GT& tab, V3& a, V3& b, C3& contrib)
+FD bool nee_prepare(const DScene& S, V3 rayDir, const HitInfo& info, C3 pm, const FRAY_RO DShader& sh, GR& rnd, GT& tab, V3& a, V3& b, C3& contrib, bool skipNull)
 {
     if (S.nLights == 0) return false;
     int lightIdx = rng_int0(rnd, S.nLights - 1);
@@ -365,15 +370,17 @@ FD bool nee_prepare(const DScene& S, V3 rayDir, const HitInfo& info, C3 pm, cons
     V3 pl;
     C3 unused;
     light_nth_sample(L, randSample, x, tab, pl, unused);
+    if (skipNull && (sh.kind == 3 || sh.kind == 4)) return false;   // Reflection / Refraction::eval: zero by construction, known before w_out is normalised
     a = x + info.norm * 1e-6;
     b = pl;
     C3 Le = light_color(L);
     V3 w_out = normalized(pl - x);
     C3 brdfAtPoint = brdf_eval(sh, info, w_out);
-    if (intensity(brdfAtPoint) == 0) { contrib = c3(0, 0, 0); return true; }
+    if (intensity(brdfAtPoint) == 0) { contrib = c3(0, 0, 0); return !skipNull; }
     float probHitLightArea = (float)fray_rcp(solidAngle);
     float probPickThisLight = S.probPickLight;
     float chooseLightProb = probHitLightArea * probPickThisLight;
     contrib = Le * pm * brdfAtPoint / chooseLightProb;
+    if (skipNull && (__float_as_uint(contrib.r) | __float_as_uint(contrib.g) | __float_as_uint(contrib.b)) == 0u) return false;
     return true;
 }

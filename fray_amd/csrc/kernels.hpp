@@ -851,7 +851,8 @@ FD void path_load_rest(const PathQueue& Q, uint32_t i, PathStateT<G>& s)
 // share, so it cannot overflow); it publishes one count.  A one-block scan turns the counts into
 // offsets; a consuming wave owns a contiguous range of dense indices and follows the segments that hold them
 // with a cursor (seg_map below).
-static __global__ __launch_bounds__(1024) void k_scan(QMeta* m0, QMeta* m1)
+// shadowTotal (may be null): m1 is a shadow queue; its entry count is added to this running total (one word per batch lane, render_state.hpp)
+static __global__ __launch_bounds__(1024) void k_scan(QMeta* m0, QMeta* m1, unsigned long long* shadowTotal)
 {
     QMeta* m = blockIdx.x == 0 ? m0 : m1;
     __shared__ uint32_t part[1024];
@@ -871,7 +872,10 @@ static __global__ __launch_bounds__(1024) void k_scan(QMeta* m0, QMeta* m1)
     uint32_t run = part[threadIdx.x] - sum;         // exclusive prefix of this thread's slice
     for (uint32_t k = 0; k < per; k++)
         if (b + k < nSeg) { m->off[b + k] = run; run += m->cnt[b + k]; }
-    if (threadIdx.x == 1023) { m->off[nSeg] = part[1023]; m->n = part[1023]; }
+    if (threadIdx.x == 1023) {
+        m->off[nSeg] = part[1023]; m->n = part[1023];
+        if (blockIdx.x == 1 && shadowTotal) *shadowTotal += part[1023];
+    }
 }
 
 // Queue 0 of a batch is dense: a single segment that holds every slot.
@@ -1166,7 +1170,7 @@ FD void path_shade(const DScene& S, PathStateT<G>& ps, const HitT<ST>& h, const 
             // that it is not carried in registers across the spawn
             V3 sa, sb;
             C3 sc;
-            shadow = nee_prepare(S, ps.d, info, ps.pm, sh, ps.rnd, ps.tab, sa, sb, sc);
+            shadow = nee_prepare(S, ps.d, info, ps.pm, sh, ps.rnd, ps.tab, sa, sb, sc, !(ST & 1) && S.skipNullSegments != 0);   // the counting variants trace every segment the reference traces
             if (shadow) {
                 shadowBack = ray_gate_class(S, sa, sb - sa);
                 const uint32_t j = seg_take(shadowEnds, shadowBack != 0);

@@ -54,7 +54,7 @@ int pt_bounces(frayhip_scene* sc, const DScene& S, const PathQueue (&Q)[2], cons
         hipLaunchKernelGGL((k_pt_bounce<ST, false>), dim3(grid), dim3(256), 0, stream, BA);
         HIP_TRY(hipEventRecord(eb, stream));
         nTraceEvents += 2;
-        hipLaunchKernelGGL(k_scan, dim3(2), dim3(1024), 0, stream, meta + ((b + 1) & 1), meta + 2);
+        hipLaunchKernelGGL(k_scan, dim3(2), dim3(1024), 0, stream, meta + ((b + 1) & 1), meta + 2, (unsigned long long*)nullptr);
         HIP_TRY(hipEventRecord(ec, stream));
         hipLaunchKernelGGL(k_pt_shadow<ST>, dim3(grid), dim3(256), 0, stream, ShadowArgs{S, SQ, mSh, TB, sc->d_stats + 1});
         HIP_TRY(hipEventRecord(ed, stream));
@@ -462,6 +462,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 unsigned short* termCount;
                 StereoBuf SB;
                 QMeta* meta;
+                unsigned long long* segTotal;       // this lane's running total of shadow-queue entries (render_state.hpp kSegTotalsOffset)
             } lane[FRAY_PT_LANES];
             unsigned char* p = (unsigned char*)sc->d_work;
             float* sum = (float*)p; p += ((size_t)nItems * 12 + 255) / 256 * 256;
@@ -469,6 +470,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 Lane& L = lane[k];
                 L.stream = k == 0 ? stream : sc->laneStream[k];
                 L.meta = sc->d_qmeta + 3 * k;
+                L.segTotal = (unsigned long long*)((unsigned char*)sc->d_stats + kSegTotalsOffset) + k;
                 p = carve_queue(p, nQueue, L.Q[0]);
                 p = carve_queue(p, nQueue, L.Q[1]);
                 p = carve_shadow(p, nQueue, L.SQ);
@@ -532,7 +534,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                         else hipLaunchKernelGGL((k_pt_bounce<ST, false>), dim3(grid), dim3(256), 0, ls, BA);
                         HIP_TRY(hipEventRecord(eb, ls));
                         nTraceEvents += 2;
-                        hipLaunchKernelGGL(k_scan, dim3(2), dim3(1024), 0, ls, L.meta + ((b + 1) & 1), L.meta + 2);
+                        hipLaunchKernelGGL(k_scan, dim3(2), dim3(1024), 0, ls, L.meta + ((b + 1) & 1), L.meta + 2, L.segTotal);
                         HIP_TRY(hipEventRecord(ec, ls));
                         bool contractedShadow = false;
                         if constexpr (!(ST & 2)) {
@@ -573,8 +575,12 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
     HIP_TRY(hipEventRecord(sc->evB, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     drain.armed = false;                    // every lane was joined into `stream` above
-    DStats dsv[2];
-    HIP_TRY(hipMemcpy(dsv, sc->d_stats, sizeof dsv, hipMemcpyDeviceToHost));
+    struct Back { DStats ds[2]; unsigned long long segTotal[FRAY_PT_LANES]; } back;         // the two counter blocks and the lanes' shadow-queue totals: one copy
+    static_assert(offsetof(Back, segTotal) == kSegTotalsOffset, "the shadow-queue totals follow the counter blocks");
+    HIP_TRY(hipMemcpy(&back, sc->d_stats, sizeof back, hipMemcpyDeviceToHost));
+    const DStats (&dsv)[2] = back.ds;
+    sc->lastShadowSegments = 0;
+    for (int k = 0; k < FRAY_PT_LANES; k++) sc->lastShadowSegments += (long long)back.segTotal[k];
     {
         unsigned long long ft[4] = {0, 0, 0, 0};
         if (fanTotals) HIP_TRY(hipMemcpy(ft, fanTotals, sizeof ft, hipMemcpyDeviceToHost));

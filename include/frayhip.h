@@ -301,12 +301,19 @@ int  frayhip_scene_set_view(frayhip_scene* s, const frayhip_camera* camera, cons
  *                          ones, "contracted_launches" 0), nor do Whitted frames (gi 0) or primary hit records; frames whose paths may draw more
  *                          than 227 random words per generator (maxTraceDepth >= 20: per-path generator state) keep every bounce exact and run
  *                          only the next-event visibility queries contracted.  tests/test_gpu_contract.py holds all of this and the primitives' bounds.
- * The environment variables FRAYHIP_PT_LANES / FRAYHIP_PT_BUDGET_MIB / FRAYHIP_SPECULATE_FANS / FRAYHIP_FP_CONTRACT preset them at frayhip_scene_create. */
+ *   "skip_null_segments" 0 / 1  path tracing, the timed kernels (frames rendered without FRAYHIP_FRAME_STATS): a next-event sample whose contribution is +0.0f in
+ *                          all three channels by bit pattern -- Reflection / Refraction::eval, a Lambert surface facing away from the sampled light point -- is not
+ *                          queued for its visibility query (default 1).  The query's answer could only choose between storing black and storing black, so the
+ *                          picture is the same bit for bit (tests/test_gpu_null_segments.py); a -0.0f or NaN channel is traced as before.  0 queues every segment.
+ *                          The counting kernels always trace every segment: shadow_rays stays the reference's count.
+ * The environment variables FRAYHIP_PT_LANES / FRAYHIP_PT_BUDGET_MIB / FRAYHIP_SPECULATE_FANS / FRAYHIP_FP_CONTRACT / FRAYHIP_SKIP_NULL_SEGMENTS preset them at
+ * frayhip_scene_create. */
 int  frayhip_scene_set_option(frayhip_scene* s, const char* name, int64_t value);
 /* Reads an option back, or one of the last frame's read-only figures: "fans_filed" (camera samples whose first fan was drawn ahead),
  * "fan_children" (rays traced ahead), "fan_children_looked_up" (results used), "fans_given_up" (fans in which a ray drew a random
  * number after all, so that the rest of the fan was traced in place), "contracted_launches" (launches of the last frame that ran a kernel of
- * the "fp_contract" build), "whitted_path" (how the last Whitted frame ran: 0 = the recursive kernel, 1 = shade / visible / gather launches, 2 = fused), "pt_budget_effective_mib" (the queue budget frames currently plan with: pt_budget_mib clamped to the device's
+ * the "fp_contract" build), "shadow_segments" (entries of the next-event queues over the launches of the last frayhip_render / frayhip_render_progressive
+ * frame: the visibility queries it actually traced), "whitted_path" (how the last Whitted frame ran: 0 = the recursive kernel, 1 = shade / visible / gather launches, 2 = fused), "pt_budget_effective_mib" (the queue budget frames currently plan with: pt_budget_mib clamped to the device's
  * free memory, halved when an allocation failed and the frame could be planned again). */
 int  frayhip_scene_get_option(frayhip_scene* s, const char* name, int64_t* value);
 
