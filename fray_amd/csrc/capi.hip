@@ -2,6 +2,7 @@
 // Stands behind render() of the reference (src/main.cpp:373-405).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstddef>
 #include <cmath>
@@ -179,7 +180,8 @@ size_t work_budget(frayhip_scene* sc)
     if (!sc->ptBudgetEff) {
         size_t freeB = 0, totalB = 0;
         size_t b = sc->ptBudgetBytes;
-        if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) b = std::min(b, (freeB + sc->work_bytes) / 5 * 4);
+        // (the seed table's memory counts as free: the workspace takes it back when it has to, ensure_work_or_shrink)
+        if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) b = std::min(b, (freeB + sc->work_bytes + sc->seedTab.bytes) / 5 * 4);
         sc->ptBudgetEff = std::max<size_t>(b, (size_t)64 << 20);
     }
     return sc->ptBudgetEff;
@@ -191,12 +193,75 @@ size_t work_budget(frayhip_scene* sc)
 // reported as FRAYHIP_E_NOMEM and the budget stays; option "pt_budget_effective_mib" reads what frames currently plan with).
 int ensure_work_or_shrink(frayhip_scene* sc, size_t bytes, bool canRetry)
 {
-    const int rc = ensure_work(sc, bytes);
+    int rc = ensure_work(sc, bytes);
     if (rc != FRAYHIP_E_NOMEM) return rc;
     (void)hipGetLastError();
+    // The seed table must never make a frame fail or shrink its batches: the workspace takes its memory back first.  A frame planned without
+    // its per-batch seed words sees seedTab.serving cleared and plans again (render_impl).
+    if (sc->seedTab.d) {
+        seed_table_free(sc);
+        sc->seedTab.noGrow = true;
+        rc = ensure_work(sc, bytes);
+        if (rc != FRAYHIP_E_NOMEM) return rc;
+        (void)hipGetLastError();
+    }
     if (!canRetry || work_budget(sc) <= ((size_t)64 << 20)) return rc;          // nothing to plan again, or already at the floor: give up with the allocation's message
     sc->ptBudgetEff = std::max<size_t>(sc->ptBudgetEff / 2, (size_t)64 << 20);
     return FRAYHIP_RETRY_SMALLER;
+}
+
+void seed_table_invalidate(frayhip_scene* sc)
+{
+    std::fill(sc->seedTab.valid.begin(), sc->seedTab.valid.end(), (unsigned char)0);
+}
+
+void seed_table_free(frayhip_scene* sc)
+{
+    SeedTable& T = sc->seedTab;
+    if (T.d) (void)hipFree(T.d);
+    T.d = nullptr;
+    T.bytes = 0;
+    T.valid.clear();
+    T.serving = false;
+}
+
+// (render_impl has cleared seedTab.serving and the last frame's figures at its head.)
+// Called at the head of a frame, when no earlier frame of this scene is in flight: every frame ends with its lanes joined into the caller's
+// stream and that stream synchronised (or, on an error, the device), so the copy and the hipFree of a growth race with nothing.
+void seed_table_begin(frayhip_scene* sc, const DFrame& F, int nItems, int spp)
+{
+    SeedTable& T = sc->seedTab;
+    if (!sc->seedTableCapBytes) { seed_table_free(sc); T.keyed = false; return; }        // option off: nothing is held
+    if (nItems <= 0 || spp <= 0) return;
+    const int32_t key[7] = {F.W, F.H, F.BW, F.BH, F.bucketFirst, F.bucketStride, F.nBuckets};
+    const size_t planeBytes = (size_t)nItems * sizeof(uint32_t);
+    if (!T.keyed || memcmp(key, T.key, sizeof key) != 0 || F.seed != T.seed || nItems != T.nItems) {
+        memcpy(T.key, key, sizeof key);
+        T.seed = F.seed; T.nItems = nItems; T.keyed = true; T.noGrow = false;
+        T.valid.assign(T.bytes / planeBytes, 0);          // the allocation is kept and cut into planes of the new size
+    }
+    const size_t need = (size_t)spp * planeBytes;
+    if (need > sc->seedTableCapBytes) return;
+    if (T.valid.size() < (size_t)spp) {
+        if (T.noGrow) return;
+        uint32_t* d = nullptr;
+        if (hipMalloc((void**)&d, need) != hipSuccess) {
+            // no room for the old and the new allocation at once: the frame renders from workspace words, and the old table, which frames of this
+            // key can no longer use whole, is given back instead of being held for nothing
+            (void)hipGetLastError();
+            seed_table_free(sc);
+            T.noGrow = true;
+            return;
+        }
+        size_t held = 0;                                  // the planes up to the last valid one move to the new allocation
+        for (size_t s = 0; s < T.valid.size(); s++) if (T.valid[s]) held = s + 1;
+        if (held && hipMemcpy(d, T.d, held * planeBytes, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipGetLastError(); std::fill(T.valid.begin(), T.valid.end(), (unsigned char)0); }
+        if (T.d) (void)hipFree(T.d);          // a device-to-device hipMemcpy may return before it is done: this hipFree synchronises the device, so the copy has completed before any stream reads the new table
+        T.d = d;
+        T.bytes = need;
+        T.valid.resize((size_t)spp, 0);
+    }
+    T.serving = true;
 }
 
 hipEvent_t pool_event(std::vector<hipEvent_t>& pool, size_t i)
@@ -831,6 +896,7 @@ int frayhip_scene_create(const frayhip_scene_desc* desc, frayhip_scene** out)
     if (const char* e = getenv("FRAYHIP_SKIP_NULL_SEGMENTS")) sc->skipNullSegments = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_FUSED_WHITTED_MAX")) { long v = atol(e); if (v >= 0 && v <= 1024) sc->fusedWhittedMax = (int)v; }
     if (const char* e = getenv("FRAYHIP_CSG_LANES")) { long v = atol(e); if (v >= 1 && v <= FRAY_PT_LANES) sc->csgLanes = (int)v; }
+    if (const char* e = getenv("FRAYHIP_SEED_TABLE_MIB")) { long v = atol(e); if (v >= 0 && v <= (1 << 20)) sc->seedTableCapBytes = (size_t)v << 20; }
     if (const char* e = getenv("FRAYHIP_PT_BUDGET_MIB")) { long v = atol(e); if (v >= 1 && v <= (1 << 20)) { sc->ptBudgetBytes = (size_t)v << 20; sc->ptBudgetEff = 0; } }
     *out = sc;
     return FRAYHIP_OK;
@@ -847,6 +913,10 @@ int frayhip_scene_get_option(frayhip_scene* s, const char* name, int64_t* value)
     else if (n == "contracted_launches") *value = s->lastContracted;
     else if (n == "skip_null_segments") *value = s->skipNullSegments ? 1 : 0;
     else if (n == "shadow_segments") *value = s->lastShadowSegments;
+    else if (n == "seed_table_mib") *value = (int64_t)(s->seedTableCapBytes >> 20);
+    else if (n == "seed_table_bytes") *value = (int64_t)s->seedTab.bytes;
+    else if (n == "seed_launches") *value = s->lastSeedLaunches;
+    else if (n == "seed_planes_reused") *value = s->lastSeedReused;
     else if (n == "whitted_path") *value = s->lastWhittedPath;
     else if (n == "fused_whitted_max") *value = s->fusedWhittedMax;
     else if (n == "pt_budget_effective_mib") *value = (int64_t)(frayhip_detail::work_budget(s) >> 20);
@@ -879,6 +949,10 @@ int frayhip_scene_set_option(frayhip_scene* s, const char* name, int64_t value)
     } else if (n == "fp_contract") {
         if (value != 0 && value != 1) { set_error("frayhip_scene_set_option: fp_contract must be 0 or 1"); return FRAYHIP_E_ARG; }
         s->fpContract = value != 0;
+    } else if (n == "seed_table_mib") {
+        if (value < 0 || value > (1 << 20)) { set_error("frayhip_scene_set_option: seed_table_mib must be 0..1048576"); return FRAYHIP_E_ARG; }
+        s->seedTableCapBytes = (size_t)value << 20;
+        if (s->seedTab.bytes > s->seedTableCapBytes) { frayhip_detail::seed_table_free(s); s->seedTab.keyed = false; }      // a table over the new cap is given back now
     } else if (n == "skip_null_segments") {
         if (value != 0 && value != 1) { set_error("frayhip_scene_set_option: skip_null_segments must be 0 or 1"); return FRAYHIP_E_ARG; }
         s->skipNullSegments = value != 0;
@@ -904,6 +978,7 @@ void frayhip_scene_destroy(frayhip_scene* s)
     if (!s) return;
     if (s->d_arena) (void)hipFree(s->d_arena);
     if (s->d_work) (void)hipFree(s->d_work);
+    frayhip_detail::seed_table_free(s);
     if (s->d_stats) (void)hipFree(s->d_stats);
     if (s->d_qmeta) (void)hipFree(s->d_qmeta);
     if (s->evA) (void)hipEventDestroy(s->evA);

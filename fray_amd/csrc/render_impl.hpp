@@ -63,6 +63,37 @@ int pt_bounces(frayhip_scene* sc, const DScene& S, const PathQueue (&Q)[2], cons
     return FRAYHIP_OK;
 }
 
+// x[397] of the seeds of batch (s0, cn) on stream ls; `out` is what the batch's kernels index with s * nItems + item, s relative to the batch.
+// Without the seed table (render_state.hpp SeedTable): one k_seed launch into the batch's own words, `scratch`.  With it: the batch's slice of
+// the table, and k_seed only for its maximal runs of planes the table does not hold -- none at all when an earlier frame left them there.
+// A valid plane is never written again.
+inline int seed_batch(frayhip_scene* sc, const DFrame& F, int nItems, int s0, int cn, uint32_t* scratch, hipStream_t ls, const uint32_t*& out)
+{
+    auto launch = [&](int a, int n, uint32_t* to) {
+        hipLaunchKernelGGL(k_seed, dim3(seed_grid(((size_t)nItems * n + FRAY_SEED_CHAINS - 1) / FRAY_SEED_CHAINS)), dim3(256), 0, ls, F, nItems, a, n, to);
+        sc->lastSeedLaunches++;
+    };
+    SeedTable& T = sc->seedTab;
+    if (!T.serving) { launch(s0, cn, scratch); out = scratch; return FRAYHIP_OK; }
+    for (int a = s0; a < s0 + cn;) {
+        if (T.valid[a]) { sc->lastSeedReused++; a++; continue; }
+        int n = 1;
+        while (a + n < s0 + cn && !T.valid[a + n]) n++;
+        launch(a, n, T.d + (size_t)a * nItems);
+        HIP_TRY(hipGetLastError());
+        // Valid from here on, for this frame's batch and for every later frame.  Within the frame only this batch reads these planes, on this stream,
+        // after the launch.  A later frame may read them on another stream: every frame joins its lanes into the caller's stream -- each lane's
+        // resolve is chained through evResolved, the caller's stream waits on the last one, the Whitted paths run on that stream alone, and a
+        // cancelled progressive frame still resolves every batch it traced -- and render_impl synchronises that stream before it returns, so
+        // the launch has completed before the next frame is enqueued, whatever stream that frame is given.  An early error return drains the
+        // device and invalidates the table (Drain, below).
+        std::fill(T.valid.begin() + a, T.valid.begin() + a + n, (unsigned char)1);
+        a += n;
+    }
+    out = T.d + (size_t)s0 * nItems;
+    return FRAYHIP_OK;
+}
+
 // The batch loop of every integrator that renders a frame in batches of `chunk` samples per pixel.  trace(j) enqueues batch j up to its resolve,
 // resolve(j) the resolve (the ordered per-pixel sum) and whatever belongs after it; both return 0 or an error code.  laneOf(j) is the stream
 // batch j runs on; evOrder (the path tracer's evResolved, one per lane) is recorded after every resolve.
@@ -176,7 +207,9 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
 
     // An early (error) return below must not leave work in flight on the side lanes' streams, which the caller cannot see: whatever
     // was enqueued is drained before the call returns.
-    struct Drain { bool armed = true; ~Drain() { if (armed) (void)hipDeviceSynchronize(); } } drain;
+    struct Drain { frayhip_scene* sc; bool armed = true; ~Drain() { if (armed) { (void)hipDeviceSynchronize(); seed_table_invalidate(sc); } } } drain{sc};
+    sc->seedTab.serving = false;
+    sc->lastSeedLaunches = sc->lastSeedReused = 0;
     HIP_TRY(hipMemsetAsync(sc->d_stats, 0, kStatsBytes, stream));
     DCursors* cursors = (DCursors*)((unsigned char*)sc->d_stats + kCursorOffset);
     HIP_TRY(hipEventRecord(sc->evA, stream));
@@ -210,7 +243,9 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 // Not in the counting variants (their counters are the reference's call counts), not in stereo frames (the right eye continues the left eye's generator).
                 int fan = (!(ST & 1) && sc->speculateFans && !(sc->camera.stereoSeparation > 0)) ? sc->specFanMax : 0;
                 int chunk = 0;
+                seed_table_begin(sc, F, nItems, spp);
                 for (;;) {          // planned again with half the budget when the allocation fails (ensure_work_or_shrink)
+                    const bool tabled = sc->seedTab.serving;          // the batches' x397 words are the table's, not the workspace's
                     const size_t wb = work_budget(sc);
                     const size_t budget = wb > colBytes + (64u << 20) ? wb - colBytes : (64u << 20);
                     // a fan so large that one sample per pixel of it does not fit the budget (or 2^31 children) is not traced ahead
@@ -221,10 +256,11 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                     while (chunk > 1 && (size_t)nItems * chunk * (size_t)std::max(fan, 1) >= ((size_t)1 << 31)) chunk /= 2;
                     const size_t slots = (size_t)nItems * chunk, kids = slots * (size_t)fan;
                     const bool canRetry = f->spp_chunk <= 0 && chunk > 1;
-                    const int rc = ensure_work_or_shrink(sc, colBytes + r256((size_t)nItems * 12) + r256(slots * 12) + r256(slots * 4) +
+                    const int rc = ensure_work_or_shrink(sc, colBytes + r256((size_t)nItems * 12) + r256(slots * 12) + (tabled ? 0 : r256(slots * 4)) +
                                                              (fan > 0 ? 256 + 2 * r256(slots * 4) + 3 * r256(slots * 8) + r256(kids * 4) + 3 * r256(kids * 8) + 3 * r256(kids * 4) + 2 * r256(kids) : 0), canRetry);
                     if (rc == FRAYHIP_RETRY_SMALLER) continue;
                     if (rc) return rc;
+                    if (tabled && !sc->seedTab.serving) continue;          // the workspace took the table's memory: plan again with the per-batch seed words
                     break;
                 }
                 unsigned char* p = (unsigned char*)sc->d_work;
@@ -232,7 +268,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 uint32_t* mtWork = (uint32_t*)take(colBytes);
                 float* sum = (float*)take((size_t)nItems * 12);
                 float* rad = (float*)take((size_t)nItems * chunk * 12);
-                uint32_t* x397 = (uint32_t*)take((size_t)nItems * chunk * 4);
+                uint32_t* seedWords = sc->seedTab.serving ? nullptr : (uint32_t*)take((size_t)nItems * chunk * 4);
                 SpecBuf SPB{};
                 if (fan > 0) {
                     const size_t slots = (size_t)nItems * chunk, kids = slots * (size_t)fan;
@@ -250,7 +286,8 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                     const int s0 = j * chunk, cn = std::min(chunk, spp - s0);
                     if (s0 > 0) HIP_TRY(hipMemsetAsync(cursors, 0, 3 * sizeof(DCursors), stream));  // the tile cursors of the previous batch
                     if (fan > 0) HIP_TRY(hipMemsetAsync(SPB.counters, 0, s0 == 0 ? 256 : 32, stream));
-                    hipLaunchKernelGGL(k_seed, dim3(seed_grid(((size_t)nItems * cn + FRAY_SEED_CHAINS - 1) / FRAY_SEED_CHAINS)), dim3(256), 0, stream, F, nItems, s0, cn, x397);
+                    const uint32_t* x397 = nullptr;
+                    if (const int rc = seed_batch(sc, F, nItems, s0, cn, seedWords, stream, x397)) return rc;
                     hipEvent_t a = pool_event(sc->evPool, nTraceEvents), b = pool_event(sc->evPool, nTraceEvents + 1);
                     if (!a || !b) return FRAYHIP_E_NOMEM;
                     HIP_TRY(hipEventRecord(a, stream));
@@ -304,7 +341,15 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 const size_t perSlot = eyes * (49 + (size_t)T * 37) + 4;
                 int chunk = 0;
                 size_t slots = 0, N = 0, NT = 0;
+                // Few light samples per hit (zaphod, forest: one point light): the fused form of k_wh_shade asks visible() in place -- one launch instead of
+                // shade + visible + gather; no k_seed when no generator can be asked for a word; no resolve when the kernel writes the pixel itself.
+                // (not beside KD meshes: there the fused kernel spills 165 registers and the lean any-hit kernel wins -- forest DOF 256 162.4 against 168.2 ms fused)
+                const bool fusedShade = T <= sc->fusedWhittedMax && !kd_variant(ST);
+                const bool draws = F.jitter || sc->camera.dof || sc->lightDraws;
+                const bool seeds = !fusedShade || draws;          // the frame launches k_seed at all
+                if (seeds) seed_table_begin(sc, F, nItems, spp);
                 for (;;) {          // planned again with half the budget when the allocation fails (ensure_work_or_shrink)
+                    const bool tabled = sc->seedTab.serving;          // the batches' x397 words are the table's, not the workspace's
                     const size_t wb = work_budget(sc);
                     const size_t budget = wb > colBytes + (64u << 20) ? wb - colBytes : (64u << 20);
                     chunk = f->spp_chunk > 0 ? f->spp_chunk : (int)std::max<size_t>(1, budget / ((size_t)nItems * perSlot));
@@ -312,10 +357,11 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                     while (chunk > 1 && (size_t)nItems * chunk * eyes * (size_t)std::max(T, 1) > ((size_t)1 << 31)) chunk /= 2;
                     slots = (size_t)nItems * chunk; N = slots * eyes; NT = N * (size_t)T;
                     const size_t bytes = colBytes + r256((size_t)nItems * 12) + r256(N * 12) + 3 * r256(N * 8) + r256(N) + 3 * r256(NT * 8) + 3 * r256(NT * 4) + r256(NT) +
-                                         2 * r256(slots * 12) + r256(slots * 4) + 4096;
+                                         2 * r256(slots * 12) + (tabled ? 0 : r256(slots * 4)) + 4096;
                     const int rc = ensure_work_or_shrink(sc, bytes, f->spp_chunk <= 0 && chunk > 1);
                     if (rc == FRAYHIP_RETRY_SMALLER) continue;
                     if (rc) return rc;
+                    if (tabled && !sc->seedTab.serving) continue;          // the workspace took the table's memory: plan again with the per-batch seed words
                     break;
                 }
                 unsigned char* p = (unsigned char*)sc->d_work;
@@ -331,19 +377,14 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 Q.vis = take(NT);
                 float* radL = (float*)take(slots * 12);
                 float* radR = (float*)take(slots * 12);
-                uint32_t* x397 = (uint32_t*)take(slots * 4);
-                // Few light samples per hit (zaphod, forest: one point light): the fused form of k_wh_shade asks visible() in place -- one launch instead of
-                // shade + visible + gather; no k_seed when no generator can be asked for a word; no resolve when the kernel writes the pixel itself.
-                // (not beside KD meshes: there the fused kernel spills 165 registers and the lean any-hit kernel wins -- forest DOF 256 162.4 against 168.2 ms fused)
-                const bool fusedShade = T <= sc->fusedWhittedMax && !kd_variant(ST);
+                uint32_t* seedWords = sc->seedTab.serving ? nullptr : (uint32_t*)take(slots * 4);
                 sc->lastWhittedPath = fusedShade ? 2 : 1;
-                const bool draws = F.jitter || sc->camera.dof || sc->lightDraws;
                 const bool direct = fusedShade && spp == 1 && !stereo;      // the fused kernel writes the pixel itself
                 auto trace = [&](int j) -> int {
                     const int s0 = j * chunk, cn = std::min(chunk, spp - s0);
                     const size_t bs = (size_t)nItems * cn, bN = bs * eyes;      // this batch's slots: arrays are used with stride bN
-                    if (!fusedShade || draws)
-                        hipLaunchKernelGGL(k_seed, dim3(seed_grid((bs + FRAY_SEED_CHAINS - 1) / FRAY_SEED_CHAINS)), dim3(256), 0, stream, F, nItems, s0, cn, x397);
+                    const uint32_t* x397 = nullptr;          // stays null when no generator can be asked for a word: no launch, and no plane of the table is touched
+                    if (seeds) { if (const int rc = seed_batch(sc, F, nItems, s0, cn, seedWords, stream, x397)) return rc; }
                     hipEvent_t ea = pool_event(sc->evPool, nTraceEvents), eb = pool_event(sc->evPool, nTraceEvents + 1);
                     hipEvent_t ec = pool_event(sc->evPoolShadow, nShadowEvents), ed = pool_event(sc->evPoolShadow, nShadowEvents + 1);
                     if (!ea || !eb || !ec || !ed) return FRAYHIP_E_NOMEM;
@@ -353,7 +394,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                     const bool claimShade = bs / 64 >= (size_t)grid * 4 * 16;
                     if (fusedShade) {
                         hipLaunchKernelGGL((k_wh_shade<ST, true>), dim3(grid), dim3(256), 0, stream,
-                                           WhShadeArgs{S, C, F, nItems, s0, cn, Q, mtWork, draws ? x397 : nullptr, sc->d_stats, claimShade ? cursors : nullptr, radL, radR, direct ? d_rgb : nullptr});
+                                           WhShadeArgs{S, C, F, nItems, s0, cn, Q, mtWork, x397, sc->d_stats, claimShade ? cursors : nullptr, radL, radR, direct ? d_rgb : nullptr});
                         HIP_TRY(hipEventRecord(eb, stream));
                         nTraceEvents += 2;
                         return FRAYHIP_OK;
@@ -433,7 +474,9 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
             const bool stereo = sc->camera.stereoSeparation > 0;
             int chunk = 0, nBatches = 0, nLanes = 0;
             size_t nPaths = 0, nQueue = 0, laneBytes = 0;
+            seed_table_begin(sc, F, nItems, spp);
             for (;;) {              // planned again with half the budget when the allocation fails (ensure_work_or_shrink)
+                const bool tabled = sc->seedTab.serving;          // the lanes' x397 words are the table's, not the workspace's
                 const size_t budget = std::max<size_t>(work_budget(sc) / perPath, 1);       // paths in flight over all lanes
                 chunk = f->spp_chunk > 0 ? f->spp_chunk : (int)std::max<size_t>(1, budget / maxLanes / (size_t)nItems);
                 if (chunk > spp) chunk = spp;
@@ -444,11 +487,12 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 nPaths = (size_t)nItems * chunk;
                 // per-wave segments round their share up to a multiple of 64: one extra wave-load per wave of the grid
                 nQueue = nPaths + (size_t)bounce_grid(nPaths, (ST & 2) != 0 && maxLanes == 1) * 4 * 128;
-                laneBytes = 2 * queue_bytes(nQueue) + shadow_bytes(nQueue) + nPaths * 12 + nPaths * 4 + 4096 + nPaths * termBytes + 512 + (longRng ? nPaths * 2 * 624 * sizeof(uint32_t) + 256 : 0) +
+                laneBytes = 2 * queue_bytes(nQueue) + shadow_bytes(nQueue) + nPaths * 12 + (tabled ? 0 : nPaths * 4) + 4096 + nPaths * termBytes + 512 + (longRng ? nPaths * 2 * 624 * sizeof(uint32_t) + 256 : 0) +
                             (stereo ? nPaths * (12 + 6 * 8 + 6 * 4) + 16 * 256 : 0);
                 const int rc = ensure_work_or_shrink(sc, (size_t)nLanes * laneBytes + (size_t)nItems * 12 + 4096, f->spp_chunk <= 0 && (chunk > 1 || nLanes > 1));
                 if (rc == FRAYHIP_RETRY_SMALLER) { if (chunk == 1 && maxLanes > 1) maxLanes--; continue; }
                 if (rc) return rc;
+                if (tabled && !sc->seedTab.serving) continue;          // the workspace took the table's memory: plan again with the per-batch seed words
                 break;
             }
             struct Lane {
@@ -456,7 +500,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 PathQueue Q[2];
                 ShadowQueue SQ;
                 float *sampleRad, *sampleRadR;
-                uint32_t* x397;
+                uint32_t* seedWords;      // the batch's own x397 words; nullptr when the seed table serves the frame
                 uint32_t* mtCols;
                 float* terms;
                 unsigned short* termCount;
@@ -475,7 +519,8 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 p = carve_queue(p, nQueue, L.Q[1]);
                 p = carve_shadow(p, nQueue, L.SQ);
                 L.sampleRad = (float*)p; p += (nPaths * 12 + 255) / 256 * 256;
-                L.x397 = (uint32_t*)p; p += (nPaths * 4 + 255) / 256 * 256;
+                L.seedWords = nullptr;
+                if (!sc->seedTab.serving) { L.seedWords = (uint32_t*)p; p += (nPaths * 4 + 255) / 256 * 256; }
                 L.terms = (float*)p; p += (nPaths * (size_t)(set.maxTraceDepth + 2) * 12 + 255) / 256 * 256;
                 L.termCount = (unsigned short*)p; p += (nPaths * 2 + 255) / 256 * 256;
                 L.mtCols = nullptr;
@@ -496,7 +541,8 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 const int s0 = batch * chunk, cn = std::min(chunk, spp - s0);
                 Lane& L = lane[batch % nLanes];
                 hipStream_t ls = L.stream;
-                hipLaunchKernelGGL(k_seed, dim3(seed_grid(((size_t)nItems * cn + FRAY_SEED_CHAINS - 1) / FRAY_SEED_CHAINS)), dim3(256), 0, ls, F, nItems, s0, cn, L.x397);
+                const uint32_t* x397 = nullptr;
+                if (const int rc = seed_batch(sc, F, nItems, s0, cn, L.seedWords, ls, x397)) return rc;
                 for (int eye = 0; eye < (stereo ? 2 : 1); eye++) {
                     // A mono frame with register generators makes its camera rays inside the first bounce (k_pt_bounce<.., FIRST>); a stereo frame (the
                     // right eye continues the left eye's streams) and long generators start from a dense queue written by k_pt_init
@@ -508,7 +554,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                         // queue 0 is dense: one segment holding every slot of the batch
                         hipLaunchKernelGGL(k_meta_dense, dim3(1), dim3(64), 0, ls, L.meta, (uint32_t)((size_t)nItems * cn));
                         hipLaunchKernelGGL(k_pt_init<ST>, dim3(grid_for((size_t)nItems * cn)), dim3(256), 0, ls, S, C, F, nItems, s0, cn, L.Q[0],
-                                           L.termCount, L.x397, L.SB, eye, sc->d_stats);
+                                           L.termCount, x397, L.SB, eye, sc->d_stats);
                     }
                     for (int b = 0; b < nBounce; b++) {
                         const QMetaRO mIn{(const FRAY_RO QMeta*)(L.meta + (b & 1))}, mSh{(const FRAY_RO QMeta*)(L.meta + 2)};
@@ -519,7 +565,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                         HIP_TRY(hipEventRecord(ea, ls));
                         const LongRng LR{L.mtCols, (uint32_t)nPaths, F, nItems, s0};
                         const TermBuf TB{L.terms, L.termCount, (uint32_t)nPaths, b};
-                        const FirstArgs FA{C, F, nItems, s0, (uint32_t)((size_t)nItems * cn), L.x397, L.termCount};
+                        const FirstArgs FA{C, F, nItems, s0, (uint32_t)((size_t)nItems * cn), x397, L.termCount};
                         const BounceArgs BA{S, L.Q[b & 1], L.Q[(b + 1) & 1], L.SQ, mIn, L.meta + ((b + 1) & 1), L.meta + 2, TB, save, LR, sc->d_stats, FA};
                         // option "fp_contract": bounces after a sample's first closest hit (and every visibility query) are colour, bounded by RMS and not by
                         // bits -- they run the kernels compiled with fused multiply-adds (render_contract.hip; not built for the Cube / CSG variants, which

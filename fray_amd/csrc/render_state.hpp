@@ -36,9 +36,27 @@ inline int hip_error_code(hipError_t e)
 #ifndef FRAY_PT_BUDGET_MIB
 #define FRAY_PT_BUDGET_MIB 24576   // default workspace budget of a path-traced / wavefront-Whitted frame (frayhip_scene_set_option "pt_budget_mib"): the headline frame then runs 8 batches of 8 spp on 4 lanes (338 B per path in flight)
 #endif
+#ifndef FRAY_SEED_TABLE_MIB
+#define FRAY_SEED_TABLE_MIB 4096   // default cap of the seed table (frayhip_scene_set_option "seed_table_mib"): holds 1080p x 256 spp (2070 MiB: planes are whole 48 x 48 buckets)
+#endif
 #ifndef FRAY_PT_LANES
 #define FRAY_PT_LANES 4   // headline frame / smallpt 64 spp, ms: 1 lane 150.0 / 136.3, 2 -> 136.9 / 126.5, 3 -> 135.8 / 125.1, 4 -> 135.8 / 123.8, 6 -> 135.2 / 123.9
 #endif
+
+// The x[397] seed table of a scene handle ("The seed table"): k_seed's words of every camera sample of a frame, kept across frames.
+// Plane-major and unpadded, d[(size_t)s * nItems + item] for the absolute sample index s, so a batch (s0, cn) is the slice at d + (size_t)s0 * nItems
+// in the layout the kernels index.  The key is what item_pixel and sample_seed read of DFrame; a plane is valid once its k_seed launch was enqueued.
+struct SeedTable {
+    uint32_t* d = nullptr;
+    size_t bytes = 0;                 // allocated
+    bool keyed = false;
+    int32_t key[7] = {};              // W, H, BW, BH, bucketFirst, bucketStride, nBuckets
+    uint32_t seed = 0;
+    int nItems = 0;
+    std::vector<unsigned char> valid; // per plane the allocation has room for under this key
+    bool noGrow = false;              // an allocation for this key failed, or the workspace needed the memory: no further attempt until the key changes
+    bool serving = false;             // the frame being rendered takes its seeds from the table
+};
 
 struct frayhip_scene {
     void* d_arena = nullptr;
@@ -80,6 +98,10 @@ struct frayhip_scene {
     // allocation fails all the same -- never re-derived per frame (other processes' allocations would move the batch size, and every growth of the
     // workspace is a hipFree + hipMalloc in the middle of a run).  0 = not computed yet.
     size_t ptBudgetEff = 0;
+    // option "seed_table_mib": the cap of the seed table, 0 = off (every batch seeds into its own scratch words, as before the table)
+    size_t seedTableCapBytes = (size_t)FRAY_SEED_TABLE_MIB << 20;
+    SeedTable seedTab;
+    long long lastSeedLaunches = 0, lastSeedReused = 0;   // the last frame's k_seed launches and planes taken from the table (get_option "seed_launches", "seed_planes_reused")
     bool rendering = false;           // a frame of this scene is being rendered: set by every render entry, so that a progress callback cannot render or change it
 };
 
@@ -101,6 +123,11 @@ int bounce_grid(size_t n, bool alone);
 int grid_for(size_t n);
 int seed_grid(size_t n);
 int ensure_work(frayhip_scene* sc, size_t bytes);
+// The seed table at the head of a frame of `spp` sample planes of `nItems` words: compares the key (a change invalidates every plane), grows the
+// allocation, and sets seedTab.serving; a frame the table cannot serve (option off, over the cap, allocation failed) renders as without it.
+void seed_table_begin(frayhip_scene* sc, const DFrame& F, int nItems, int spp);
+void seed_table_invalidate(frayhip_scene* sc);
+void seed_table_free(frayhip_scene* sc);
 
 // A progressive frame's request (frayhip_render_progressive / frayhip_render_device_progressive): the caller's callback and preview interval;
 // h_rgb is the host frame the host entry copies every preview (and the final frame) to before it calls back, nullptr for the device entry.

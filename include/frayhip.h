@@ -306,15 +306,27 @@ int  frayhip_scene_set_view(frayhip_scene* s, const frayhip_camera* camera, cons
  *                          queued for its visibility query (default 1).  The query's answer could only choose between storing black and storing black, so the
  *                          picture is the same bit for bit (tests/test_gpu_null_segments.py); a -0.0f or NaN channel is traced as before.  0 queues every segment.
  *                          The counting kernels always trace every segment: shadow_rays stays the reference's count.
- * The environment variables FRAYHIP_PT_LANES / FRAYHIP_PT_BUDGET_MIB / FRAYHIP_SPECULATE_FANS / FRAYHIP_FP_CONTRACT / FRAYHIP_SKIP_NULL_SEGMENTS preset them at
- * frayhip_scene_create. */
+ *   "seed_table_mib" 0..1048576  the cap, in MiB, of the scene's seed table (default 4096).  Every camera sample's generator starts from x[397] of the
+ *                          mt19937 seeding recurrence of sample_seed(seed, pixel, sample) -- a word that depends on the contract seed, the frame size and the
+ *                          bucket share and on nothing else, and that costs a 397-step chain (k_seed) per sample.  The table keeps these words, 4 bytes per
+ *                          camera sample (1080p x 64 spp: 518 MiB), from one frayhip_render* frame of the scene to the next: a frame with the same seed, size
+ *                          and bucket share launches k_seed only for sample planes the table does not hold yet -- none at all when it repeats the last
+ *                          frame's, whatever changed in the camera, the view settings, spp_chunk, pt_lanes or fp_contract; a frame asking for more samples
+ *                          seeds the new planes only.  A change of seed, size or bucket share refills the table (the same k_seed work as without it, written
+ *                          to another address: frames rendered with seed + k, as a denoised sequence is, gain nothing and lose nothing but the memory).
+ *                          The picture is the same bit for bit (tests/test_gpu_seed_table.py).  A frame whose table would pass the cap, or whose allocation
+ *                          fails, renders as without the table; the workspace takes the table's memory back before it plans smaller batches.
+ *                          0 = off: nothing is held, every batch seeds its own words.  Radiance queries, adaptive and feature frames do not use the table.
+ * The environment variables FRAYHIP_PT_LANES / FRAYHIP_PT_BUDGET_MIB / FRAYHIP_SPECULATE_FANS / FRAYHIP_FP_CONTRACT / FRAYHIP_SKIP_NULL_SEGMENTS /
+ * FRAYHIP_SEED_TABLE_MIB preset them at frayhip_scene_create. */
 int  frayhip_scene_set_option(frayhip_scene* s, const char* name, int64_t value);
 /* Reads an option back, or one of the last frame's read-only figures: "fans_filed" (camera samples whose first fan was drawn ahead),
  * "fan_children" (rays traced ahead), "fan_children_looked_up" (results used), "fans_given_up" (fans in which a ray drew a random
  * number after all, so that the rest of the fan was traced in place), "contracted_launches" (launches of the last frame that ran a kernel of
  * the "fp_contract" build), "shadow_segments" (entries of the next-event queues over the launches of the last frayhip_render / frayhip_render_progressive
  * frame: the visibility queries it actually traced), "whitted_path" (how the last Whitted frame ran: 0 = the recursive kernel, 1 = shade / visible / gather launches, 2 = fused), "pt_budget_effective_mib" (the queue budget frames currently plan with: pt_budget_mib clamped to the device's
- * free memory, halved when an allocation failed and the frame could be planned again). */
+ * free memory, halved when an allocation failed and the frame could be planned again), "seed_table_bytes" (what the seed table currently holds on the
+ * device), "seed_launches" (k_seed launches of the last frame) and "seed_planes_reused" (sample planes the last frame took from the table). */
 int  frayhip_scene_get_option(frayhip_scene* s, const char* name, int64_t* value);
 
 /* Threads: a frayhip_scene renders one frame at a time (it owns one workspace and one set of
