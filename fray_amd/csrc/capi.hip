@@ -303,6 +303,7 @@ DScene frame_scene(const frayhip_scene* s)
     S.gi = set.gi;
     S.saturation = set.saturation;
     S.skipNullSegments = s->skipNullSegments ? 1 : 0;
+    S.segmentPlanes = s->segmentPlanes ? 1 : 0;
     return S;
 }
 
@@ -559,6 +560,10 @@ int frayhip_scene_create(const frayhip_scene_desc* desc, frayhip_scene** out)
     A.host.resize(oNodesX + nodes.size() * sizeof(DNodeX));
     size_t oGates = A.add(nullptr, 0);                  // the path tracer's scheduling hint (DGate), filled with the nodes
     A.host.resize(oGates + FRAY_MAX_GATES * sizeof(DGate));
+    size_t oSegPlanes = A.add(nullptr, 0);              // the planes shadow segments are certified against (dev_segcert.hpp), filled with the nodes
+    A.host.resize(oSegPlanes + FRAY_SEG_MAX_PLANES * sizeof(DSegPlane));
+    size_t oSegMasks = A.add(nullptr, 0);
+    A.host.resize(oSegMasks + FRAY_SEG_MAX_NODES * sizeof(uint32_t));
     std::vector<DPlane> planes(d.n_planes);
     for (int i = 0; i < d.n_planes; i++) { planes[i].limit = d.planes[i].limit; planes[i].height = d.planes[i].height; }
     size_t oPlanes = A.add(planes.data(), planes.size() * sizeof(DPlane));
@@ -739,7 +744,7 @@ int frayhip_scene_create(const frayhip_scene_desc* desc, frayhip_scene** out)
     for (int i = 0; i < d.n_nodes; i++) {
         DNode& N = nodes[i];
         DNodeX& X = nodesX[i];
-        N.tlTris = 0; N.tlCulling = 0; N.tlPtr = nullptr; N.boxMax = 0; N.gated = 0; N.padN = 0;
+        N.tlTris = 0; N.tlCulling = 0; N.tlPtr = nullptr; N.boxMax = 0; N.gated = 0; N.segNode = 0;
         for (int k = 0; k < 3; k++) N.bmin[k] = N.bmax[k] = X.bminE[k] = X.bmaxE[k] = 0;
         if (N.geomKind == FRAYHIP_GEOM_MESH && !meshes[N.geomIndex].hasKd) {
             const DMesh& M = meshes[N.geomIndex];
@@ -794,6 +799,49 @@ int frayhip_scene_create(const frayhip_scene_desc* desc, frayhip_scene** out)
             X.cM = std::max(X.cM, std::fabs(X.cc[k]) + X.ch[k]);
         }
         X.csgBox = X.cM < 1e9 ? 1 : 0;
+    }
+    // Nodes a next-event segment may skip by the planes of their triangles (dev_segcert.hpp): untransformed meshes without a KD-tree and too small for a gate,
+    // every triangle with finite, bounded coordinates and a normal that is not (nearly) zero.  Triangles whose N and fl(N . A) are equal bit for bit share a
+    // plane entry (a planar quad is one plane).  A scene that would need more entries or nodes than the tables hold gets none.
+    int nSegPlanes = 0, nSegNodes = 0;
+    {
+        DSegPlane planes[FRAY_SEG_MAX_PLANES];
+        double planeAmax[FRAY_SEG_MAX_PLANES];
+        uint32_t masks[FRAY_SEG_MAX_NODES];
+        int segNodeOf[FRAY_SEG_MAX_NODES];
+        bool fits = true;
+        for (int i = 0; i < d.n_nodes && fits; i++) {
+            const DNode& N = nodes[i];
+            if (!(N.tlTris > 0 && N.tlTris < FRAY_GATE_MIN_TRIS && N.xfIdentity)) continue;
+            const frayhip_mesh& m = d.meshes[N.geomIndex];
+            bool ok = true;
+            for (int t = 0; t < m.n_triangles && ok; t++) ok = segcert_triangle_ok(m.triangles[t].ABcrossAC, m.vertices + 3 * (size_t)m.triangles[t].v[0]);
+            if (!ok) continue;
+            if (nSegNodes == FRAY_SEG_MAX_NODES) { fits = false; break; }
+            uint32_t mask = 0;
+            for (int t = 0; t < m.n_triangles; t++) {
+                const double* TN = m.triangles[t].ABcrossAC;
+                const double* TA = m.vertices + 3 * (size_t)m.triangles[t].v[0];
+                const double k = segcert_offset(TN, TA), am = std::max(std::fabs(TA[0]), std::max(std::fabs(TA[1]), std::fabs(TA[2])));
+                int p = 0;
+                while (p < nSegPlanes && (memcmp(planes[p].N, TN, 3 * sizeof(double)) != 0 || memcmp(&planes[p].k, &k, sizeof k) != 0)) p++;
+                if (p == nSegPlanes) {
+                    if (nSegPlanes == FRAY_SEG_MAX_PLANES) { fits = false; break; }
+                    memcpy(planes[p].N, TN, 3 * sizeof(double)); planes[p].k = k; planeAmax[p] = 0;
+                    nSegPlanes++;
+                }
+                planeAmax[p] = std::max(planeAmax[p], am);
+                mask |= 1u << p;
+            }
+            if (!fits) break;
+            segNodeOf[nSegNodes] = i;
+            masks[nSegNodes++] = mask;
+        }
+        if (!fits) nSegPlanes = nSegNodes = 0;
+        for (int p = 0; p < nSegPlanes; p++) { const DSegPlane q = planes[p]; segcert_make(planes[p], q.N, q.k, planeAmax[p]); }
+        for (int j = 0; j < nSegNodes; j++) nodes[segNodeOf[j]].segNode = j + 1;
+        if (nSegPlanes) memcpy(A.host.data() + oSegPlanes, planes, (size_t)nSegPlanes * sizeof(DSegPlane));
+        if (nSegNodes) memcpy(A.host.data() + oSegMasks, masks, (size_t)nSegNodes * sizeof(uint32_t));
     }
     if (!nodes.empty()) memcpy(A.host.data() + oNodes, nodes.data(), nodes.size() * sizeof(DNode));
     if (!nodesX.empty()) memcpy(A.host.data() + oNodesX, nodesX.data(), nodesX.size() * sizeof(DNodeX));
@@ -860,6 +908,9 @@ int frayhip_scene_create(const frayhip_scene_desc* desc, frayhip_scene** out)
     S.nodesX = (const FRAY_RO DNodeX*)(base + oNodesX);
     S.gates = (const FRAY_RO DGate*)(base + oGates);
     S.nGates = nGates; S.gatesExact = gatesExact ? 1 : 0;
+    S.segPlanes = (const FRAY_RO DSegPlane*)(base + oSegPlanes);
+    S.segNodeMasks = (const FRAY_RO uint32_t*)(base + oSegMasks);
+    S.nSegPlanes = nSegPlanes; S.nSegNodes = nSegNodes;
     S.planes = (const FRAY_RO DPlane*)(base + oPlanes);
     S.spheres = (const FRAY_RO DSphere*)(base + oSpheres);
     S.cubes = (const FRAY_RO DCube*)(base + oCubes);
@@ -894,6 +945,7 @@ int frayhip_scene_create(const frayhip_scene_desc* desc, frayhip_scene** out)
     if (const char* e = getenv("FRAYHIP_SPECULATE_FANS")) sc->speculateFans = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_FP_CONTRACT")) sc->fpContract = atol(e) == 1;
     if (const char* e = getenv("FRAYHIP_SKIP_NULL_SEGMENTS")) sc->skipNullSegments = atol(e) != 0;
+    if (const char* e = getenv("FRAYHIP_SEGMENT_PLANES")) sc->segmentPlanes = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_FUSED_WHITTED_MAX")) { long v = atol(e); if (v >= 0 && v <= 1024) sc->fusedWhittedMax = (int)v; }
     if (const char* e = getenv("FRAYHIP_CSG_LANES")) { long v = atol(e); if (v >= 1 && v <= FRAY_PT_LANES) sc->csgLanes = (int)v; }
     if (const char* e = getenv("FRAYHIP_SEED_TABLE_MIB")) { long v = atol(e); if (v >= 0 && v <= (1 << 20)) sc->seedTableCapBytes = (size_t)v << 20; }
@@ -913,6 +965,9 @@ int frayhip_scene_get_option(frayhip_scene* s, const char* name, int64_t* value)
     else if (n == "contracted_launches") *value = s->lastContracted;
     else if (n == "skip_null_segments") *value = s->skipNullSegments ? 1 : 0;
     else if (n == "shadow_segments") *value = s->lastShadowSegments;
+    else if (n == "segment_planes") *value = s->segmentPlanes ? 1 : 0;
+    else if (n == "segment_plane_nodes") *value = s->S.nSegNodes;
+    else if (n == "shadow_nodes_skipped") *value = s->lastShadowNodesSkipped;
     else if (n == "seed_table_mib") *value = (int64_t)(s->seedTableCapBytes >> 20);
     else if (n == "seed_table_bytes") *value = (int64_t)s->seedTab.bytes;
     else if (n == "seed_launches") *value = s->lastSeedLaunches;
@@ -956,6 +1011,9 @@ int frayhip_scene_set_option(frayhip_scene* s, const char* name, int64_t value)
     } else if (n == "skip_null_segments") {
         if (value != 0 && value != 1) { set_error("frayhip_scene_set_option: skip_null_segments must be 0 or 1"); return FRAYHIP_E_ARG; }
         s->skipNullSegments = value != 0;
+    } else if (n == "segment_planes") {
+        if (value != 0 && value != 1) { set_error("frayhip_scene_set_option: segment_planes must be 0 or 1"); return FRAYHIP_E_ARG; }
+        s->segmentPlanes = value != 0;
     } else {
         set_error("frayhip_scene_set_option: unknown option " + n);
         return FRAYHIP_E_ARG;

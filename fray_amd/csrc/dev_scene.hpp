@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include "frayhip.h"      // FRAYHIP_BUCKET_SKEW: the bucket numbering is part of the C ABI
 #include "dev_tricert.hpp"  // DTri32
+#include "dev_segcert.hpp"  // DSegPlane
 
 // Scene tables are read-only for the whole frame.  On the device their pointers are typed into the
 // constant address space (4): loads through them are known not to alias the kernels' stores, so a
@@ -54,7 +55,8 @@ struct DNode {
     double bmin[3], bmax[3];
     const FRAY_RO DTri* tlPtr;
     double boxMax;        // max |coordinate| of bmin / bmax (margins of the certified box test, dev_boxcert.hpp)
-    int32_t gated, padN;  // this node's geometry lies inside an EXACT gate (DGate::exact): a ray its producer certified to miss every gate skips the node
+    int32_t gated;        // this node's geometry lies inside an EXACT gate (DGate::exact): a ray its producer certified to miss every gate skips the node
+    int32_t segNode;      // 1 + the node's index in DScene::segNodeMasks when a shadow segment may skip it by its triangles' planes (dev_segcert.hpp), else 0
 };                        // 272 B
 // What only the box test of the scenes WITHOUT KD meshes reads (DScene::nodesX): the node's box widened by inside()'s tolerance
 struct DNodeX {
@@ -194,6 +196,12 @@ struct DScene {
     float ambient[3];
     int32_t maxTraceDepth, gi;
     float saturation;
+    // Planes of the nodes a next-event segment may skip (dev_segcert.hpp; capi.hip decides eligibility): the table, and per eligible node the set of
+    // entries its triangles lie in, one bit per entry.  nSegNodes = 0: the scene has no such node (or too many planes).
+    const FRAY_RO DSegPlane* segPlanes;
+    const FRAY_RO uint32_t* segNodeMasks;
+    int32_t nSegPlanes, nSegNodes;
+    int32_t segmentPlanes;         // option "segment_planes": k_pt_shadow's timed variants for untransformed scenes skip, per wave, the nodes whose planes no live segment crosses
     int32_t skipNullSegments;      // option "skip_null_segments": the timed path-tracing kernels do not queue a next-event segment whose contribution is +0 in all three channels (dev_shade.hpp nee_prepare)
 };
 

@@ -23,6 +23,7 @@
 #define FRAY_CERT_SEQ() __builtin_amdgcn_sched_barrier(0)
 #include "dev_boxcert.hpp"
 #include "dev_misscert.hpp"
+#include "dev_segcert.hpp"
 
 #ifdef FRAY_LEAFSTAT
 static __device__ unsigned long long g_leafStat[4];      // diagnostic build only, read back by render_impl (FRAY_LEAFSTAT)
@@ -1083,8 +1084,33 @@ FD void closest_hit(const DScene& S, V3 o, V3 d, HitT<ST>& best, Cnt& c, bool ga
 // lies closer than b ends the loop.
 // GATES: compiled with the test for gate-free rays (the shadow kernel takes this copy only for queues whose producer certified them: for a scene without
 // exact gates the per-node test -- a divergent branch on a lane flag -- cost its shadow kernel 9 %: smallpt, 1.30 -> 1.43 ms per launch).
-template <int ST, bool GATES = false>
-FD bool visible(const DScene& S, V3 a, V3 b, Cnt& c, bool gateFree = false)
+// The segment-plane shortcut of k_pt_shadow's timed variants for untransformed scenes (dev_segcert.hpp).  Called by the WHOLE wave before visible(): each lane
+// evaluates the certificate for the scene's plane entries; an entry counts when every live lane passes it (a dead lane passes), and a node whose entries all
+// count is one the reference's arithmetic could not make report anything nearer than b for any of the wave's segments.  Returns those nodes, bit j for the
+// node with segNode == j + 1: a wave-uniform word, computed in wave-uniform control flow, so that it and everything derived from it stay in scalar registers.
+FD uint32_t segment_skip_nodes(const DScene& S, V3 a, V3 b, bool live)
+{
+    const int nP = S.segmentPlanes ? S.nSegPlanes : 0;
+    if (nP <= 0) return 0u;
+    const V3 e = b - a;                 // (visible()'s own first step)
+    const double m = seg_cert_scale(a.x, a.y, a.z, b.x, b.y, b.z, e.x, e.y, e.z);
+    const lanes_t all = lanes(true);
+    uint32_t certified = 0;
+    for (int p = 0; p < nP; p++) {
+        const FRAY_RO DSegPlane& P = S.segPlanes[p];
+        if (lanes(!live || seg_same_side(P.N[0], P.N[1], P.N[2], P.k, P.t0, P.t1, m, a.x, a.y, a.z, b.x, b.y, b.z)) == all) certified |= 1u << p;
+    }
+    uint32_t skipNodes = 0;
+    const int nS = S.nSegNodes;
+    for (int j = 0; j < nS; j++)
+        if ((S.segNodeMasks[j] & ~certified) == 0u) skipNodes |= 1u << j;
+    return skipNodes;
+}
+
+// SEGP: compiled with the test for the nodes in `skipNodes` (segment_skip_nodes above; k_pt_shadow only -- every other kernel's visible() is the code it was
+// without it).  The nodes not skipped run what they always ran.
+template <int ST, bool GATES = false, bool SEGP = false>
+FD bool visible(const DScene& S, V3 a, V3 b, Cnt& c, bool gateFree = false, uint32_t skipNodes = 0u)
 {
     bump<ST>(c.shadow);
     V3 d = b - a;
@@ -1101,6 +1127,7 @@ FD bool visible(const DScene& S, V3 a, V3 b, Cnt& c, bool gateFree = false)
         int tri;
         LeafOut lo;
         if constexpr (GATES && !(ST & 1)) { if (S.nodes[i].gated) { if (gateFree) continue; } }
+        if constexpr (SEGP) { const int sn = S.nodes[i].segNode; if (sn && ((skipNodes >> (sn - 1)) & 1u)) continue; }      // (wave-uniform: a scalar branch)
         if (node_intersect<ST>(S, i, a, d, lr, dist, t, tri, l2, l3, nullptr, (ST & 2) ? &lo : nullptr, c) && dist < maxDist) return false;
     }
     return true;

@@ -1359,7 +1359,8 @@ static __global__ __launch_bounds__(256, waves_for(ST, kd_variant(ST) ? FRAY_BOU
 
 // visible() for every queued next-event segment (main.cpp:64-80, 143-144): the sample's term of this bounce is the
 // segment's radiance if it is unobstructed, black otherwise.
-struct ShadowArgs { DScene S; ShadowQueue SQ; QMetaRO meta; TermBuf TB; DStats* st; };
+// segSkipped (may be null): the batch lane's count of nodes skipped by the segment-plane certificate (render_state.hpp kSegSkippedOffset), one atomic per wave
+struct ShadowArgs { DScene S; ShadowQueue SQ; QMetaRO meta; TermBuf TB; DStats* st; unsigned long long* segSkipped; };
 template <int ST, int ARITH = FRAY_ARITH>
 static __global__ __launch_bounds__(256, anyhit_waves(ST)) void k_pt_shadow(ShadowArgs A)
 {
@@ -1378,6 +1379,8 @@ static __global__ __launch_bounds__(256, anyhit_waves(ST)) void k_pt_shadow(Shad
     stamp_begin();
 #endif
     constexpr bool SORT = FRAY_SORT && sort_variant(ST);
+    constexpr bool SEGP = identity_variant(ST) && !(ST & 1);                // the segment-plane shortcut (dev_trace.hpp visible): the counting variants ask every node
+    uint32_t segSkipped = 0;                                                // (wave-uniform)
     const uint32_t sortN = (uint32_t)FRAY_SORT_N;
     for (uint32_t b0 = ws.begin, b1 = 0; b0 < ws.end; b0 = b1) {            // (a kernel that does not sort takes its whole share in one go)
     b1 = (SORT && ws.end - b0 > sortN) ? b0 + sortN : ws.end;
@@ -1401,6 +1404,24 @@ static __global__ __launch_bounds__(256, anyhit_waves(ST)) void k_pt_shadow(Shad
         else i = seg_map(off, nfIn, nSeg, chunkIn, base, di, live, seg);
         const bool gateFree = certFront && (i & FRAY_FRONT_BIT);
         i &= ~FRAY_FRONT_BIT;
+        if constexpr (SEGP) {
+            // The whole wave evaluates the certificate, in wave-uniform control flow: the nodes to skip and their count stay in scalar registers.  (The
+            // rest is the other branch's code once more: any sharing of it moved the registers of the variants that do not take this branch.)
+            V3 a = v3(0, 0, 0), b = a;
+            if (live) { a = v3(SQ.ax[i], SQ.ay[i], SQ.az[i]); b = v3(SQ.bx[i], SQ.by[i], SQ.bz[i]); }
+            const uint32_t skipNodes = segment_skip_nodes(S, a, b, live);
+            segSkipped += (uint32_t)__builtin_popcount(skipNodes);
+            if (live) {
+                STAMP(0);
+                const bool vis = certFront ? visible<ST, true, true>(S, a, b, c, gateFree, skipNodes) : visible<ST, false, true>(S, a, b, c, false, skipNodes);       // (wave-uniform choice)
+                const uint32_t sl = SQ.slot[i];
+#ifdef FRAY_QCHECK
+                if (sl >= TB.nPaths) { atomicAdd(&st->rngOverflow, 1ull); continue; }
+                SQ.slot[i] = 0xffffffffu;
+#endif
+                term_store(TB, sl, vis ? c3(SQ.cr[i], SQ.cg[i], SQ.cb[i]) : c3(0, 0, 0));
+            }
+        } else
         if (live) {
             const V3 a = v3(SQ.ax[i], SQ.ay[i], SQ.az[i]), b = v3(SQ.bx[i], SQ.by[i], SQ.bz[i]);
             STAMP(0);
@@ -1420,6 +1441,10 @@ static __global__ __launch_bounds__(256, anyhit_waves(ST)) void k_pt_shadow(Shad
 #ifdef FRAY_STAMPS
     if (lane < 24) { atomicAdd(&st->stamp[lane], g_stampAcc[threadIdx.x >> 6][lane]); atomicAdd(&st->stampLanes[lane], g_stampLanes[threadIdx.x >> 6][lane]); }
 #endif
+    if constexpr (SEGP) {
+        unsigned long long* const total = KARG(ShadowArgs, kernel_args<ShadowArgs>(), segSkipped);
+        if (total && segSkipped && lane == 0) atomicAdd(total, (unsigned long long)segSkipped);
+    }
     if (ST & 1) flush_stats(st, c);
     if ((ST & 2) && c.envelope) atomicAdd(&st->rngOverflow, 1ull);
 }

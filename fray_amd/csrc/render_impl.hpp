@@ -56,7 +56,7 @@ int pt_bounces(frayhip_scene* sc, const DScene& S, const PathQueue (&Q)[2], cons
         nTraceEvents += 2;
         hipLaunchKernelGGL(k_scan, dim3(2), dim3(1024), 0, stream, meta + ((b + 1) & 1), meta + 2, (unsigned long long*)nullptr);
         HIP_TRY(hipEventRecord(ec, stream));
-        hipLaunchKernelGGL(k_pt_shadow<ST>, dim3(grid), dim3(256), 0, stream, ShadowArgs{S, SQ, mSh, TB, sc->d_stats + 1});
+        hipLaunchKernelGGL(k_pt_shadow<ST>, dim3(grid), dim3(256), 0, stream, ShadowArgs{S, SQ, mSh, TB, sc->d_stats + 1, (unsigned long long*)((unsigned char*)sc->d_stats + kSegSkippedOffset)});
         HIP_TRY(hipEventRecord(ed, stream));
         nShadowEvents += 2;
     }
@@ -507,6 +507,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 StereoBuf SB;
                 QMeta* meta;
                 unsigned long long* segTotal;       // this lane's running total of shadow-queue entries (render_state.hpp kSegTotalsOffset)
+                unsigned long long* segSkipped;     // ... and of the nodes its shadow launches skipped by the segment-plane certificate (kSegSkippedOffset)
             } lane[FRAY_PT_LANES];
             unsigned char* p = (unsigned char*)sc->d_work;
             float* sum = (float*)p; p += ((size_t)nItems * 12 + 255) / 256 * 256;
@@ -515,6 +516,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 L.stream = k == 0 ? stream : sc->laneStream[k];
                 L.meta = sc->d_qmeta + 3 * k;
                 L.segTotal = (unsigned long long*)((unsigned char*)sc->d_stats + kSegTotalsOffset) + k;
+                L.segSkipped = (unsigned long long*)((unsigned char*)sc->d_stats + kSegSkippedOffset) + k;
                 p = carve_queue(p, nQueue, L.Q[0]);
                 p = carve_queue(p, nQueue, L.Q[1]);
                 p = carve_shadow(p, nQueue, L.SQ);
@@ -584,9 +586,9 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                         HIP_TRY(hipEventRecord(ec, ls));
                         bool contractedShadow = false;
                         if constexpr (!(ST & 2)) {
-                            if (sc->fpContract) { launch_shadow_contracted<ST>(grid, ls, ShadowArgs{S, L.SQ, mSh, TB, sc->d_stats + 1}); contractedShadow = true; nContracted++; }
+                            if (sc->fpContract) { launch_shadow_contracted<ST>(grid, ls, ShadowArgs{S, L.SQ, mSh, TB, sc->d_stats + 1, L.segSkipped}); contractedShadow = true; nContracted++; }
                         }
-                        if (!contractedShadow) hipLaunchKernelGGL(k_pt_shadow<ST>, dim3(grid), dim3(256), 0, ls, ShadowArgs{S, L.SQ, mSh, TB, sc->d_stats + 1});
+                        if (!contractedShadow) hipLaunchKernelGGL(k_pt_shadow<ST>, dim3(grid), dim3(256), 0, ls, ShadowArgs{S, L.SQ, mSh, TB, sc->d_stats + 1, L.segSkipped});
                         HIP_TRY(hipEventRecord(ed, ls));
                         nShadowEvents += 2;
                     }
@@ -621,12 +623,14 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
     HIP_TRY(hipEventRecord(sc->evB, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     drain.armed = false;                    // every lane was joined into `stream` above
-    struct Back { DStats ds[2]; unsigned long long segTotal[FRAY_PT_LANES]; } back;         // the two counter blocks and the lanes' shadow-queue totals: one copy
-    static_assert(offsetof(Back, segTotal) == kSegTotalsOffset, "the shadow-queue totals follow the counter blocks");
+    struct Back { DStats ds[2]; unsigned long long segTotal[FRAY_PT_LANES], segSkipped[FRAY_PT_LANES]; } back;         // the two counter blocks, the lanes' shadow-queue totals and skipped nodes: one copy
+    static_assert(offsetof(Back, segTotal) == kSegTotalsOffset && offsetof(Back, segSkipped) == kSegSkippedOffset, "the shadow-queue totals and the skipped nodes follow the counter blocks");
     HIP_TRY(hipMemcpy(&back, sc->d_stats, sizeof back, hipMemcpyDeviceToHost));
     const DStats (&dsv)[2] = back.ds;
     sc->lastShadowSegments = 0;
     for (int k = 0; k < FRAY_PT_LANES; k++) sc->lastShadowSegments += (long long)back.segTotal[k];
+    sc->lastShadowNodesSkipped = 0;
+    for (int k = 0; k < FRAY_PT_LANES; k++) sc->lastShadowNodesSkipped += (long long)back.segSkipped[k];
     {
         unsigned long long ft[4] = {0, 0, 0, 0};
         if (fanTotals) HIP_TRY(hipMemcpy(ft, fanTotals, sizeof ft, hipMemcpyDeviceToHost));

@@ -75,6 +75,8 @@ struct frayhip_scene {
     bool fpContract = false;          // option "fp_contract": path tracing past a sample's first closest hit on the kernels built with fused multiply-adds (render_contract.hip)
     long long lastContracted = 0;     // the last frame's launches of contracted kernels (frayhip_scene_get_option "contracted_launches")
     bool skipNullSegments = true;     // option "skip_null_segments": the timed path-tracing kernels queue no next-event segment whose contribution is +0 in every channel (dev_shade.hpp nee_prepare)
+    bool segmentPlanes = true;        // option "segment_planes": k_pt_shadow skips, per wave, the eligible nodes whose triangles' planes no live segment crosses (dev_segcert.hpp)
+    long long lastShadowNodesSkipped = 0;   // the last frame's sum over k_pt_shadow's wave iterations of the nodes skipped that way (frayhip_scene_get_option "shadow_nodes_skipped")
     long long lastShadowSegments = 0; // the last frame's shadow-queue entries over all its launches (frayhip_scene_get_option "shadow_segments"; render_impl frames)
     long long lastFans[4] = {0, 0, 0, 0};   // the last frame's fans filed, children traced ahead, children looked up, fans given up part of the way (frayhip_scene_get_option)
     int lightSampleCount = 0;         // sum over lights of Light::getNumSamples(): segments a Lambert / Phong hit queues (wavefront Whitted)
@@ -109,9 +111,11 @@ namespace frayhip_detail {
 
 // d_stats: two DStats blocks, then (256-byte aligned) the work cursors; one memset clears all of it per frame
 // ... and, in the gap before the cursors, one running total of shadow-queue entries per batch lane (k_scan adds each launch's total to its lane's word:
-// the launches of a lane are ordered by its stream, so no atomic is needed)
+// the launches of a lane are ordered by its stream, so no atomic is needed); and after those, per batch lane, the nodes k_pt_shadow's waves skipped by the
+// segment-plane certificate (one atomic per wave at the kernel's end)
 constexpr size_t kSegTotalsOffset = 2 * sizeof(DStats);
-constexpr size_t kCursorOffset = (kSegTotalsOffset + FRAY_PT_LANES * sizeof(unsigned long long) + 255) / 256 * 256;
+constexpr size_t kSegSkippedOffset = kSegTotalsOffset + FRAY_PT_LANES * sizeof(unsigned long long);
+constexpr size_t kCursorOffset = (kSegSkippedOffset + FRAY_PT_LANES * sizeof(unsigned long long) + 255) / 256 * 256;
 constexpr size_t kStatsBytes = kCursorOffset + 3 * sizeof(DCursors);     // sets of tile cursors: a batch's closest-hit and any-hit kernels; the three passes of speculative Whitted
 
 DCamera camera_begin_frame(const frayhip_camera& c, int W, int H);

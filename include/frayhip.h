@@ -306,6 +306,14 @@ int  frayhip_scene_set_view(frayhip_scene* s, const frayhip_camera* camera, cons
  *                          queued for its visibility query (default 1).  The query's answer could only choose between storing black and storing black, so the
  *                          picture is the same bit for bit (tests/test_gpu_null_segments.py); a -0.0f or NaN channel is traced as before.  0 queues every segment.
  *                          The counting kernels always trace every segment: shadow_rays stays the reference's count.
+ *   "segment_planes" 0 / 1  path tracing, the timed any-hit kernel of scenes whose kernels are the leanest variants (no KD mesh, no Cube / CSG, no texture:
+ *                          cornell_box's): before its node loop every next-event segment is tested against the planes of the scene's ELIGIBLE nodes -- untransformed
+ *                          meshes without a KD-tree, of fewer than six triangles, with finite bounded coordinates and no zero normal; at most 16 planes and 16
+ *                          nodes per scene, else none -- and a node is skipped by a wave of 64 segments when both ends of every one of them lie on one side of
+ *                          every triangle's plane by a margin (default 1).  Under that certificate (fray_amd/csrc/dev_segcert.hpp: statement, proof,
+ *                          tests/test_segcert.py) the reference's own arithmetic cannot report a hit of such a triangle nearer than the segment's end, so the
+ *                          picture is the same bit for bit, in both arithmetics (tests/test_gpu_segment_planes.py).  0 asks every node, as do the counting
+ *                          kernels always: node_tests and tri_tests stay the reference's counts.
  *   "seed_table_mib" 0..1048576  the cap, in MiB, of the scene's seed table (default 4096).  Every camera sample's generator starts from x[397] of the
  *                          mt19937 seeding recurrence of sample_seed(seed, pixel, sample) -- a word that depends on the contract seed, the frame size and the
  *                          bucket share and on nothing else, and that costs a 397-step chain (k_seed) per sample.  The table keeps these words, 4 bytes per
@@ -318,13 +326,15 @@ int  frayhip_scene_set_view(frayhip_scene* s, const frayhip_camera* camera, cons
  *                          fails, renders as without the table; the workspace takes the table's memory back before it plans smaller batches.
  *                          0 = off: nothing is held, every batch seeds its own words.  Radiance queries, adaptive and feature frames do not use the table.
  * The environment variables FRAYHIP_PT_LANES / FRAYHIP_PT_BUDGET_MIB / FRAYHIP_SPECULATE_FANS / FRAYHIP_FP_CONTRACT / FRAYHIP_SKIP_NULL_SEGMENTS /
- * FRAYHIP_SEED_TABLE_MIB preset them at frayhip_scene_create. */
+ * FRAYHIP_SEGMENT_PLANES / FRAYHIP_SEED_TABLE_MIB preset them at frayhip_scene_create. */
 int  frayhip_scene_set_option(frayhip_scene* s, const char* name, int64_t value);
 /* Reads an option back, or one of the last frame's read-only figures: "fans_filed" (camera samples whose first fan was drawn ahead),
  * "fan_children" (rays traced ahead), "fan_children_looked_up" (results used), "fans_given_up" (fans in which a ray drew a random
  * number after all, so that the rest of the fan was traced in place), "contracted_launches" (launches of the last frame that ran a kernel of
  * the "fp_contract" build), "shadow_segments" (entries of the next-event queues over the launches of the last frayhip_render / frayhip_render_progressive
- * frame: the visibility queries it actually traced), "whitted_path" (how the last Whitted frame ran: 0 = the recursive kernel, 1 = shade / visible / gather launches, 2 = fused), "pt_budget_effective_mib" (the queue budget frames currently plan with: pt_budget_mib clamped to the device's
+ * frame: the visibility queries it actually traced), "segment_plane_nodes" (the scene's nodes eligible for option "segment_planes"; fixed at
+ * frayhip_scene_create), "shadow_nodes_skipped" (the last such frame's sum, over the wave iterations of its any-hit launches -- 64 segments each -- of the
+ * nodes skipped under that option), "whitted_path" (how the last Whitted frame ran: 0 = the recursive kernel, 1 = shade / visible / gather launches, 2 = fused), "pt_budget_effective_mib" (the queue budget frames currently plan with: pt_budget_mib clamped to the device's
  * free memory, halved when an allocation failed and the frame could be planned again), "seed_table_bytes" (what the seed table currently holds on the
  * device), "seed_launches" (k_seed launches of the last frame) and "seed_planes_reused" (sample planes the last frame took from the table). */
 int  frayhip_scene_get_option(frayhip_scene* s, const char* name, int64_t* value);
