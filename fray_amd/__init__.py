@@ -5,9 +5,9 @@ the reference's `Scene` interface (src/scene.h:280-299: parseScene / settings / 
 beginRender) and `render()` (src/main.cpp:373).  All rendering happens in the HIP library; there is
 no CPU fallback -- if the library is missing or no GPU is present the calls fail loudly.
 """
-from .scene import (Scene, FrayError, lib, render_info, denoise, denoise_params, denoise_signal,  # noqa: F401
+from .scene import (Scene, Accumulation, FrayError, lib, render_info, denoise, denoise_params, denoise_signal,  # noqa: F401
                     temporal_accumulate, temporal_params, view_from_camera)
 from . import abi  # noqa: F401
 
-__all__ = ["Scene", "FrayError", "lib", "abi", "render_info", "denoise", "denoise_params", "denoise_signal", "temporal_accumulate",
+__all__ = ["Scene", "Accumulation", "FrayError", "lib", "abi", "render_info", "denoise", "denoise_params", "denoise_signal", "temporal_accumulate",
            "temporal_params", "view_from_camera"]

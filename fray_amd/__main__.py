@@ -7,7 +7,10 @@ src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --he
                          python -m fray_amd scene.fray -o out.bmp --denoise [--feature-samples N] [--features-out FILE.npy]   (the frame denoised
                                                                                           with its first-hit features; --features-out alone saves them)
                          python -m fray_amd scene.fray -o out.bmp --denoise --frames N [--yaw-step DEG]   (N frames with temporal accumulation, the scene
-                                                                                          file's camera turned by DEG per frame: out_0000.bmp ...)"""
+                                                                                          file's camera turned by DEG per frame: out_0000.bmp ...)
+                         python -m fray_amd scene.fray -o out.bmp --accumulate FILE.npz [--spp N] [--noise-out FILE.npy] [--time-limit SECONDS]
+                                                                                         (N more samples per pixel on top of the state in FILE.npz, which
+                                                                                          is started when it does not exist; the picture of all of them)"""
 import argparse
 import json
 import os
@@ -16,7 +19,7 @@ import time
 
 import numpy as np
 
-from . import Scene, abi, lib
+from . import Accumulation, Scene, abi, lib
 
 
 def build_parser():
@@ -53,6 +56,12 @@ def build_parser():
                          "OUTPUT's name with _0000, _0001, ... before the extension")
     ap.add_argument("--yaw-step", type=float, default=1.0, metavar="DEG",
                     help="with --frames: frame k sees the scene file's camera with its yaw turned by k * DEG degrees (default 1)")
+    ap.add_argument("--accumulate", metavar="FILE.npz",
+                    help="resumable frame (Scene.render_samples): continue the state saved in FILE.npz by --spp more samples per pixel (default: the "
+                         "scene's own count), or start it when the file does not exist; writes FILE.npz and the picture of all samples so far.  A "
+                         "state of another size or seed is refused.  With --time-limit the state that was cut short is saved and can be continued")
+    ap.add_argument("--noise-out", metavar="FILE.npy",
+                    help="with --accumulate: also save the noise buffer, float32 [H, W] (the variance estimate of the mean's luminance)")
     return ap
 
 
@@ -82,6 +91,25 @@ def check_args(ap, a):
         ap.error("--frames must be >= 1")
     if a.frames is not None and a.features_out:
         ap.error("--frames cannot be combined with --features-out")
+    if a.accumulate and (a.denoise or a.adaptive is not None or a.probe):
+        ap.error("--accumulate cannot be combined with --denoise, --adaptive or --probe")
+    if a.noise_out and not a.accumulate:
+        ap.error("--noise-out needs --accumulate")
+    if a.spp is not None and a.accumulate and a.spp < 1:
+        ap.error("--spp must be >= 1")
+
+
+def load_accumulation(ap, a, s):
+    """The state of --accumulate before the scene is uploaded: FILE.npz's when it exists (refused unless it is a state of this size and seed),
+    else a new one."""
+    if not os.path.exists(a.accumulate):
+        return Accumulation.empty(s.frame_size, a.seed)
+    try:
+        state = Accumulation.load(a.accumulate)
+        state.check("--accumulate " + a.accumulate, s.frame_size, a.seed, 0, 1)
+    except (ValueError, OSError, KeyError) as e:
+        ap.error(str(e))
+    return state
 
 
 def adaptive_summary(spp, info):
@@ -120,6 +148,7 @@ def main(argv=None):
             s.settings.numPaths = a.spp
         elif s.camera.dof:
             s.camera.numDOFSamples = a.spp
+    state = load_accumulation(ap, a, s) if a.accumulate else None
     s.beginRender(a.device)
     if a.probe:
         print(json.dumps(probe(s, a.probe[0], a.probe[1], a.shade, a.seed)))
@@ -151,6 +180,25 @@ def main(argv=None):
         st = info["stats"]
         print(json.dumps(adaptive_summary(spp_map, info)))
         spp_text = "adaptive, mean %.2f spp" % spp_map.mean()
+    elif a.accumulate:
+        def progress(info):
+            if a.progress:
+                print("%s%d / %d spp, batch %d / %d, %.1f ms" % ("done: " if info["final"] else "", info["samples_done"], info["samples_total"],
+                                                                info["batches_done"], info["batches_total"], info["ms_elapsed"]), flush=True)
+            return a.time_limit is not None and not info["final"] and info["ms_elapsed"] >= a.time_limit * 1000.0
+        before = state.samples_done
+        count = a.spp if a.spp else s.samples_per_pixel()
+        watch = a.progress or a.time_limit is not None
+        out = s.render_samples(count, state, seed=a.seed, stats=True, noise=bool(a.noise_out), progress=progress if watch else None)
+        img, st = out[0], out[-1]
+        spp_text = "samples %d .. %d of the state, %d spp in all" % (before, state.samples_done - 1, state.samples_done)
+        if st.get("cancelled"):
+            print("Time limit of %gs reached: the state holds %d samples per pixel (%d of this run's %d); run again to continue"
+                  % (a.time_limit, state.samples_done, state.samples_done - before, count))
+        print("wrote", state.save(a.accumulate))
+        if a.noise_out:
+            np.save(a.noise_out, out[2])
+            print("wrote", a.noise_out)
     elif a.progress or a.time_limit is not None:
         def progress(info):
             if a.progress:

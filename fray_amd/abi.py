@@ -169,6 +169,13 @@ class Adaptive(C.Structure):
                 ("samples", u64)]
 
 
+ACCUM_CHANNELS = 4      # FRAYHIP_ACCUM_CHANNELS: sum.r, sum.g, sum.b, m2
+
+
+class Samples(C.Structure):
+    _fields_ = [("sample_first", i32), ("sample_count", i32), ("samples_done", i32), ("_pad", i32)]
+
+
 # struct frayhip_denoise (a struct tag without a typedef: the name is also the entry point's, so it is not in STRUCTS, which mirrors the typedefs)
 class Denoise(C.Structure):
     _fields_ = [("levels", i32), ("demodulate", i32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float),
@@ -200,7 +207,8 @@ STRUCTS = {"frayhip_transform": Transform, "frayhip_geom_ref": GeomRef, "frayhip
            "frayhip_settings": Settings, "frayhip_environment": Environment,
            "frayhip_scene_desc": SceneDesc, "frayhip_frame": Frame, "frayhip_stats": Stats,
            "frayhip_progress": Progress, "frayhip_progressive": Progressive,
-           "frayhip_shade_request": ShadeRequest, "frayhip_adaptive": Adaptive, "frayhip_view": View}
+           "frayhip_shade_request": ShadeRequest, "frayhip_adaptive": Adaptive, "frayhip_samples": Samples,
+           "frayhip_view": View}
 
 # Every symbol include/frayhip.h declares: name -> (restype, argtypes)
 VP = C.c_void_p
@@ -220,6 +228,8 @@ SYMBOLS = {
     "frayhip_render_device_progressive": (C.c_int, [VP, P(Frame), P(Progressive), VP, VP, VP, VP, P(Stats)]),
     "frayhip_render_adaptive": (C.c_int, [VP, P(Frame), P(Adaptive), VP, VP, VP, P(Stats)]),
     "frayhip_render_device_adaptive": (C.c_int, [VP, P(Frame), P(Adaptive), VP, VP, VP, VP, P(Stats)]),
+    "frayhip_render_samples": (C.c_int, [VP, P(Frame), P(Samples), P(Progressive), VP, VP, VP, P(Stats)]),
+    "frayhip_render_samples_device": (C.c_int, [VP, P(Frame), P(Samples), P(Progressive), VP, VP, VP, VP, P(Stats)]),
     "frayhip_render_features": (C.c_int, [VP, P(Frame), C.c_int, VP, P(Stats)]),
     "frayhip_render_features_device": (C.c_int, [VP, P(Frame), C.c_int, VP, VP, P(Stats)]),
     "frayhip_denoise_defaults": (C.c_int, [P(Denoise)]),

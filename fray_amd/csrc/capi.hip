@@ -972,6 +972,7 @@ int frayhip_scene_get_option(frayhip_scene* s, const char* name, int64_t* value)
     else if (n == "seed_table_bytes") *value = (int64_t)s->seedTab.bytes;
     else if (n == "seed_launches") *value = s->lastSeedLaunches;
     else if (n == "seed_planes_reused") *value = s->lastSeedReused;
+    else if (n == "batch_lanes") *value = s->lastBatchLanes;
     else if (n == "whitted_path") *value = s->lastWhittedPath;
     else if (n == "fused_whitted_max") *value = s->fusedWhittedMax;
     else if (n == "pt_budget_effective_mib") *value = (int64_t)(frayhip_detail::work_budget(s) >> 20);
@@ -1061,7 +1062,7 @@ int render_dispatch(frayhip_scene* s, const frayhip_frame* f, float* d_rgb, int3
     if (s->rendering) { set_error("frayhip_render: the scene is already rendering a frame (a render call from inside a progress callback?)"); return FRAYHIP_E_ARG; }
     frayhip_detail::Busy busy(s, stream, false);          // render_impl drains its lanes itself on an early return
     return frayhip_detail::for_flag_word(frayhip_detail::flag_word(s, (f->flags & FRAYHIP_FRAME_STATS) != 0), [&](auto w) {
-        return frayhip_detail::render_impl<decltype(w)::value>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog);
+        return frayhip_detail::render_impl<decltype(w)::value>(s, f, d_rgb, d_hit_id, d_hit_dist, stream, st, prog, nullptr);
     });
 }
 

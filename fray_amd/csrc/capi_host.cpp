@@ -115,7 +115,7 @@ int frayhip_sizeof(const char* n)
     FRAYHIP_SZ(frayhip_kdnode) FRAYHIP_SZ(frayhip_mesh) FRAYHIP_SZ(frayhip_texture) FRAYHIP_SZ(frayhip_shader)
     FRAYHIP_SZ(frayhip_layer) FRAYHIP_SZ(frayhip_light) FRAYHIP_SZ(frayhip_camera) FRAYHIP_SZ(frayhip_settings)
     FRAYHIP_SZ(frayhip_environment) FRAYHIP_SZ(frayhip_scene_desc) FRAYHIP_SZ(frayhip_frame) FRAYHIP_SZ(frayhip_stats)
-    FRAYHIP_SZ(frayhip_progress) FRAYHIP_SZ(frayhip_progressive) FRAYHIP_SZ(frayhip_shade_request) FRAYHIP_SZ(frayhip_adaptive)
+    FRAYHIP_SZ(frayhip_progress) FRAYHIP_SZ(frayhip_progressive) FRAYHIP_SZ(frayhip_shade_request) FRAYHIP_SZ(frayhip_adaptive) FRAYHIP_SZ(frayhip_samples)
     FRAYHIP_SZ(frayhip_view)
     if (!strcmp(n, "frayhip_denoise")) return (int)sizeof(struct frayhip_denoise);   // a struct tag: the name is also a function's
     if (!strcmp(n, "frayhip_temporal")) return (int)sizeof(struct frayhip_temporal);

@@ -51,9 +51,12 @@ auto for_flag_word(int w, Fn&& fn)
     __builtin_unreachable();
 }
 
+// acc: the accumulation request of frayhip_render_samples (accum.hpp), nullptr on every other entry
+struct AccumCall;
 template <int ST>
-int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t* d_id, double* d_dist, hipStream_t stream, frayhip_stats* st, const Progress* prog);
-FRAY_EXTERN_ST(int render_impl, (frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*))
+int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t* d_id, double* d_dist, hipStream_t stream, frayhip_stats* st, const Progress* prog,
+                AccumCall* acc);
+FRAY_EXTERN_ST(int render_impl, (frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*, AccumCall*))
 
 // The frame's samples per pixel (main.cpp:395-400)
 int frame_spp(const frayhip_scene* s);

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <cstdio>
 
+#include "accum.hpp"
 #include "entry_support.hpp"
 #include "kernels.hpp"
 
@@ -103,6 +104,8 @@ inline int seed_batch(frayhip_scene* sc, const DFrame& F, int nItems, int s0, in
 //     for the host entry) follows it on the same lane, before the event the host waits on and the next resolve waits on is recorded: `sum` and
 //     the frame are not touched again until the host has seen them, and evOrder[r % window] is re-recorded only after that;
 //   - a cancel stops the tracing; the batches already traced are resolved in order (no more callbacks), and finish() writes their mean.
+// With an accumulation request (accum.hpp: frayhip_render_samples) the batches are samples first .. total - 1, the sum is the caller's state, which
+// every resolve leaves complete, and previews and finish() make the frame (and the noise) from it with k_acc_mean -- also when nothing was cut short.
 struct Batches {
     frayhip_scene* sc = nullptr;
     const Progress* prog = nullptr;
@@ -112,6 +115,8 @@ struct Batches {
     float* d_rgb = nullptr;
     size_t frameBytes = 0;            // the host entry's whole-frame copy
     float* sum = nullptr;             // the running per-pixel sum between batches
+    AccumCall* acc = nullptr;         // the accumulation request: its state takes the place of `sum`
+    int first = 0;                    // the first sample of the call (0 without the request)
     int total = 1, chunk = 1, nBatches = 1, window = 1;
     int resolved = 1, samplesDone = 1;
     bool cancelled = false;
@@ -128,6 +133,12 @@ struct Batches {
         p.preview = preview ? 1 : 0; p.final = final ? 1 : 0;
         p.rgb = rgb;
         return prog->req->fn(prog->req->user, &p);
+    }
+    int samples_after(int r) const { return std::min(total, first + (r + 1) * chunk); }          // ... batch r was resolved
+    void mean(hipStream_t ls, int n, bool withNoise) const
+    {
+        if (acc) launch_acc_mean(grid_for(nItems), ls, F, nItems, n, acc->accum, d_rgb, withNoise ? acc->noise : nullptr);
+        else hipLaunchKernelGGL(k_resolve_mean, dim3(grid_for(nItems)), dim3(256), 0, ls, F, nItems, n, (const float*)sum, d_rgb);
     }
     bool preview_due()
     {
@@ -150,7 +161,7 @@ struct Batches {
             resolved = nBatches; samplesDone = total;
             return FRAYHIP_OK;
         }
-        resolved = samplesDone = 0;
+        resolved = 0; samplesDone = first;
         int traced = 0;
         for (; traced < std::min(window, nBatches); traced++)
             if (const int rc = trace(traced)) return rc;
@@ -160,7 +171,7 @@ struct Batches {
             const bool last = r == nBatches - 1;
             const bool preview = !last && !cancelled && preview_due();
             if (preview) {
-                hipLaunchKernelGGL(k_resolve_mean, dim3(grid_for(nItems)), dim3(256), 0, ls, F, nItems, std::min(total, (r + 1) * chunk), (const float*)sum, d_rgb);
+                mean(ls, samples_after(r), false);
                 if (prog->h_rgb) HIP_TRY(hipMemcpyAsync(prog->h_rgb, d_rgb, frameBytes, hipMemcpyDeviceToHost, ls));
             }
             hipEvent_t ev = evOrder ? evOrder[r % window] : sc->evResolved[0];
@@ -170,7 +181,7 @@ struct Batches {
                 traced++;
             }
             resolved = r + 1;
-            samplesDone = std::min(total, (r + 1) * chunk);
+            samplesDone = samples_after(r);
             if (cancelled || last) continue;
             HIP_TRY(hipEventSynchronize(ev));
             HIP_TRY(hipGetLastError());
@@ -182,34 +193,45 @@ struct Batches {
     bool cut_short() const { return prog && samplesDone < total; }
     void finish(hipStream_t stream) const
     {
-        if (cut_short() && d_rgb && sum && samplesDone > 0)
-            hipLaunchKernelGGL(k_resolve_mean, dim3(grid_for(nItems)), dim3(256), 0, stream, F, nItems, samplesDone, (const float*)sum, d_rgb);
+        if (acc) {
+            acc->done = samplesDone;
+            if ((d_rgb || acc->noise) && nItems > 0 && samplesDone > 0) mean(stream, samplesDone, true);
+        } else if (cut_short() && d_rgb && sum && samplesDone > 0) mean(stream, samplesDone, false);
     }
 };
 }  // namespace
 
 template <int ST>
-int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t* d_id, double* d_dist, hipStream_t stream, frayhip_stats* st, const Progress* prog)
+int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t* d_id, double* d_dist, hipStream_t stream, frayhip_stats* st, const Progress* prog,
+                AccumCall* acc)
 {
+    const char* const who = acc ? "frayhip_render_samples" : "frayhip_render";
     const auto t0 = std::chrono::steady_clock::now();
     const frayhip_settings& set = sc->settings;
     const int W = set.frameWidth, H = set.frameHeight;
-    const DFrame F = frame_record(sc, f->bucket_first, f->bucket_stride, f->seed);
-    if (const int rc = check_bucket_range("frayhip_render", F.nBuckets)) return rc;
-    if (const int rc = check_pixel_cap("frayhip_render", F.nBuckets)) return rc;
-    const int spp = F.spp, nItems = F.nBuckets * 2304;
+    DFrame F = frame_record(sc, f->bucket_first, f->bucket_stride, f->seed);
+    if (const int rc = check_bucket_range(who, F.nBuckets)) return rc;
+    if (const int rc = check_pixel_cap(who, F.nBuckets)) return rc;
+    // An accumulation request (accum.hpp; MODE_RENDER, checked by its entries): the call's samples are first .. first + spp - 1, batch j begins at sample
+    // first + j * chunk, and the frame's own sample count plays no part.  The kernels read F.spp only to learn whether they write the pixel of a
+    // one-sample frame themselves; on this path none does (every sample goes through the state), so the record carries no count at all.
+    const int first = acc ? acc->first : 0;
+    if (acc) F.spp = 0;
+    const int spp = acc ? acc->count : F.spp, nItems = F.nBuckets * 2304;
     const DScene S = frame_scene(sc);
     DCamera C = camera_begin_frame(sc->camera, W, H);
     Batches B;
     B.sc = sc; B.prog = prog; B.t0 = t0; B.F = F; B.nItems = nItems; B.d_rgb = d_rgb;
     B.frameBytes = (size_t)W * H * 12;
-    B.total = B.samplesDone = f->mode == FRAYHIP_MODE_PRIMARY_ID ? 1 : spp;          // one-shot paths (k_primary, k_black) report one batch
+    B.acc = acc; B.first = first;
+    B.total = B.samplesDone = f->mode == FRAYHIP_MODE_PRIMARY_ID ? 1 : first + spp;          // one-shot paths (k_primary, k_black) report one batch
 
     // An early (error) return below must not leave work in flight on the side lanes' streams, which the caller cannot see: whatever
     // was enqueued is drained before the call returns.
     struct Drain { frayhip_scene* sc; bool armed = true; ~Drain() { if (armed) { (void)hipDeviceSynchronize(); seed_table_invalidate(sc); } } } drain{sc};
     sc->seedTab.serving = false;
     sc->lastSeedLaunches = sc->lastSeedReused = 0;
+    sc->lastBatchLanes = 1;
     HIP_TRY(hipMemsetAsync(sc->d_stats, 0, kStatsBytes, stream));
     DCursors* cursors = (DCursors*)((unsigned char*)sc->d_stats + kCursorOffset);
     HIP_TRY(hipEventRecord(sc->evA, stream));
@@ -226,11 +248,12 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
             nTraceEvents = 2;
         }
     } else if (f->mode == FRAYHIP_MODE_RENDER) {
-        if (!d_rgb) { set_error("frayhip_render: MODE_RENDER needs an rgb buffer"); return FRAYHIP_E_ARG; }
+        if (!d_rgb && !acc) { set_error("frayhip_render: MODE_RENDER needs an rgb buffer"); return FRAYHIP_E_ARG; }
         if (set.maxTraceDepth < 0) {
-            if (nItems > 0) hipLaunchKernelGGL(k_black, dim3(grid_for(nItems)), dim3(256), 0, stream, F, nItems, sc->camera.stereoSeparation > 0 ? 2 : 1, d_rgb, sc->d_stats);
+            if (nItems > 0 && acc) launch_acc_black(grid_for(nItems), stream, F, nItems, first, spp, sc->camera.stereoSeparation > 0 ? 2 : 1, acc->accum, sc->d_stats);
+            else if (nItems > 0) hipLaunchKernelGGL(k_black, dim3(grid_for(nItems)), dim3(256), 0, stream, F, nItems, sc->camera.stereoSeparation > 0 ? 2 : 1, d_rgb, sc->d_stats);
         } else if (!set.gi) {
-            if (!F.jitter && spp > 5) { set_error("frayhip_render: bad sample count"); return FRAYHIP_E_ARG; }
+            if (!acc && !F.jitter && spp > 5) { set_error("frayhip_render: bad sample count"); return FRAYHIP_E_ARG; }
             sc->lastWhittedPath = 0;
             if (nItems > 0 && sc->whittedNeedsRecursion) {
                 // workspace: per-thread mt19937 state columns for samples that draw more than 227 words, the pixels' running sums, then per
@@ -243,7 +266,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 // Not in the counting variants (their counters are the reference's call counts), not in stereo frames (the right eye continues the left eye's generator).
                 int fan = (!(ST & 1) && sc->speculateFans && !(sc->camera.stereoSeparation > 0)) ? sc->specFanMax : 0;
                 int chunk = 0;
-                seed_table_begin(sc, F, nItems, spp);
+                if (first == 0) seed_table_begin(sc, F, nItems, spp);          // a call that continues a state seeds into the workspace: its planes would never be read again
                 for (;;) {          // planned again with half the budget when the allocation fails (ensure_work_or_shrink)
                     const bool tabled = sc->seedTab.serving;          // the batches' x397 words are the table's, not the workspace's
                     const size_t wb = work_budget(sc);
@@ -283,9 +306,9 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                     SPB.cdraws = take(kids);
                 }
                 auto trace = [&](int j) -> int {
-                    const int s0 = j * chunk, cn = std::min(chunk, spp - s0);
-                    if (s0 > 0) HIP_TRY(hipMemsetAsync(cursors, 0, 3 * sizeof(DCursors), stream));  // the tile cursors of the previous batch
-                    if (fan > 0) HIP_TRY(hipMemsetAsync(SPB.counters, 0, s0 == 0 ? 256 : 32, stream));
+                    const int s0 = first + j * chunk, cn = std::min(chunk, spp - j * chunk);
+                    if (j > 0) HIP_TRY(hipMemsetAsync(cursors, 0, 3 * sizeof(DCursors), stream));  // the tile cursors of the previous batch
+                    if (fan > 0) HIP_TRY(hipMemsetAsync(SPB.counters, 0, j == 0 ? 256 : 32, stream));
                     const uint32_t* x397 = nullptr;
                     if (const int rc = seed_batch(sc, F, nItems, s0, cn, seedWords, stream, x397)) return rc;
                     hipEvent_t a = pool_event(sc->evPool, nTraceEvents), b = pool_event(sc->evPool, nTraceEvents + 1);
@@ -321,8 +344,9 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                     return FRAYHIP_OK;
                 };
                 auto resolve = [&](int j) -> int {
-                    const int s0 = j * chunk, cn = std::min(chunk, spp - s0);
-                    if (spp > 1) hipLaunchKernelGGL(k_pt_resolve, dim3(grid_for(nItems)), dim3(256), 0, stream, F, C, set.saturation, nItems, s0, cn, rad, (const float*)nullptr, sum, d_rgb);
+                    const int s0 = first + j * chunk, cn = std::min(chunk, spp - j * chunk);
+                    if (acc) launch_acc_resolve(grid_for(nItems), stream, F, C, set.saturation, nItems, s0, cn, rad, nullptr, acc->accum);
+                    else if (spp > 1) hipLaunchKernelGGL(k_pt_resolve, dim3(grid_for(nItems)), dim3(256), 0, stream, F, C, set.saturation, nItems, s0, cn, rad, (const float*)nullptr, sum, d_rgb);
                     if (fan > 0) hipLaunchKernelGGL(k_add4, dim3(1), dim3(64), 0, stream, SPB.counters, (unsigned long long*)(SPB.counters + 8));       // the frame's totals over its batches
                     return FRAYHIP_OK;
                 };
@@ -347,7 +371,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 const bool fusedShade = T <= sc->fusedWhittedMax && !kd_variant(ST);
                 const bool draws = F.jitter || sc->camera.dof || sc->lightDraws;
                 const bool seeds = !fusedShade || draws;          // the frame launches k_seed at all
-                if (seeds) seed_table_begin(sc, F, nItems, spp);
+                if (seeds && first == 0) seed_table_begin(sc, F, nItems, spp);
                 for (;;) {          // planned again with half the budget when the allocation fails (ensure_work_or_shrink)
                     const bool tabled = sc->seedTab.serving;          // the batches' x397 words are the table's, not the workspace's
                     const size_t wb = work_budget(sc);
@@ -379,9 +403,9 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 float* radR = (float*)take(slots * 12);
                 uint32_t* seedWords = sc->seedTab.serving ? nullptr : (uint32_t*)take(slots * 4);
                 sc->lastWhittedPath = fusedShade ? 2 : 1;
-                const bool direct = fusedShade && spp == 1 && !stereo;      // the fused kernel writes the pixel itself
+                const bool direct = fusedShade && spp == 1 && !stereo && !acc;      // the fused kernel writes the pixel itself
                 auto trace = [&](int j) -> int {
-                    const int s0 = j * chunk, cn = std::min(chunk, spp - s0);
+                    const int s0 = first + j * chunk, cn = std::min(chunk, spp - j * chunk);
                     const size_t bs = (size_t)nItems * cn, bN = bs * eyes;      // this batch's slots: arrays are used with stride bN
                     const uint32_t* x397 = nullptr;          // stays null when no generator can be asked for a word: no launch, and no plane of the table is touched
                     if (seeds) { if (const int rc = seed_batch(sc, F, nItems, s0, cn, seedWords, stream, x397)) return rc; }
@@ -389,7 +413,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                     hipEvent_t ec = pool_event(sc->evPoolShadow, nShadowEvents), ed = pool_event(sc->evPoolShadow, nShadowEvents + 1);
                     if (!ea || !eb || !ec || !ed) return FRAYHIP_E_NOMEM;
                     HIP_TRY(hipEventRecord(ea, stream));
-                    if (s0 > 0) HIP_TRY(hipMemsetAsync(cursors, 0, 2 * sizeof(DCursors), stream));        // the previous batch's tile cursors (one set per kernel)
+                    if (j > 0) HIP_TRY(hipMemsetAsync(cursors, 0, 2 * sizeof(DCursors), stream));        // the previous batch's tile cursors (one set per kernel)
                     // tiles are claimed when a wave gets at least 16 of them, walked with a fixed stride otherwise (next_tile, kernels.hpp)
                     const bool claimShade = bs / 64 >= (size_t)grid * 4 * 16;
                     if (fusedShade) {
@@ -412,8 +436,9 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                     return FRAYHIP_OK;
                 };
                 auto resolve = [&](int j) -> int {
-                    const int s0 = j * chunk, cn = std::min(chunk, spp - s0);
-                    if (!direct) hipLaunchKernelGGL(k_pt_resolve, dim3(grid_for(nItems)), dim3(256), 0, stream, F, C, set.saturation, nItems, s0, cn, radL, stereo ? radR : nullptr, sum, d_rgb);
+                    const int s0 = first + j * chunk, cn = std::min(chunk, spp - j * chunk);
+                    if (acc) launch_acc_resolve(grid_for(nItems), stream, F, C, set.saturation, nItems, s0, cn, radL, stereo ? radR : nullptr, acc->accum);
+                    else if (!direct) hipLaunchKernelGGL(k_pt_resolve, dim3(grid_for(nItems)), dim3(256), 0, stream, F, C, set.saturation, nItems, s0, cn, radL, stereo ? radR : nullptr, sum, d_rgb);
                     return FRAYHIP_OK;
                 };
                 B.sum = sum; B.chunk = chunk; B.nBatches = (spp + chunk - 1) / chunk;
@@ -474,7 +499,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
             const bool stereo = sc->camera.stereoSeparation > 0;
             int chunk = 0, nBatches = 0, nLanes = 0;
             size_t nPaths = 0, nQueue = 0, laneBytes = 0;
-            seed_table_begin(sc, F, nItems, spp);
+            if (first == 0) seed_table_begin(sc, F, nItems, spp);
             for (;;) {              // planned again with half the budget when the allocation fails (ensure_work_or_shrink)
                 const bool tabled = sc->seedTab.serving;          // the lanes' x397 words are the table's, not the workspace's
                 const size_t budget = std::max<size_t>(work_budget(sc) / perPath, 1);       // paths in flight over all lanes
@@ -495,6 +520,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 if (tabled && !sc->seedTab.serving) continue;          // the workspace took the table's memory: plan again with the per-batch seed words
                 break;
             }
+            sc->lastBatchLanes = nLanes;
             struct Lane {
                 hipStream_t stream;
                 PathQueue Q[2];
@@ -540,7 +566,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
             HIP_TRY(hipEventRecord(sc->evLaneStart, stream));               // the side lanes start after whatever precedes this frame on the caller's stream
             for (int k = 1; k < nLanes; k++) HIP_TRY(hipStreamWaitEvent(sc->laneStream[k], sc->evLaneStart, 0));
             auto trace = [&](int batch) -> int {
-                const int s0 = batch * chunk, cn = std::min(chunk, spp - s0);
+                const int s0 = first + batch * chunk, cn = std::min(chunk, spp - batch * chunk);
                 Lane& L = lane[batch % nLanes];
                 hipStream_t ls = L.stream;
                 const uint32_t* x397 = nullptr;
@@ -600,12 +626,14 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 return FRAYHIP_OK;
             };
             auto resolve = [&](int batch) -> int {
-                const int s0 = batch * chunk, cn = std::min(chunk, spp - s0);
+                const int s0 = first + batch * chunk, cn = std::min(chunk, spp - batch * chunk);
                 Lane& L = lane[batch % nLanes];
                 hipStream_t ls = L.stream;
                 // the running per-pixel sum takes the batches in sample order (evResolved is recorded after each resolve, Batches::run)
                 if (batch > 0 && nLanes > 1) HIP_TRY(hipStreamWaitEvent(ls, sc->evResolved[(batch - 1) % nLanes], 0));
-                if (stereo) hipLaunchKernelGGL(k_pt_resolve, dim3(grid_for(nItems)), dim3(256), 0, ls, F, C, set.saturation, nItems, s0, cn, L.sampleRad, L.sampleRadR, sum, d_rgb);
+                if (acc && stereo) launch_acc_resolve(grid_for(nItems), ls, F, C, set.saturation, nItems, s0, cn, L.sampleRad, L.sampleRadR, acc->accum);
+                else if (acc) launch_acc_resolve_terms(grid_for(nItems), ls, F, nItems, s0, cn, TermBuf{L.terms, L.termCount, (uint32_t)nPaths, 0}, acc->accum);
+                else if (stereo) hipLaunchKernelGGL(k_pt_resolve, dim3(grid_for(nItems)), dim3(256), 0, ls, F, C, set.saturation, nItems, s0, cn, L.sampleRad, L.sampleRadR, sum, d_rgb);
                 else hipLaunchKernelGGL(k_pt_resolve_terms, dim3(grid_for(nItems)), dim3(256), 0, ls, F, nItems, s0, cn, TermBuf{L.terms, L.termCount, (uint32_t)nPaths, 0}, sum, d_rgb);
                 return FRAYHIP_OK;
             };
@@ -618,7 +646,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
         set_error("frayhip_render: unknown mode");
         return FRAYHIP_E_ARG;
     }
-    B.finish(stream);                       // a cancelled progressive frame: the mean of the samples resolved
+    B.finish(stream);                       // a cancelled progressive frame: the mean of the samples resolved; an accumulating call: always, from its state
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sc->evB, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -695,10 +723,10 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
     }
     if (prog) {
         // the final call: the finished (or cancelled) frame, copied to the host frame first for the host entry
-        const bool rgbOut = f->mode == FRAYHIP_MODE_RENDER;
+        const bool rgbOut = f->mode == FRAYHIP_MODE_RENDER && d_rgb;
         if (rgbOut && prog->h_rgb) HIP_TRY(hipMemcpy(prog->h_rgb, d_rgb, B.frameBytes, hipMemcpyDeviceToHost));
         (void)B.call(rgbOut, true, rgbOut ? (prog->h_rgb ? prog->h_rgb : d_rgb) : nullptr);
-        if (B.cut_short()) { set_error("frayhip_render: cancelled by the progress callback"); return FRAYHIP_E_CANCELLED; }
+        if (B.cut_short()) { set_error(std::string(who) + ": cancelled by the progress callback"); return FRAYHIP_E_CANCELLED; }
     }
     return FRAYHIP_OK;
 }

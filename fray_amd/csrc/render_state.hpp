@@ -103,6 +103,7 @@ struct frayhip_scene {
     // option "seed_table_mib": the cap of the seed table, 0 = off (every batch seeds into its own scratch words, as before the table)
     size_t seedTableCapBytes = (size_t)FRAY_SEED_TABLE_MIB << 20;
     SeedTable seedTab;
+    int lastBatchLanes = 0;           // the last frame's batch lanes: the streams its batches ran on, as planned (get_option "batch_lanes"; 1 unless path-traced)
     long long lastSeedLaunches = 0, lastSeedReused = 0;   // the last frame's k_seed launches and planes taken from the table (get_option "seed_launches", "seed_planes_reused")
     bool rendering = false;           // a frame of this scene is being rendered: set by every render entry, so that a progress callback cannot render or change it
 };

@@ -7,5 +7,5 @@
 #endif
 
 namespace frayhip_detail {
-template int render_impl<FRAY_ST>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*);
+template int render_impl<FRAY_ST>(frayhip_scene*, const frayhip_frame*, float*, int32_t*, double*, hipStream_t, frayhip_stats*, const Progress*, AccumCall*);
 }

@@ -288,6 +288,75 @@ def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, st
     return (hist, signal, var, st.as_dict()) if stats else (hist, signal, var)
 
 
+class Accumulation:
+    """The state of a resumable frame (include/frayhip.h "resumable frames"): `state`, float32 [H, W, 4] -- per pixel the FP32 sum of its samples'
+    colours and the second moment of their luminance -- as a numpy array (Scene.render_samples then goes through the host entry) or a torch tensor
+    on the GPU (the device entry); `samples_done`, the samples per pixel it holds; and what it belongs to: `seed`, `size` (W, H) and the bucket
+    share (`bucket_first`, `bucket_stride`) that was rendered into it.  The scene, its view and its settings are the caller's to keep unchanged."""
+
+    def __init__(self, state, samples_done=0, seed=42, size=None, bucket_first=0, bucket_stride=1):
+        self.state = state
+        self.samples_done = int(samples_done)
+        self.seed = int(seed) & 0xffffffff
+        self.size = (int(size[0]), int(size[1])) if size is not None else (int(state.shape[1]), int(state.shape[0]))
+        self.bucket_first, self.bucket_stride = int(bucket_first), int(bucket_stride)
+
+    @classmethod
+    def empty(cls, size, seed=42, bucket_first=0, bucket_stride=1, device=None):
+        """A state of no samples for a W x H frame: a numpy array, or with `device` a torch tensor there."""
+        W, H = int(size[0]), int(size[1])
+        if device is None:
+            state = np.zeros((H, W, abi.ACCUM_CHANNELS), np.float32)
+        else:
+            import torch
+            state = torch.zeros((H, W, abi.ACCUM_CHANNELS), dtype=torch.float32, device=device)
+        return cls(state, 0, seed, (W, H), bucket_first, bucket_stride)
+
+    @property
+    def on_device(self):
+        return _torch_tensor(self.state)
+
+    def check(self, who, size, seed, bucket_first, bucket_stride):
+        """ValueError unless the state is a well-formed one of this size, seed and bucket share."""
+        W, H = size
+        if self.size != (W, H):
+            raise ValueError("%s: the state belongs to a %d x %d frame, the scene renders %d x %d" % ((who,) + self.size + (W, H)))
+        if self.seed != (int(seed) & 0xffffffff):
+            raise ValueError("%s: the state was rendered with seed %d, the call asks for seed %d" % (who, self.seed, int(seed) & 0xffffffff))
+        if (self.bucket_first, self.bucket_stride) != (int(bucket_first), int(bucket_stride)):
+            raise ValueError("%s: the state holds the bucket share (first %d, stride %d), the call asks for (first %d, stride %d)"
+                             % (who, self.bucket_first, self.bucket_stride, bucket_first, bucket_stride))
+        if self.samples_done < 0:
+            raise ValueError("%s: the state's samples_done is negative" % who)
+        st = self.state
+        if self.on_device:
+            import torch
+            ok = st.is_cuda and st.dtype == torch.float32 and st.is_contiguous()
+        else:
+            ok = isinstance(st, np.ndarray) and st.dtype == np.float32 and st.flags.c_contiguous and st.flags.writeable
+        if not ok or tuple(st.shape) != (H, W, abi.ACCUM_CHANNELS):
+            raise ValueError("%s: the state must be a contiguous float32 numpy array or GPU torch tensor shaped %s" % (who, (H, W, abi.ACCUM_CHANNELS)))
+
+    def save(self, path):
+        """Writes the state in .npz format to `path` as it is given (a tensor is copied to the host); load() reads it back as a numpy state.
+        Returns the path."""
+        path = os.fspath(path)
+        arr = self.state.cpu().numpy() if self.on_device else self.state
+        with open(path, "wb") as f:
+            np.savez(f, state=arr, samples_done=np.int64(self.samples_done), seed=np.uint32(self.seed), size=np.array(self.size, np.int64),
+                     share=np.array([self.bucket_first, self.bucket_stride], np.int64))
+        return path
+
+    @classmethod
+    def load(cls, path):
+        with np.load(os.fspath(path)) as z:
+            missing = [k for k in ("state", "samples_done", "seed", "size", "share") if k not in z.files]
+            if missing:
+                raise ValueError("Accumulation.load: %s is not a saved state (no %s)" % (path, ", ".join(missing)))
+            state = np.ascontiguousarray(z["state"], dtype=np.float32)
+            return cls(state, int(z["samples_done"]), int(z["seed"]), tuple(int(v) for v in z["size"]), int(z["share"][0]), int(z["share"][1]))
+
+
 class Scene:
     """`Scene scene` of the reference (scene.h:280-299).
 
@@ -361,7 +430,7 @@ class Scene:
 
     def get_option(self, name):
         """frayhip_scene_get_option: an option's value, or a figure of the last frame ("fans_filed", "fan_children", "fan_children_looked_up", "fans_given_up", "contracted_launches", "shadow_segments",
-        "segment_plane_nodes", "shadow_nodes_skipped", "seed_table_bytes", "seed_launches", "seed_planes_reused")."""
+        "segment_plane_nodes", "shadow_nodes_skipped", "seed_table_bytes", "seed_launches", "seed_planes_reused", "batch_lanes")."""
         self._need_dev()
         v = C.c_int64(0)
         _check(lib.frayhip_scene_get_option(self._dev, name.encode(), C.byref(v)))
@@ -533,6 +602,62 @@ class Scene:
                 if n:                                   # (an empty tensor's data_ptr() is 0: nothing to call)
                     _check(lib.frayhip_shade_rays_device(self._dev, n, o.data_ptr(), d.data_ptr(), C.byref(req), rgb.data_ptr(), call.handle, C.byref(st)))
         return (rgb, st.as_dict()) if stats else rgb
+
+    # ---- resumable frames (include/frayhip.h "resumable frames") ----
+    def render_samples(self, count, state=None, seed=42, bucket_first=0, bucket_stride=1, spp_chunk=0, stats=False, progress=None, preview_ms=-1,
+                       noise=False, stream=None):
+        """Adds `count` samples per pixel to a frame (frayhip_render_samples): samples state.samples_done .. state.samples_done + count - 1 of the
+        call's buckets, under the scene's current view and settings; the frame's own sample count plays no part.  state: an Accumulation, or
+        None to start one (a numpy state).  A numpy state goes through the host entry and a state on the GPU through the device entry, on
+        `stream` (None: the current stream); rgb and noise are of the state's kind.
+
+        Returns (rgb, state[, noise][, stats]): rgb float32 [H, W, 3] is the mean of all samples the state holds -- after samples 0 .. N-1 it is
+        render() with N samples per pixel, bit for bit -- and `state` is the one given, updated in place.  noise=True adds the variance estimate
+        of the mean's luminance, float32 [H, W] (denoise_signal's variance, with demodulate=0).  The stats dict follows with stats=True or a
+        progress callback.  progress / preview_ms: as render(); previews show the running mean of all samples so far (info["image"], or
+        info["d_rgb"] for a state on the GPU), and samples_done counts from sample 0.  A cancelled call returns normally, with
+        stats["cancelled"] set and state.samples_done at the samples resolved; the next call continues from there.
+        A state of another seed, size or bucket share is refused (ValueError)."""
+        who = "render_samples"
+        count = int(count)
+        if count < 1:
+            raise ValueError("%s: count must be >= 1, got %d" % (who, count))
+        W, H = self.frame_size
+        if state is None:
+            state = Accumulation.empty((W, H), seed, bucket_first, bucket_stride)
+        elif not isinstance(state, Accumulation):
+            raise TypeError("%s: state must be an Accumulation, got %s" % (who, type(state).__name__))
+        state.check(who, (W, H), seed, bucket_first, bucket_stride)
+        self._need_dev()
+        st = abi.Stats()
+        fr = self._frame(abi.MODE_RENDER, state.seed, bucket_first, bucket_stride, spp_chunk, stats)
+        req = abi.Samples(sample_first=state.samples_done, sample_count=count)
+        preq, run = None, None
+        if not state.on_device:
+            rgb = np.zeros((H, W, 3), np.float32)
+            var = np.zeros((H, W), np.float32) if noise else None
+            if progress is not None:
+                preq, run = _progress_request(progress, preview_ms, lambda p: {"image": np.ctypeslib.as_array(p.rgb, shape=(H, W, 3))})
+            rc = lib.frayhip_render_samples(self._dev, C.byref(fr), C.byref(req), C.byref(preq) if preq is not None else None, _ptr(state.state),
+                                            _ptr(rgb), _ptr(var), C.byref(st))
+        else:
+            with _DeviceCall(state.state.device, stream) as call:
+                rgb = call.torch.zeros((H, W, 3), dtype=call.torch.float32, device=state.state.device)
+                var = call.torch.zeros((H, W), dtype=call.torch.float32, device=state.state.device) if noise else None
+                if progress is not None:
+                    preq, run = _progress_request(progress, preview_ms, lambda p: {"d_rgb": C.cast(p.rgb, C.c_void_p).value})
+                rc = lib.frayhip_render_samples_device(self._dev, C.byref(fr), C.byref(req), C.byref(preq) if preq is not None else None,
+                                                       _ptr(state.state), _ptr(rgb), _ptr(var), call.handle, C.byref(st))
+        if rc in (abi.OK, abi.E_CANCELLED):
+            state.samples_done = req.samples_done
+        if run is not None:
+            info = run.finish(rc, st)
+            info["samples_done"] = state.samples_done
+        else:
+            _check(rc)
+            info = st.as_dict()
+        out = (rgb, state) + ((var,) if noise else ())
+        return out + ((info,) if (stats or progress is not None) else ())
 
     # ---- adaptive frames (include/frayhip.h "adaptive frames") ----
     def _adaptive_request(self, threshold, min_spp, err_floor):

@@ -336,7 +336,8 @@ int  frayhip_scene_set_option(frayhip_scene* s, const char* name, int64_t value)
  * frayhip_scene_create), "shadow_nodes_skipped" (the last such frame's sum, over the wave iterations of its any-hit launches -- 64 segments each -- of the
  * nodes skipped under that option), "whitted_path" (how the last Whitted frame ran: 0 = the recursive kernel, 1 = shade / visible / gather launches, 2 = fused), "pt_budget_effective_mib" (the queue budget frames currently plan with: pt_budget_mib clamped to the device's
  * free memory, halved when an allocation failed and the frame could be planned again), "seed_table_bytes" (what the seed table currently holds on the
- * device), "seed_launches" (k_seed launches of the last frame) and "seed_planes_reused" (sample planes the last frame took from the table). */
+ * device), "seed_launches" (k_seed launches of the last frame) and "seed_planes_reused" (sample planes the last frame took from the table).
+ * "batch_lanes": the streams the last frame's batches ran on, as planned (1 unless path-traced). */
 int  frayhip_scene_get_option(frayhip_scene* s, const char* name, int64_t* value);
 
 /* Threads: a frayhip_scene renders one frame at a time (it owns one workspace and one set of
@@ -544,6 +545,63 @@ int  frayhip_render_adaptive(frayhip_scene* s, const frayhip_frame* f, frayhip_a
                              float* rgb, int32_t* spp_out, float* err_out, frayhip_stats* st);
 int  frayhip_render_device_adaptive(frayhip_scene* s, const frayhip_frame* f, frayhip_adaptive* a,
                                     float* d_rgb, int32_t* d_spp, float* d_err, void* hip_stream, frayhip_stats* st);
+
+/* ---- resumable frames (samples added to a frame that is already rendered) ---------------------------------------------------------------------
+ * The running per-pixel sum of a frame as a caller-held buffer, the STATE: W*H rows of FRAYHIP_ACCUM_CHANNELS floats, row-major, one 16-byte row
+ * per pixel: sum.r, sum.g, sum.b, m2.  A call renders samples sample_first .. sample_first + sample_count - 1 of every pixel of the call's buckets
+ * (frame.bucket_first / bucket_stride, as frayhip_render) into it, under the scene's current view, settings and integrator.  Pixels of other
+ * buckets are untouched in accum, rgb and noise.
+ *
+ * Which samples.  Sample i of a pixel is sample i of any frayhip_render frame of this scene and frame.seed -- film position (AA offset or
+ *   jitter), lens and both generators -- whatever the frame's own sample count (numPaths, numDOFSamples), which plays no part.  One exception: a
+ *   frame whose samples are not jittered (Whitted without DOF) has only its 1 (or, with wantAA, 5) samples, and sample_first + sample_count
+ *   beyond them is FRAYHIP_E_ARG.  For jittered frames the bound is 2^24, so that (float)N is exact.
+ * State, per pixel, all FP32, in sample order, without contraction.  c_i = the colour the frame's resolve adds for sample i: a path's terms
+ *   folded innermost first (term[n-1], then term[k] + result for k = n-2 .. 0); for a stereo frame the blended eyes.  For each sample in order:
+ *       sum = sum + c_i                       (per channel)
+ *       l   = ((c_i.r + c_i.g) + c_i.b) / 3.0f
+ *       m2  = m2 + l * l
+ *   With sample_first == 0 the buffer's contents are ignored and the row starts as the frame's sum does, at (0, 0, 0, 0).  With sample_first > 0
+ *   the buffer is taken as the state of samples 0 .. sample_first - 1: the caller's word is trusted.
+ * Outputs, N = samples_done.  rgb (optional, W*H*3) = sum / (float)N per channel, the frame's own division: after samples 0 .. N-1 it IS
+ *   frayhip_render with N samples per pixel, bit for bit, however the samples were cut into calls and batches.  noise (optional, W*H)
+ *   estimates the variance of the luminance of the mean:
+ *       lbar  = ((rgb.r + rgb.g) + rgb.b) / 3.0f
+ *       v     = max(0, m2 / (float)N - lbar * lbar)
+ *       noise = v / (float)(N - 1)            for N >= 2
+ *       noise = lbar * lbar                   for N == 1: one sample knows nothing about its spread, so it is "as uncertain as the value"
+ *   It is in rgb's domain, not demodulated: it goes into frayhip_denoise_signal (as `variance`, with rgb as `signal`) with demodulate = 0.
+ * Progress and cancel.  p may be NULL.  With it the contract of frayhip_render_progressive holds (callback thread, pacing, cancel latency);
+ *   previews are the running mean of ALL samples the state holds, and samples_done / samples_total in frayhip_progress count from sample 0.
+ *   After a cancel the call returns FRAYHIP_E_CANCELLED, the state holds exactly the resolved samples, r->samples_done says how many, rgb
+ *   and noise are made from them, and the next call continues from there.
+ * Behaves as a frame.  frame.spp_chunk is the batch size (0 = as many as the queue budget holds); the options pt_lanes, pt_budget_mib,
+ *   fp_contract, skip_null_segments, segment_planes, speculate_fans and fused_whitted_max act as in frayhip_render, and none of the first two
+ *   changes a bit of the state.  The last frame's figures (frayhip_scene_get_option) are updated as a frame updates them.  With
+ *   FRAYHIP_FRAME_STATS *st counts this call's samples only, so the counters of calls that tile [0, N) add up to the one-shot frame's.
+ * Seed table.  A call with sample_first == 0 uses the table as a frame does; one with sample_first > 0 neither reads nor alters it (its planes
+ *   would never be read again) and seeds into the workspace.
+ * Black frames.  With maxTraceDepth < 0 the call adds +0 for each sample.
+ * Nothing a frame supports is refused: mono and stereo, DOF, long generators and Cube / CSG scenes all take this path.
+ * The host entry copies accum in only when sample_first > 0 (or when the call renders a subset of the buckets, with rgb and noise, so that the
+ *   other pixels keep their values) and copies accum, rgb and noise out.  The _device entry takes DEVICE pointers -- d_accum 16-byte aligned, the
+ *   others 4-byte aligned -- and follows frayhip_render_device's stream contract.
+ * FRAYHIP_E_ARG, before the device is touched, with the entry's name in frayhip_last_error(): a NULL scene, frame, request or accum; mode !=
+ *   FRAYHIP_MODE_RENDER; sample_first < 0, sample_count < 1, or their sum past the bound above; bucket arguments that frayhip_render refuses;
+ *   a NaN preview_ms; an output overlapping accum or another output; a misaligned device pointer; a call on a scene whose frame is being
+ *   rendered. */
+#define FRAYHIP_ACCUM_CHANNELS 4   /* per pixel, row-major: sum.r, sum.g, sum.b, m2 -- one 16-byte row */
+typedef struct frayhip_samples {
+    int32_t sample_first;    /* in:  index of the first sample to render, >= 0                        */
+    int32_t sample_count;    /* in:  how many, >= 1                                                   */
+    int32_t samples_done;    /* out: samples per pixel the state holds after the call                 */
+    int32_t _pad;
+} frayhip_samples;
+
+int  frayhip_render_samples(frayhip_scene* s, const frayhip_frame* f, frayhip_samples* r, const frayhip_progressive* p,
+                            float* accum, float* rgb, float* noise, frayhip_stats* st);
+int  frayhip_render_samples_device(frayhip_scene* s, const frayhip_frame* f, frayhip_samples* r, const frayhip_progressive* p,
+                                   float* d_accum, float* d_rgb, float* d_noise, void* hip_stream, frayhip_stats* st);
 
 /* ---- feature frames (first-hit guides for a denoiser) ---------------------------------------------------------------------------------------
  * For every pixel of the call's buckets (frame.bucket_first / bucket_stride, as frayhip_render; other pixels untouched), the FP32 mean, in
