@@ -16,31 +16,13 @@
 #include "entry_support.hpp"
 #include "dev_rng.hpp"
 #include "dev_pack.hpp"
+#include "scene_arena.hpp"
 
 namespace {
 
 using frayhip_detail::set_error;
 
-// One device allocation holding every read-only table of a scene.
-struct Arena {
-    std::vector<unsigned char> host;
-    size_t add(const void* p, size_t bytes, size_t align = 256)
-    {
-        size_t off = (host.size() + align - 1) / align * align;
-        host.resize(off + bytes);
-        if (bytes) memcpy(host.data() + off, p, bytes);
-        return off;
-    }
-};
-
 void put3(double* o, const double* p) { o[0] = p[0]; o[1] = p[1]; o[2] = p[2]; }
-void putX(DXform& X, const frayhip_transform& T)
-{
-    put3(X.off, T.offset);
-    memcpy(X.m, T.m, sizeof X.m);
-    memcpy(X.inv, T.invM, sizeof X.inv);
-}
-
 }  // namespace
 
 namespace frayhip_detail {
@@ -368,20 +350,6 @@ namespace {
 using frayhip_detail::kStatsBytes;
 using frayhip_detail::grid_for;
 
-bool shader_uses_uv(const frayhip_scene_desc& d, int s, int depth = 0)
-{
-    if (s < 0 || s >= d.n_shaders || depth > 40) return false;
-    const frayhip_shader& sh = d.shaders[s];
-    auto texUV = [&](int t) { return t >= 0 && t < d.n_textures && d.textures[t].kind != FRAYHIP_TEX_FRESNEL; };
-    if (texUV(sh.texture)) return true;
-    if (sh.kind == FRAYHIP_SHADER_LAYERED)
-        for (int i = 0; i < sh.layer_count; i++) {
-            const frayhip_layer& L = d.layers[sh.layer_begin + i];
-            if (texUV(L.texture) || shader_uses_uv(d, L.shader, depth + 1)) return true;
-        }
-    return false;
-}
-
 bool create_lanes(frayhip_scene* sc)
 {
     if (hipEventCreateWithFlags(&sc->evLaneStart, hipEventDisableTiming) != hipSuccess) return false;
@@ -525,412 +493,32 @@ int frayhip_scene_create(const frayhip_scene_desc* desc, frayhip_scene** out)
                 return FRAYHIP_E_UNSUPPORTED;
             }
     }
+    // the arena and the scene facts (scene_arena.hpp): built without a device, then placed at the device allocation's addresses and uploaded
+    frayhip_arena::ArenaBuilt B;
+    frayhip_arena::arena_build(d, B);
     frayhip_scene* sc = new frayhip_scene();
-    for (int i = 0; i < d.n_nodes; i++) {
-        int k = d.geoms[d.nodes[i].geom].kind;
-        if (k == FRAYHIP_GEOM_CUBE || k == FRAYHIP_GEOM_CSG) sc->extGeometry = true;   // selects the <ST | 2> kernel variants
-    }
-    Arena A;
-    // nodes
-    std::vector<DNode> nodes(d.n_nodes);
-    for (int i = 0; i < d.n_nodes; i++) {
-        const frayhip_node& n = d.nodes[i];
-        putX(nodes[i].T, n.T);
-        nodes[i].geomKind = d.geoms[n.geom].kind;
-        nodes[i].geomIndex = d.geoms[n.geom].index;
-        nodes[i].shader = n.shader;
-        nodes[i].bumpTex = n.bump_tex;
-        nodes[i].xfClass = i;
-        {
-            static const double I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Z3[3] = {0, 0, 0};       // +0.0 everywhere: a -0.0 in the file's transform is not the identity
-            nodes[i].xfIdentity = (!memcmp(n.T.offset, Z3, sizeof Z3) && !memcmp(n.T.m, I9, sizeof I9) && !memcmp(n.T.invM, I9, sizeof I9)) ? 1 : 0;
-        }
-        for (int j = 0; j < i; j++)
-            if (!memcmp(d.nodes[j].T.offset, n.T.offset, sizeof n.T.offset) && !memcmp(d.nodes[j].T.invM, n.T.invM, sizeof n.T.invM) &&
-                !memcmp(d.nodes[j].T.m, n.T.m, sizeof n.T.m)) {
-                nodes[i].xfClass = nodes[j].xfClass;
-                break;
-            }
-        int sk = d.shaders[n.shader].kind;
-        if (sk == FRAYHIP_SHADER_REFL || sk == FRAYHIP_SHADER_REFR || sk == FRAYHIP_SHADER_LAYERED) sc->whittedNeedsRecursion = true;
-    }
-    size_t oNodes = A.add(nullptr, 0);                  // filled after the meshes: tree-less nodes hold a device pointer
-    A.host.resize(oNodes + nodes.size() * sizeof(DNode));
-    size_t oNodesX = A.add(nullptr, 0);
-    A.host.resize(oNodesX + nodes.size() * sizeof(DNodeX));
-    size_t oGates = A.add(nullptr, 0);                  // the path tracer's scheduling hint (DGate), filled with the nodes
-    A.host.resize(oGates + FRAY_MAX_GATES * sizeof(DGate));
-    size_t oSegPlanes = A.add(nullptr, 0);              // the planes shadow segments are certified against (dev_segcert.hpp), filled with the nodes
-    A.host.resize(oSegPlanes + FRAY_SEG_MAX_PLANES * sizeof(DSegPlane));
-    size_t oSegMasks = A.add(nullptr, 0);
-    A.host.resize(oSegMasks + FRAY_SEG_MAX_NODES * sizeof(uint32_t));
-    std::vector<DPlane> planes(d.n_planes);
-    for (int i = 0; i < d.n_planes; i++) { planes[i].limit = d.planes[i].limit; planes[i].height = d.planes[i].height; }
-    size_t oPlanes = A.add(planes.data(), planes.size() * sizeof(DPlane));
-    std::vector<DSphere> spheres(d.n_spheres);
-    for (int i = 0; i < d.n_spheres; i++) { put3(spheres[i].O, d.spheres[i].O); spheres[i].R = d.spheres[i].R; }
-    size_t oSpheres = A.add(spheres.data(), spheres.size() * sizeof(DSphere));
-    std::vector<DCube> cubes(d.n_cubes);
-    for (int i = 0; i < d.n_cubes; i++) { put3(cubes[i].O, d.cubes[i].O); cubes[i].halfSide = d.cubes[i].halfSide; }
-    size_t oCubes = A.add(cubes.data(), cubes.size() * sizeof(DCube));
-    std::vector<DCsg> csgs(d.n_csgs);
-    for (int i = 0; i < d.n_csgs; i++) {
-        const frayhip_csg& g = d.csgs[i];
-        csgs[i].op = g.op;
-        csgs[i].leftKind = d.geoms[g.left].kind; csgs[i].leftIndex = d.geoms[g.left].index; csgs[i].leftGeom = g.left;
-        csgs[i].rightKind = d.geoms[g.right].kind; csgs[i].rightIndex = d.geoms[g.right].index; csgs[i].rightGeom = g.right;
-        csgs[i].flat = (csgs[i].leftKind <= FRAYHIP_GEOM_CUBE && csgs[i].rightKind <= FRAYHIP_GEOM_CUBE) ? 1 : 0;
-    }
-    size_t oCsgs = A.add(csgs.data(), csgs.size() * sizeof(DCsg));
-    // meshes
-    std::vector<DMesh> meshes(d.n_meshes);
-    struct MeshOff { size_t tris, attrs, kd, kdBox, refs, ltris, ltris32; };
-    std::vector<MeshOff> moff(d.n_meshes);
-    for (int mi = 0; mi < d.n_meshes; mi++) {
-        const frayhip_mesh& m = d.meshes[mi];
-        DMesh& M = meshes[mi];
-        put3(M.bmin, m.bbox_min);
-        put3(M.bmax, m.bbox_max);
-        M.boxMax = 0;
-        for (int k = 0; k < 3; k++) M.boxMax = std::max(M.boxMax, std::max(std::fabs(m.bbox_min[k]), std::fabs(m.bbox_max[k])));
-        M.nTris = m.n_triangles;
-        M.hasKd = m.has_kd;
-        if (m.has_kd) sc->kdMeshes = true;
-        M.smooth = !(m.faceted || m.n_normals == 0);
-        M.culling = m.backfaceCulling;
-        M.hasUV = m.n_uvs != 0;
-        std::vector<DTri> tris(m.n_triangles);
-        std::vector<DTriAttr> attrs(m.n_triangles);
-        for (int t = 0; t < m.n_triangles; t++) {
-            const frayhip_triangle& T = m.triangles[t];
-            DTri& o = tris[t];
-            put3(o.g, T.gnormal);
-            put3(o.A, m.vertices + 3 * (size_t)T.v[0]);
-            put3(o.N, T.ABcrossAC);
-            put3(o.AC, T.AC);
-            put3(o.AB, T.AB);
-            o.index = t; o.pad = 0;
-            DTriAttr& a = attrs[t];
-            memset(&a, 0, sizeof a);
-            if (M.smooth) {
-                put3(a.nA, m.normals + 3 * (size_t)T.n[0]);
-                put3(a.nB, m.normals + 3 * (size_t)T.n[1]);
-                put3(a.nC, m.normals + 3 * (size_t)T.n[2]);
-            }
-            if (M.hasUV) {
-                const double* tA = m.uvs + 3 * (size_t)T.t[0]; const double* tB = m.uvs + 3 * (size_t)T.t[1]; const double* tC = m.uvs + 3 * (size_t)T.t[2];
-                a.tA[0] = tA[0]; a.tA[1] = tA[1]; a.tB[0] = tB[0]; a.tB[1] = tB[1]; a.tC[0] = tC[0]; a.tC[1] = tC[1];
-            }
-            put3(a.dNdx, T.dNdx);
-            put3(a.dNdy, T.dNdy);
-        }
-        // KD nodes: add each node's own box.  Boxes are derived top-down exactly as BBox::split
-        // does (copy parent, overwrite one coordinate).
-        std::vector<DKd> kd(m.n_kdnodes);
-        std::vector<DKdBox> kdBox(m.n_kdnodes);
-        if (m.n_kdnodes > 0) {
-            for (int k = 0; k < 3; k++) { kdBox[0].lo[k] = m.bbox_min[k]; kdBox[0].hi[k] = m.bbox_max[k]; }
-            for (int n = 0; n < m.n_kdnodes; n++) {   // parents precede children in the array
-                const frayhip_kdnode& K = m.kdnodes[n];
-                DKd& o = kd[n];
-                o.child0 = K.child0; o.meta = K.axis;
-                if (K.axis != 3) {
-                    o.split = K.split;
-                    o.meta |= (m.kdnodes[K.child0].axis == 3 ? 4 : 0) | (m.kdnodes[K.child0 + 1].axis == 3 ? 8 : 0);
-                    kdBox[K.child0] = kdBox[n];
-                    kdBox[K.child0 + 1] = kdBox[n];
-                    kdBox[K.child0].hi[K.axis] = K.split;
-                    kdBox[K.child0 + 1].lo[K.axis] = K.split;
-                } else {
-                    o.triBegin = K.tri_begin; o.triCount = K.tri_count;
-                }
-            }
-        }
-        moff[mi].tris = A.add(tris.data(), tris.size() * sizeof(DTri));
-        moff[mi].attrs = A.add(attrs.data(), attrs.size() * sizeof(DTriAttr));
-        moff[mi].kd = A.add(kd.data(), kd.size() * sizeof(DKd));
-        moff[mi].kdBox = A.add(kdBox.data(), kdBox.size() * sizeof(DKdBox));
-        moff[mi].refs = A.add(m.trirefs, (size_t)m.n_trirefs * sizeof(int32_t));
-        std::vector<DTri> ltris((size_t)m.n_trirefs);
-        for (int r = 0; r < m.n_trirefs; r++) ltris[r] = tris[m.trirefs[r]];
-        moff[mi].ltris = A.add(ltris.data(), ltris.size() * sizeof(DTri));
-        // the same leaf order again as FP32 records of the certified filter (dev_tricert.hpp), relative to the centre of the mesh's box
-        for (int k = 0; k < 3; k++) M.ref[k] = (m.bbox_min[k] + m.bbox_max[k]) * 0.5;
-        std::vector<DTri32> l32(ltris.size());
-        for (size_t r = 0; r < ltris.size(); r++) tricert_make(l32[r], ltris[r].A, ltris[r].AB, ltris[r].AC, ltris[r].N, M.ref);
-        moff[mi].ltris32 = A.add(l32.data(), l32.size() * sizeof(DTri32));
-    }
-    size_t oTexels = A.add(d.texels, (size_t)d.n_texels * sizeof(float));
-    std::vector<DTexture> tex(d.n_textures);
-    for (int i = 0; i < d.n_textures; i++) {
-        const frayhip_texture& t = d.textures[i];
-        DTexture& o = tex[i];
-        o.kind = t.kind; o.width = t.width; o.height = t.height; o.pad = 0;
-        memcpy(o.color1, t.color1, sizeof o.color1);
-        memcpy(o.color2, t.color2, sizeof o.color2);
-        o.scaling = t.scaling; o.bumpIntensity = t.bumpIntensity; o.ior = t.ior;
-        o.texels = nullptr;   // patched below
-    }
-    std::vector<DShader> shaders(d.n_shaders);
-    for (int i = 0; i < d.n_shaders; i++) {
-        const frayhip_shader& s = d.shaders[i];
-        DShader& o = shaders[i];
-        o.kind = s.kind; o.texture = s.texture;
-        memcpy(o.color, s.color, sizeof o.color);
-        memcpy(o.specularColor, s.specularColor, sizeof o.specularColor);
-        memcpy(o.mult, s.mult, sizeof o.mult);
-        o.numSamples = s.numSamples;
-        o.exponent = s.exponent; o.specularMultiplier = s.specularMultiplier; o.glossiness = s.glossiness;
-        o.deflectionScaling = s.deflectionScaling; o.ior = s.ior;
-        o.layerBegin = s.layer_begin; o.layerCount = s.layer_count;
-        o.usesUV = shader_uses_uv(d, i);
-        o.pad = 0;
-    }
-    size_t oShaders = A.add(shaders.data(), shaders.size() * sizeof(DShader));
-    std::vector<DLayer> layers(d.n_layers);
-    for (int i = 0; i < d.n_layers; i++) {
-        layers[i].shader = d.layers[i].shader; layers[i].texture = d.layers[i].texture;
-        memcpy(layers[i].opacity, d.layers[i].opacity, sizeof layers[i].opacity);
-        layers[i].pad = 0;
-    }
-    size_t oLayers = A.add(layers.data(), layers.size() * sizeof(DLayer));
-    std::vector<DLight> lights(d.n_lights);
-    bool anyLightDraws = false;
-    for (int i = 0; i < d.n_lights; i++) {
-        const frayhip_light& l = d.lights[i];
-        DLight& o = lights[i];
-        o.kind = l.kind; o.xSubd = l.xSubd; o.ySubd = l.ySubd; o.pad = 0;
-        memcpy(o.color, l.color, sizeof o.color);
-        o.power = l.power;
-        put3(o.pos, l.pos);
-        putX(o.T, l.T);
-        put3(o.center, l.center);
-        o.area = l.area;
-        sc->lightSampleCount += l.kind == FRAYHIP_LIGHT_RECT ? l.xSubd * l.ySubd : 1;
-        if (l.kind == FRAYHIP_LIGHT_RECT) sc->lightDraws = true;
-        if (l.kind == FRAYHIP_LIGHT_RECT) anyLightDraws = true;          // RectLight::getNthSample draws two words per sample (lights.cpp:62-63)
-        o.areaXsize = 1.0 / l.xSubd;
-        o.areaYsize = 1.0 / l.ySubd;
-    }
-    // glossy fans may be drawn ahead (dev_whitted.hpp) where nothing under them is likely to draw: no light that samples, a fan of eight or more
-    sc->specFanMax = 0;
-    if (!anyLightDraws)
-        for (int i = 0; i < d.n_shaders; i++)
-            if (d.shaders[i].kind == FRAYHIP_SHADER_REFL && d.shaders[i].glossiness != 1.0 && d.shaders[i].numSamples >= 8)
-                sc->specFanMax = std::max(sc->specFanMax, (int)d.shaders[i].numSamples);
-    size_t oLights = A.add(lights.data(), lights.size() * sizeof(DLight));
-    size_t oMeshes = A.add(nullptr, 0);              // reserve aligned slots for the tables that hold device pointers
-    A.host.resize(oMeshes + meshes.size() * sizeof(DMesh));
-    size_t oTex = A.add(nullptr, 0);
-    A.host.resize(oTex + tex.size() * sizeof(DTexture));
-
-    if (hipMalloc(&sc->d_arena, A.host.size() ? A.host.size() : 256) != hipSuccess) {
+    sc->extGeometry = B.F.extGeometry != 0;
+    sc->kdMeshes = B.F.kdMeshes != 0;
+    sc->textured = B.F.textured != 0;
+    sc->whittedNeedsRecursion = B.F.whittedNeedsRecursion != 0;
+    sc->lightDraws = B.F.lightDraws != 0;
+    sc->lightSampleCount = B.F.lightSampleCount;
+    sc->specFanMax = B.F.specFanMax;
+    if (hipMalloc(&sc->d_arena, B.host.size() ? B.host.size() : 256) != hipSuccess) {
         set_error("frayhip_scene_create: hipMalloc failed (no device?)");
         delete sc;
         return FRAYHIP_E_NODEVICE;
     }
-    unsigned char* base = (unsigned char*)sc->d_arena;
-    for (int mi = 0; mi < d.n_meshes; mi++) {
-        meshes[mi].tris = (const FRAY_RO DTri*)(base + moff[mi].tris);
-        meshes[mi].attrs = (const FRAY_RO DTriAttr*)(base + moff[mi].attrs);
-        meshes[mi].kd = (const FRAY_RO DKd*)(base + moff[mi].kd);
-        meshes[mi].kdBox = (const FRAY_RO DKdBox*)(base + moff[mi].kdBox);
-        meshes[mi].refs = (const FRAY_RO int32_t*)(base + moff[mi].refs);
-        meshes[mi].ltris = (const FRAY_RO DTri*)(base + moff[mi].ltris);
-        meshes[mi].ltris32 = (const FRAY_RO DTri32*)(base + moff[mi].ltris32);
-    }
-    if (!meshes.empty()) memcpy(A.host.data() + oMeshes, meshes.data(), meshes.size() * sizeof(DMesh));
-    std::vector<DNodeX> nodesX(nodes.size());
-    for (int i = 0; i < d.n_nodes; i++) {
-        DNode& N = nodes[i];
-        DNodeX& X = nodesX[i];
-        N.tlTris = 0; N.tlCulling = 0; N.tlPtr = nullptr; N.boxMax = 0; N.gated = 0; N.segNode = 0;
-        for (int k = 0; k < 3; k++) N.bmin[k] = N.bmax[k] = X.bminE[k] = X.bmaxE[k] = 0;
-        if (N.geomKind == FRAYHIP_GEOM_MESH && !meshes[N.geomIndex].hasKd) {
-            const DMesh& M = meshes[N.geomIndex];
-            N.tlTris = M.nTris; N.tlCulling = M.culling; N.tlPtr = M.tris;
-            put3(N.bmin, M.bmin); put3(N.bmax, M.bmax);
-            N.boxMax = M.boxMax;
-            for (int k = 0; k < 3; k++) { X.bminE[k] = N.bmin[k] - 1e-6; X.bmaxE[k] = N.bmax[k] + 1e-6; }
-        }
-    }
-    // Bounds of a geometry tree in its own (local) space: every point an intersection of the tree can lie on.  Plus: both operands; Minus: the left one
-    // (a ray that has no intersection with the left operand is never inside the difference); And: either operand alone bounds the result, the smaller
-    // box is taken.  A Plane operand makes its tree unbounded (ok = false) unless the operator hides it.
-    struct GB { bool ok; double lo[3], hi[3]; };
-    std::function<GB(int, int)> bounds = [&](int g, int depth) -> GB {
-        GB b{true, {0, 0, 0}, {0, 0, 0}};
-        if (g < 0 || g >= d.n_geoms || depth > FRAY_CSG_DEPTH + 1) { b.ok = false; return b; }
-        const int kind = d.geoms[g].kind, idx = d.geoms[g].index;
-        if (kind == FRAYHIP_GEOM_PLANE) {
-            // never bounded here: Plane::intersect divides 0 by 0 for a horizontal ray that starts at the plane's height and then reports a hit at NaN
-            // (geometry.cpp:35-41: no comparison with NaN is true), wherever the ray is -- no box holds that
-            b.ok = false; return b;
-        } else if (kind == FRAYHIP_GEOM_SPHERE) {
-            for (int k = 0; k < 3; k++) { b.lo[k] = d.spheres[idx].O[k] - std::fabs(d.spheres[idx].R); b.hi[k] = d.spheres[idx].O[k] + std::fabs(d.spheres[idx].R); }
-        } else if (kind == FRAYHIP_GEOM_CUBE) {
-            for (int k = 0; k < 3; k++) { b.lo[k] = d.cubes[idx].O[k] - std::fabs(d.cubes[idx].halfSide); b.hi[k] = d.cubes[idx].O[k] + std::fabs(d.cubes[idx].halfSide); }
-        } else if (kind == FRAYHIP_GEOM_MESH) {
-            for (int k = 0; k < 3; k++) { b.lo[k] = d.meshes[idx].bbox_min[k]; b.hi[k] = d.meshes[idx].bbox_max[k]; }
-        } else if (kind == FRAYHIP_GEOM_CSG) {
-            const frayhip_csg& C = d.csgs[idx];
-            const GB L = bounds(C.left, depth + 1), R = bounds(C.right, depth + 1);
-            auto vol = [](const GB& q) { return (q.hi[0] - q.lo[0]) * (q.hi[1] - q.lo[1]) * (q.hi[2] - q.lo[2]); };
-            if (C.op == FRAYHIP_CSG_MINUS) return L;
-            if (C.op == FRAYHIP_CSG_AND) { if (L.ok && R.ok) return vol(L) <= vol(R) ? L : R; return L.ok ? L : R; }
-            if (!L.ok || !R.ok) { b.ok = false; return b; }
-            for (int k = 0; k < 3; k++) { b.lo[k] = std::min(L.lo[k], R.lo[k]); b.hi[k] = std::max(L.hi[k], R.hi[k]); }
-        } else b.ok = false;
-        for (int k = 0; k < 3; k++) if (!(std::isfinite(b.lo[k]) && std::isfinite(b.hi[k]) && b.lo[k] <= b.hi[k])) b.ok = false;
-        return b;
-    };
-    std::vector<GB> csgLocal(d.n_nodes, GB{false, {0, 0, 0}, {0, 0, 0}});
-    for (int i = 0; i < d.n_nodes; i++) {
-        DNodeX& X = nodesX[i];
-        for (int k = 0; k < 3; k++) X.cc[k] = X.ch[k] = 0;
-        X.cM = 0; X.csgBox = 0; X.padX = 0;
-        if (nodes[i].geomKind != FRAYHIP_GEOM_CSG) continue;
-        const GB b = bounds(d.nodes[i].geom, 0);
-        if (!b.ok) continue;
-        csgLocal[i] = b;
-        for (int k = 0; k < 3; k++) {
-            X.cc[k] = 0.5 * (b.lo[k] + b.hi[k]);
-            X.ch[k] = std::max(b.hi[k] - X.cc[k], X.cc[k] - b.lo[k]) * (1.0 + 1e-12) + 1e-5;       // the true extents and dev_misscert.hpp's constant margin
-            X.cM = std::max(X.cM, std::fabs(X.cc[k]) + X.ch[k]);
-        }
-        X.csgBox = X.cM < 1e9 ? 1 : 0;
-    }
-    // Nodes a next-event segment may skip by the planes of their triangles (dev_segcert.hpp): untransformed meshes without a KD-tree and too small for a gate,
-    // every triangle with finite, bounded coordinates and a normal that is not (nearly) zero.  Triangles whose N and fl(N . A) are equal bit for bit share a
-    // plane entry (a planar quad is one plane).  A scene that would need more entries or nodes than the tables hold gets none.
-    int nSegPlanes = 0, nSegNodes = 0;
     {
-        DSegPlane planes[FRAY_SEG_MAX_PLANES];
-        double planeAmax[FRAY_SEG_MAX_PLANES];
-        uint32_t masks[FRAY_SEG_MAX_NODES];
-        int segNodeOf[FRAY_SEG_MAX_NODES];
-        bool fits = true;
-        for (int i = 0; i < d.n_nodes && fits; i++) {
-            const DNode& N = nodes[i];
-            if (!(N.tlTris > 0 && N.tlTris < FRAY_GATE_MIN_TRIS && N.xfIdentity)) continue;
-            const frayhip_mesh& m = d.meshes[N.geomIndex];
-            bool ok = true;
-            for (int t = 0; t < m.n_triangles && ok; t++) ok = segcert_triangle_ok(m.triangles[t].ABcrossAC, m.vertices + 3 * (size_t)m.triangles[t].v[0]);
-            if (!ok) continue;
-            if (nSegNodes == FRAY_SEG_MAX_NODES) { fits = false; break; }
-            uint32_t mask = 0;
-            for (int t = 0; t < m.n_triangles; t++) {
-                const double* TN = m.triangles[t].ABcrossAC;
-                const double* TA = m.vertices + 3 * (size_t)m.triangles[t].v[0];
-                const double k = segcert_offset(TN, TA), am = std::max(std::fabs(TA[0]), std::max(std::fabs(TA[1]), std::fabs(TA[2])));
-                int p = 0;
-                while (p < nSegPlanes && (memcmp(planes[p].N, TN, 3 * sizeof(double)) != 0 || memcmp(&planes[p].k, &k, sizeof k) != 0)) p++;
-                if (p == nSegPlanes) {
-                    if (nSegPlanes == FRAY_SEG_MAX_PLANES) { fits = false; break; }
-                    memcpy(planes[p].N, TN, 3 * sizeof(double)); planes[p].k = k; planeAmax[p] = 0;
-                    nSegPlanes++;
-                }
-                planeAmax[p] = std::max(planeAmax[p], am);
-                mask |= 1u << p;
-            }
-            if (!fits) break;
-            segNodeOf[nSegNodes] = i;
-            masks[nSegNodes++] = mask;
-        }
-        if (!fits) nSegPlanes = nSegNodes = 0;
-        for (int p = 0; p < nSegPlanes; p++) { const DSegPlane q = planes[p]; segcert_make(planes[p], q.N, q.k, planeAmax[p]); }
-        for (int j = 0; j < nSegNodes; j++) nodes[segNodeOf[j]].segNode = j + 1;
-        if (nSegPlanes) memcpy(A.host.data() + oSegPlanes, planes, (size_t)nSegPlanes * sizeof(DSegPlane));
-        if (nSegNodes) memcpy(A.host.data() + oSegMasks, masks, (size_t)nSegNodes * sizeof(uint32_t));
+        unsigned char* const base = (unsigned char*)sc->d_arena;
+        std::vector<unsigned char*> stage(B.tables.size());
+        std::vector<const unsigned char*> addr(B.tables.size());
+        for (size_t t = 0; t < B.tables.size(); t++) { stage[t] = B.host.data() + B.tables[t].off; addr[t] = base + B.tables[t].off; }
+        frayhip_arena::arena_place(B.F, B.meshTables.data(), B.texelOffset.data(), stage.data(), addr.data(), sc->S);
     }
-    if (!nodes.empty()) memcpy(A.host.data() + oNodes, nodes.data(), nodes.size() * sizeof(DNode));
-    if (!nodesX.empty()) memcpy(A.host.data() + oNodesX, nodesX.data(), nodesX.size() * sizeof(DNodeX));
-    // gates: world-space boxes of the meshes whose brute-force triangle loops are worth skipping for a whole wave (dev_scene.hpp DGate):
-    // the eight corners of the mesh's box through the node's transform (Transform::transformPoint, matrix.cpp:137-146), a hair wider
-    int nGates = 0;
-    bool gatesExact = false;
-    {
-        DGate gates[FRAY_MAX_GATES];
-        int gateNode[FRAY_MAX_GATES];
-        // ... and of the CsgOp nodes whose tree is bounded (their machine is the most expensive thing a ray can enter), unless the box is so large
-        // against the others that nearly every ray enters it anyway (a floor slab): larger than 30 times the smallest such box in some extent
-        double smallest = 1e300;
-        for (int i = 0; i < d.n_nodes; i++)
-            if (csgLocal[i].ok) for (int k = 0; k < 3; k++) smallest = std::min(smallest, std::max(csgLocal[i].hi[k] - csgLocal[i].lo[k], 1e-9));
-        for (int i = 0; i < d.n_nodes && nGates < FRAY_MAX_GATES; i++) {
-            const DNode& N = nodes[i];
-            double bmin[3], bmax[3];
-            if (N.tlTris >= FRAY_GATE_MIN_TRIS) { put3(bmin, N.bmin); put3(bmax, N.bmax); }
-            else if (csgLocal[i].ok) {
-                bool huge = false;
-                for (int k = 0; k < 3; k++) { bmin[k] = csgLocal[i].lo[k]; bmax[k] = csgLocal[i].hi[k]; huge = huge || bmax[k] - bmin[k] > 30.0 * smallest; }
-                if (huge) continue;
-            } else continue;
-            DGate g;
-            for (int k = 0; k < 3; k++) { g.lo[k] = 1e300; g.hi[k] = -1e300; }
-            for (int c = 0; c < 8; c++) {
-                const double p[3] = {c & 1 ? bmax[0] : bmin[0], c & 2 ? bmax[1] : bmin[1], c & 4 ? bmax[2] : bmin[2]};
-                for (int k = 0; k < 3; k++) {
-                    const double w = p[0] * N.T.m[k] + p[1] * N.T.m[3 + k] + p[2] * N.T.m[6 + k] + N.T.off[k];
-                    g.lo[k] = std::min(g.lo[k], w); g.hi[k] = std::max(g.hi[k], w);
-                }
-            }
-            // an untransformed node: the box is the geometry's own, in the space the reference tests it in -- the producers' FP32 certificate applies
-            g.exact = N.xfIdentity ? 1 : 0;
-            g.Mf = 0;
-            for (int k = 0; k < 3; k++) {
-                const double c = 0.5 * (bmin[k] + bmax[k]), half = std::max(bmax[k] - c, c - bmin[k]);
-                g.cf[k] = (float)c;
-                g.hf[k] = std::nextafterf((float)(half * (1.0 + 1e-12) + 1e-5 + std::fabs(c - (double)g.cf[k])), INFINITY);
-                g.Mf = std::max(g.Mf, std::nextafterf(std::fabs(g.cf[k]) + g.hf[k], INFINITY));
-            }
-            if (!(g.Mf < 1e9f)) g.exact = 0;
-            for (int k = 0; k < 3; k++) { const double e = 1e-6 * (1.0 + std::fabs(g.lo[k]) + std::fabs(g.hi[k])); g.lo[k] -= e; g.hi[k] += e; }
-            gateNode[nGates] = i;
-            gates[nGates++] = g;
-        }
-        gatesExact = nGates > 0;
-        for (int q = 0; q < nGates; q++) gatesExact = gatesExact && gates[q].exact;
-        if (gatesExact) {
-            for (int q = 0; q < nGates; q++) nodes[gateNode[q]].gated = 1;
-            memcpy(A.host.data() + oNodes, nodes.data(), nodes.size() * sizeof(DNode));        // (the nodes were copied before the gates were known)
-        }
-        if (nGates) memcpy(A.host.data() + oGates, gates, (size_t)nGates * sizeof(DGate));
-    }
-    for (int i = 0; i < d.n_textures; i++) tex[i].texels = (const FRAY_RO float*)(base + oTexels) + d.textures[i].texel_offset;
-    if (!tex.empty()) memcpy(A.host.data() + oTex, tex.data(), tex.size() * sizeof(DTexture));
-    hipError_t e = hipMemcpy(sc->d_arena, A.host.data(), A.host.size(), hipMemcpyHostToDevice);
+    hipError_t e = hipMemcpy(sc->d_arena, B.host.data(), B.host.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) { set_error(std::string("frayhip_scene_create: upload failed: ") + hipGetErrorString(e)); (void)hipFree(sc->d_arena); delete sc; return FRAYHIP_E_NODEVICE; }
-    sc->arena_bytes = A.host.size();
-
-    DScene& S = sc->S;
-    S.nodes = (const FRAY_RO DNode*)(base + oNodes);
-    S.nodesX = (const FRAY_RO DNodeX*)(base + oNodesX);
-    S.gates = (const FRAY_RO DGate*)(base + oGates);
-    S.nGates = nGates; S.gatesExact = gatesExact ? 1 : 0;
-    S.segPlanes = (const FRAY_RO DSegPlane*)(base + oSegPlanes);
-    S.segNodeMasks = (const FRAY_RO uint32_t*)(base + oSegMasks);
-    S.nSegPlanes = nSegPlanes; S.nSegNodes = nSegNodes;
-    S.planes = (const FRAY_RO DPlane*)(base + oPlanes);
-    S.spheres = (const FRAY_RO DSphere*)(base + oSpheres);
-    S.cubes = (const FRAY_RO DCube*)(base + oCubes);
-    S.csgs = (const FRAY_RO DCsg*)(base + oCsgs);
-    S.meshes = (const FRAY_RO DMesh*)(base + oMeshes);
-    S.shaders = (const FRAY_RO DShader*)(base + oShaders);
-    S.layers = (const FRAY_RO DLayer*)(base + oLayers);
-    S.textures = (const FRAY_RO DTexture*)(base + oTex);
-    S.lights = (const FRAY_RO DLight*)(base + oLights);
-    S.env.present = d.environment.present;
-    if (d.n_textures > 0 || (d.environment.present && d.environment.loaded)) sc->textured = true;
-    S.env.loaded = d.environment.loaded;
-    for (int f = 0; f < 6; f++) {
-        S.env.width[f] = d.environment.width[f];
-        S.env.height[f] = d.environment.height[f];
-        S.env.face[f] = (const FRAY_RO float*)(base + oTexels) + d.environment.texel_offset[f];
-    }
-    S.nNodes = d.n_nodes;
-    S.nLights = d.n_lights;
-    S.probPickLight = d.n_lights > 0 ? 1.0f / (float)d.n_lights : 0.0f;
+    sc->arena_bytes = B.host.size();
     sc->camera = d.camera;
     sc->settings = d.settings;
     // [0] everything but k_pt_shadow, [1] k_pt_shadow
