@@ -8,6 +8,9 @@ src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --he
                                                                                           with its first-hit features; --features-out alone saves them)
                          python -m fray_amd scene.fray -o out.bmp --denoise --frames N [--yaw-step DEG]   (N frames with temporal accumulation, the scene
                                                                                           file's camera turned by DEG per frame: out_0000.bmp ...)
+                         python -m fray_amd scene.fray -o out.bmp --frames N --move NODE DX DY DZ [--move ...] [--denoise]   (N frames of one uploaded
+                                                                                          scene, node NODE moved by (DX, DY, DZ) more in each: frame k sees it
+                                                                                          at k times that; plain frames unless --denoise)
                          python -m fray_amd scene.fray -o out.bmp --accumulate FILE.npz [--spp N] [--noise-out FILE.npy] [--time-limit SECONDS]
                                                                                          (N more samples per pixel on top of the state in FILE.npz, which
                                                                                           is started when it does not exist; the picture of all of them)"""
@@ -19,7 +22,7 @@ import time
 
 import numpy as np
 
-from . import Accumulation, Scene, abi, lib
+from . import Accumulation, Scene, Transform, abi, lib
 
 
 def build_parser():
@@ -54,8 +57,12 @@ def build_parser():
     ap.add_argument("--frames", type=int, metavar="N",
                     help="with --denoise: render N frames with temporal accumulation (Scene.render_sequence; frame k has seed SEED + k) and write "
                          "OUTPUT's name with _0000, _0001, ... before the extension")
-    ap.add_argument("--yaw-step", type=float, default=1.0, metavar="DEG",
-                    help="with --frames: frame k sees the scene file's camera with its yaw turned by k * DEG degrees (default 1)")
+    ap.add_argument("--yaw-step", type=float, default=None, metavar="DEG",
+                    help="with --frames: frame k sees the scene file's camera with its yaw turned by k * DEG degrees (default 1; 0 with --move)")
+    ap.add_argument("--move", type=float, nargs=4, action="append", metavar=("NODE", "DX", "DY", "DZ"),
+                    help="with --frames: translate node NODE (its index among the scene's nodes) by (DX, DY, DZ) more in every frame -- frame 0 is the "
+                         "scene file's, frame k sees the node k steps on; the uploaded scene is edited in place (Scene.update).  May be repeated.  "
+                         "Without --denoise the frames are plain frames of the edited scene, all with seed SEED")
     ap.add_argument("--accumulate", metavar="FILE.npz",
                     help="resumable frame (Scene.render_samples): continue the state saved in FILE.npz by --spp more samples per pixel (default: the "
                          "scene's own count), or start it when the file does not exist; writes FILE.npz and the picture of all samples so far.  A "
@@ -79,14 +86,28 @@ def orbit(camera, frames, yaw_step):
         yield c
 
 
+def move_nodes(s, moves):
+    """One step of --move: every named node's transform translated by its (DX, DY, DZ), and the uploaded scene updated."""
+    for node, dx, dy, dz in moves:
+        Transform(s.nodes[int(node)]).translate(dx, dy, dz).store(s.nodes[int(node)])
+    s.update()
+
+
 def check_args(ap, a):
     """Refuses combinations the CLI does not render (before the scene is loaded)."""
     if a.denoise and a.adaptive is not None:
         ap.error("--denoise cannot be combined with --adaptive: denoising adaptive frames is not supported")
     if a.denoise and a.time_limit is not None:
         ap.error("--denoise cannot be combined with --time-limit: the denoiser needs the whole frame")
-    if a.frames is not None and not a.denoise:
+    if a.frames is not None and not a.denoise and not a.move:
         ap.error("--frames needs --denoise: a sequence is rendered with temporal accumulation and the filter")
+    if a.move and a.frames is None:
+        ap.error("--move needs --frames")
+    if a.move and (a.adaptive is not None or a.accumulate or a.probe or a.time_limit is not None):
+        ap.error("--move cannot be combined with --adaptive, --accumulate, --probe or --time-limit")
+    for m in a.move or []:
+        if m[0] != int(m[0]) or m[0] < 0:
+            ap.error("--move: NODE must be a node index, got %r" % m[0])
     if a.frames is not None and a.frames < 1:
         ap.error("--frames must be >= 1")
     if a.frames is not None and a.features_out:
@@ -148,12 +169,33 @@ def main(argv=None):
             s.settings.numPaths = a.spp
         elif s.camera.dof:
             s.camera.numDOFSamples = a.spp
+    for m in a.move or []:
+        if int(m[0]) >= s.desc.n_nodes:
+            ap.error("--move: the scene has %d nodes, no node %d" % (s.desc.n_nodes, int(m[0])))
+    if a.yaw_step is None:
+        a.yaw_step = 0.0 if a.move else 1.0
     state = load_accumulation(ap, a, s) if a.accumulate else None
     s.beginRender(a.device)
     if a.probe:
         print(json.dumps(probe(s, a.probe[0], a.probe[1], a.shade, a.seed)))
         return 0
     t0 = time.time()
+    if a.frames is not None and not a.denoise:
+        # plain frames of the edited scene: the sequence of --move without the filter
+        for k, cam in enumerate(orbit(abi.Camera.from_buffer_copy(s.camera), a.frames, a.yaw_step)):
+            if k:
+                move_nodes(s, a.move)
+            s.camera.yaw = cam.yaw
+            s.beginFrame()
+            img, st = s.render(seed=a.seed)
+            path = sequence_path(a.output, k)
+            if lib.frayhip_save_bmp(path.encode(), img.ctypes.data, img.shape[1], img.shape[0]):
+                print(lib.frayhip_last_error().decode(), file=sys.stderr)
+                return 1
+            print("frame %d: yaw %+.2f, frame %.1f ms (kernels), scene update %d bytes; wrote %s"
+                  % (k, k * a.yaw_step, st["ms_kernels"], s.get_option("scene_update_bytes"), path), flush=True)
+        print("Rendered %d frames in %.2fs" % (a.frames, time.time() - t0))
+        return 0
     if a.frames is not None:
         start = abi.Camera.from_buffer_copy(s.camera)
         for k, (img, _raw, info) in enumerate(s.render_sequence(orbit(start, a.frames, a.yaw_step), seed=a.seed, feature_samples=a.feature_samples)):
@@ -165,6 +207,8 @@ def main(argv=None):
             print("frame %d: yaw %+.2f, frame %.1f ms, features %.1f ms, accumulation %.2f ms, filter %.2f ms (kernels); wrote %s"
                   % (k, k * a.yaw_step, info["render"]["ms_kernels"], info["features"]["ms_kernels"], info["temporal"]["ms_kernels"],
                      info["denoise"]["ms_kernels"], path), flush=True)
+            if a.move and k + 1 < a.frames:
+                move_nodes(s, a.move)           # the generator renders the next frame when it is asked for it: after this edit
         print("Rendered %d frames in %.2fs" % (a.frames, time.time() - t0))
         return 0
     if a.denoise:

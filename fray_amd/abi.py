@@ -220,6 +220,13 @@ SYMBOLS = {
     "frayhip_scene_create": (C.c_int, [P(SceneDesc), P(VP)]),
     "frayhip_scene_destroy": (None, [VP]),
     "frayhip_scene_set_view": (C.c_int, [VP, P(Camera), P(Settings)]),
+    "frayhip_scene_update": (C.c_int, [VP, P(SceneDesc)]),
+    "frayhip_transform_identity": (C.c_int, [P(Transform)]),
+    "frayhip_transform_scale": (C.c_int, [P(Transform), f64, f64, f64]),
+    "frayhip_transform_rotate": (C.c_int, [P(Transform), f64, f64, f64]),
+    "frayhip_transform_translate": (C.c_int, [P(Transform), f64, f64, f64]),
+    "frayhip_light_begin_frame": (C.c_int, [P(Light)]),
+    "frayhip_shader_begin_frame": (C.c_int, [P(Shader)]),
     "frayhip_scene_set_option": (C.c_int, [VP, C.c_char_p, i64]),
     "frayhip_scene_get_option": (C.c_int, [VP, C.c_char_p, P(i64)]),
     "frayhip_render": (C.c_int, [VP, P(Frame), VP, VP, VP, P(Stats)]),

@@ -345,6 +345,26 @@ frayhip_stats finish_stats(frayhip_scene* sc, const DStats* blocks, int nBlocks,
 
 }  // namespace frayhip_detail
 
+// What frayhip_scene_update needs of a scene after its description is gone (include/frayhip.h "scene edits").  Of the arena as built: the table
+// list, the facts, and a host copy of the tables arena_update writes or reads -- the editable tables, the DMesh table and the triangle records of the
+// meshes whose planes the segment-plane tables are made from (detail::arena_keeps_tris: tree-less, fewer than FRAY_GATE_MIN_TRIS triangles) -- packed back
+// to back: nothing whose size grows with a large mesh or with the texel pool.  Of the description: its fixed part, to compare an update's with.
+struct SceneEdit {
+    frayhip_arena::ArenaFacts F;
+    std::vector<frayhip_arena::ArenaTable> tables;
+    std::vector<frayhip_arena::ArenaMeshTables> meshTables;
+    std::vector<int64_t> texelOffset;
+    std::vector<unsigned char> host;
+    std::vector<int64_t> hostOff;             // per table: where it starts in `host`, -1 for a table that is not kept
+    int32_t counts[11];
+    int64_t nTexels;
+    std::vector<frayhip_geom_ref> geoms;
+    std::vector<frayhip_csg> csgs;
+    std::vector<frayhip_mesh> meshes;         // header scalars; the array pointers are never read
+    std::vector<frayhip_texture> textures;    // kind, width, height, texel_offset
+    frayhip_environment environment;
+};
+
 namespace {
 
 using frayhip_detail::kStatsBytes;
@@ -358,6 +378,34 @@ bool create_lanes(frayhip_scene* sc)
         if (hipEventCreateWithFlags(&sc->evResolved[k], hipEventDisableTiming) != hipSuccess) return false;
     }
     return true;
+}
+
+// The range checks of the EDITABLE part of a description (include/frayhip.h, frayhip_scene_update): layers, shaders, nodes and lights against the
+// element counts.  One copy, for frayhip_scene_create (inside validate_desc) and for frayhip_scene_update.
+std::string validate_editable(const frayhip_scene_desc& d, const char* who)
+{
+    auto bad = [](const char* who, const char* what, long long i) { return std::string(who) + ": " + what + " (element " + std::to_string(i) + ")"; };
+    for (int i = 0; i < d.n_layers; i++) {
+        const frayhip_layer& L = d.layers[i];
+        if (L.shader < 0 || L.shader >= d.n_shaders || L.texture < -1 || L.texture >= d.n_textures) return bad(who, "layer reference out of range", i);
+    }
+    for (int i = 0; i < d.n_shaders; i++) {
+        const frayhip_shader& sh = d.shaders[i];
+        if (sh.kind < 0 || sh.kind > 5) return bad(who, "unknown shader kind", i);
+        if (sh.texture < -1 || sh.texture >= d.n_textures) return bad(who, "shader texture out of range", i);
+        if (sh.kind == FRAYHIP_SHADER_LAYERED && (sh.layer_begin < 0 || sh.layer_count < 0 || (int64_t)sh.layer_begin + sh.layer_count > d.n_layers)) return bad(who, "layer range out of bounds", i);
+        if (sh.kind == FRAYHIP_SHADER_REFL && sh.numSamples < 0) return bad(who, "negative numSamples", i);
+    }
+    for (int i = 0; i < d.n_nodes; i++) {
+        const frayhip_node& n = d.nodes[i];
+        if (n.geom < 0 || n.geom >= d.n_geoms || n.shader < 0 || n.shader >= d.n_shaders || n.bump_tex < -1 || n.bump_tex >= d.n_textures) return bad(who, "node reference out of range", i);
+    }
+    for (int i = 0; i < d.n_lights; i++) {
+        const frayhip_light& L = d.lights[i];
+        if (L.kind < 0 || L.kind > 1) return bad(who, "unknown light kind", i);
+        if (L.kind == FRAYHIP_LIGHT_RECT && (L.xSubd <= 0 || L.ySubd <= 0 || (int64_t)L.xSubd * L.ySubd > (1 << 20))) return bad(who, "bad RectLight subdivision", i);
+    }
+    return std::string();
 }
 
 // A description can come from any host, not only from frayhip_scene_parse: every
@@ -391,25 +439,9 @@ std::string validate_desc(const frayhip_scene_desc& d)
         if ((t.kind == FRAYHIP_TEX_BITMAP || t.kind == FRAYHIP_TEX_BUMP) && (t.width <= 0 || t.height <= 0)) return bad("bitmap texture without texels", i);   // the lookup wraps modulo width / height
         if ((t.kind == FRAYHIP_TEX_BITMAP || t.kind == FRAYHIP_TEX_BUMP) && !texel_range_ok(t.texel_offset, t.width, t.height)) return bad("texture texels outside the pool", i);
     }
-    for (int i = 0; i < d.n_layers; i++) {
-        const frayhip_layer& L = d.layers[i];
-        if (L.shader < 0 || L.shader >= d.n_shaders || L.texture < -1 || L.texture >= d.n_textures) return bad("layer reference out of range", i);
-    }
-    for (int i = 0; i < d.n_shaders; i++) {
-        const frayhip_shader& sh = d.shaders[i];
-        if (sh.kind < 0 || sh.kind > 5) return bad("unknown shader kind", i);
-        if (sh.texture < -1 || sh.texture >= d.n_textures) return bad("shader texture out of range", i);
-        if (sh.kind == FRAYHIP_SHADER_LAYERED && (sh.layer_begin < 0 || sh.layer_count < 0 || (int64_t)sh.layer_begin + sh.layer_count > d.n_layers)) return bad("layer range out of bounds", i);
-        if (sh.kind == FRAYHIP_SHADER_REFL && sh.numSamples < 0) return bad("negative numSamples", i);
-    }
-    for (int i = 0; i < d.n_nodes; i++) {
-        const frayhip_node& n = d.nodes[i];
-        if (n.geom < 0 || n.geom >= d.n_geoms || n.shader < 0 || n.shader >= d.n_shaders || n.bump_tex < -1 || n.bump_tex >= d.n_textures) return bad("node reference out of range", i);
-    }
-    for (int i = 0; i < d.n_lights; i++) {
-        const frayhip_light& L = d.lights[i];
-        if (L.kind < 0 || L.kind > 1) return bad("unknown light kind", i);
-        if (L.kind == FRAYHIP_LIGHT_RECT && (L.xSubd <= 0 || L.ySubd <= 0 || (int64_t)L.xSubd * L.ySubd > (1 << 20))) return bad("bad RectLight subdivision", i);
+    {
+        const std::string why = validate_editable(d, "frayhip_scene_create");
+        if (!why.empty()) return why;
     }
     if (d.environment.present && d.environment.loaded)
         for (int f = 0; f < 6; f++)
@@ -449,6 +481,76 @@ std::string validate_desc(const frayhip_scene_desc& d)
     }
     if (d.settings.frameWidth <= 0 || d.settings.frameHeight <= 0) return "frayhip_scene_create: bad frame size";
     return std::string();
+}
+
+void desc_counts(const frayhip_scene_desc& d, int32_t out[11])
+{
+    const int32_t counts[11] = {d.n_nodes, d.n_geoms, d.n_planes, d.n_spheres, d.n_cubes, d.n_csgs, d.n_meshes, d.n_shaders, d.n_layers, d.n_textures, d.n_lights};
+    memcpy(out, counts, sizeof counts);
+}
+
+// frayhip_scene_create: keeps what an update needs.  B is the arena as uploaded (placed).
+SceneEdit* make_scene_edit(const frayhip_scene_desc& d, const frayhip_arena::ArenaBuilt& B)
+{
+    SceneEdit* E = new SceneEdit();
+    E->F = B.F; E->tables = B.tables; E->meshTables = B.meshTables; E->texelOffset = B.texelOffset;
+    E->hostOff.assign(B.tables.size(), -1);
+    std::vector<int32_t> keep = frayhip_arena::arena_editable_tables(B.F);
+    keep.push_back(B.F.tMeshes);
+    const DMesh* const meshes = (const DMesh*)(B.host.data() + B.tables[B.F.tMeshes].off);
+    for (int mi = 0; mi < B.F.nMeshes; mi++)
+        if (frayhip_arena::detail::arena_keeps_tris(meshes[mi])) keep.push_back(B.meshTables[mi].tris);
+    size_t bytes = 0;
+    for (int32_t t : keep) { E->hostOff[t] = (int64_t)bytes; bytes += (B.tables[t].bytes + 15) / 16 * 16; }
+    E->host.resize(bytes);
+    for (int32_t t : keep) if (B.tables[t].bytes) memcpy(E->host.data() + E->hostOff[t], B.host.data() + B.tables[t].off, B.tables[t].bytes);
+    desc_counts(d, E->counts);
+    E->nTexels = d.n_texels;
+    E->geoms.assign(d.geoms, d.geoms + d.n_geoms);
+    E->csgs.assign(d.csgs, d.csgs + d.n_csgs);
+    E->meshes.assign(d.meshes, d.meshes + d.n_meshes);
+    E->textures.assign(d.textures, d.textures + d.n_textures);
+    E->environment = d.environment;
+    return E;
+}
+
+// The fixed part of an update's description against the one the scene was created from; the name of the first table that differs, or nullptr.
+const char* fixed_part_differs(const SceneEdit& E, const frayhip_scene_desc& d)
+{
+    int32_t counts[11];
+    desc_counts(d, counts);
+    if (memcmp(counts, E.counts, sizeof counts) != 0 || d.n_texels != E.nTexels) return "an element count";
+    const void* arrays[] = {d.nodes, d.geoms, d.planes, d.spheres, d.cubes, d.csgs, d.meshes, d.shaders, d.layers, d.textures, d.lights};
+    for (int k = 0; k < 11; k++) if (counts[k] > 0 && !arrays[k]) return "a null array with a non-zero count";
+    for (int i = 0; i < d.n_geoms; i++) if (d.geoms[i].kind != E.geoms[i].kind || d.geoms[i].index != E.geoms[i].index) return "geoms[]";
+    for (int i = 0; i < d.n_csgs; i++) if (d.csgs[i].op != E.csgs[i].op || d.csgs[i].left != E.csgs[i].left || d.csgs[i].right != E.csgs[i].right) return "csgs[]";
+    for (int i = 0; i < d.n_meshes; i++) {
+        const frayhip_mesh &a = d.meshes[i], &b = E.meshes[i];
+        if (a.n_vertices != b.n_vertices || a.n_normals != b.n_normals || a.n_uvs != b.n_uvs || a.n_triangles != b.n_triangles || a.n_kdnodes != b.n_kdnodes ||
+            a.n_trirefs != b.n_trirefs || a.faceted != b.faceted || a.backfaceCulling != b.backfaceCulling || a.has_kd != b.has_kd ||
+            a.kd_max_depth != b.kd_max_depth || a.kd_depth_sum != b.kd_depth_sum ||
+            memcmp(a.bbox_min, b.bbox_min, sizeof a.bbox_min) != 0 || memcmp(a.bbox_max, b.bbox_max, sizeof a.bbox_max) != 0) return "meshes[] (a mesh header)";
+    }
+    for (int i = 0; i < d.n_textures; i++) {
+        const frayhip_texture &a = d.textures[i], &b = E.textures[i];
+        if (a.kind != b.kind || a.width != b.width || a.height != b.height || a.texel_offset != b.texel_offset) return "textures[] (kind, width, height or texel_offset)";
+    }
+    const frayhip_environment &a = d.environment, &b = E.environment;
+    if (a.present != b.present || a.loaded != b.loaded || memcmp(a.width, b.width, sizeof a.width) != 0 || memcmp(a.height, b.height, sizeof a.height) != 0 ||
+        memcmp(a.texel_offset, b.texel_offset, sizeof a.texel_offset) != 0) return "environment";
+    return nullptr;
+}
+
+// every field frayhip_scene_create and frayhip_scene_update take from the arena's facts
+void commit_facts(frayhip_scene* sc, const frayhip_arena::ArenaFacts& F)
+{
+    sc->extGeometry = F.extGeometry != 0;
+    sc->kdMeshes = F.kdMeshes != 0;
+    sc->textured = F.textured != 0;
+    sc->whittedNeedsRecursion = F.whittedNeedsRecursion != 0;
+    sc->lightDraws = F.lightDraws != 0;
+    sc->lightSampleCount = F.lightSampleCount;
+    sc->specFanMax = F.specFanMax;
 }
 
 }  // namespace
@@ -497,13 +599,7 @@ int frayhip_scene_create(const frayhip_scene_desc* desc, frayhip_scene** out)
     frayhip_arena::ArenaBuilt B;
     frayhip_arena::arena_build(d, B);
     frayhip_scene* sc = new frayhip_scene();
-    sc->extGeometry = B.F.extGeometry != 0;
-    sc->kdMeshes = B.F.kdMeshes != 0;
-    sc->textured = B.F.textured != 0;
-    sc->whittedNeedsRecursion = B.F.whittedNeedsRecursion != 0;
-    sc->lightDraws = B.F.lightDraws != 0;
-    sc->lightSampleCount = B.F.lightSampleCount;
-    sc->specFanMax = B.F.specFanMax;
+    commit_facts(sc, B.F);
     if (hipMalloc(&sc->d_arena, B.host.size() ? B.host.size() : 256) != hipSuccess) {
         set_error("frayhip_scene_create: hipMalloc failed (no device?)");
         delete sc;
@@ -519,6 +615,7 @@ int frayhip_scene_create(const frayhip_scene_desc* desc, frayhip_scene** out)
     hipError_t e = hipMemcpy(sc->d_arena, B.host.data(), B.host.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) { set_error(std::string("frayhip_scene_create: upload failed: ") + hipGetErrorString(e)); (void)hipFree(sc->d_arena); delete sc; return FRAYHIP_E_NODEVICE; }
     sc->arena_bytes = B.host.size();
+    sc->edit = make_scene_edit(d, B);
     sc->camera = d.camera;
     sc->settings = d.settings;
     // [0] everything but k_pt_shadow, [1] k_pt_shadow
@@ -564,6 +661,9 @@ int frayhip_scene_get_option(frayhip_scene* s, const char* name, int64_t* value)
     else if (n == "whitted_path") *value = s->lastWhittedPath;
     else if (n == "fused_whitted_max") *value = s->fusedWhittedMax;
     else if (n == "pt_budget_effective_mib") *value = (int64_t)(frayhip_detail::work_budget(s) >> 20);
+    else if (n == "scene_updates") *value = s->sceneUpdates;
+    else if (n == "scene_update_bytes") *value = s->sceneUpdateBytes;
+    else if (n == "arena_bytes") *value = (int64_t)s->arena_bytes;
     else if (n == "fans_filed") *value = s->lastFans[0];
     else if (n == "fan_children") *value = s->lastFans[1];
     else if (n == "fan_children_looked_up") *value = s->lastFans[2];
@@ -620,9 +720,52 @@ int frayhip_scene_set_view(frayhip_scene* s, const frayhip_camera* camera, const
     return FRAYHIP_OK;
 }
 
+int frayhip_scene_update(frayhip_scene* s, const frayhip_scene_desc* desc)
+{
+    if (!s || !desc) { set_error("frayhip_scene_update: null argument"); return FRAYHIP_E_ARG; }
+    if (s->rendering) { set_error("frayhip_scene_update: the scene is rendering a frame"); return FRAYHIP_E_ARG; }
+    if (desc->abi_version != FRAYHIP_ABI_VERSION) { set_error("frayhip_scene_update: ABI version mismatch"); return FRAYHIP_E_ARG; }
+    const frayhip_scene_desc& d = *desc;
+    SceneEdit& E = *s->edit;
+    if (const char* what = fixed_part_differs(E, d)) {
+        set_error(std::string("frayhip_scene_update: ") + what + " differs from the description the scene was created from (only nodes, primitives, shaders, layers, lights and texture parameters can be edited)");
+        return FRAYHIP_E_ARG;
+    }
+    {
+        const std::string why = validate_editable(d, "frayhip_scene_update");
+        if (!why.empty()) { set_error(why); return FRAYHIP_E_ARG; }
+    }
+    // the new tables, built beside the kept ones: nothing of the handle changes before the upload
+    std::vector<unsigned char> next(E.host);
+    frayhip_arena::ArenaFacts F = E.F;
+    std::vector<unsigned char*> tab(E.tables.size());
+    std::vector<const unsigned char*> addr(E.tables.size());
+    for (size_t t = 0; t < E.tables.size(); t++) {
+        tab[t] = E.hostOff[t] >= 0 ? next.data() + E.hostOff[t] : nullptr;
+        addr[t] = (const unsigned char*)s->d_arena + E.tables[t].off;
+    }
+    frayhip_arena::arena_update(d, E.meshTables.data(), F, tab.data());
+    DScene S = s->S;
+    frayhip_arena::arena_place(F, E.meshTables.data(), E.texelOffset.data(), tab.data(), addr.data(), S);
+    long long bytes = 0;
+    for (int32_t t : frayhip_arena::arena_editable_tables(F)) {
+        if (!E.tables[t].bytes) continue;
+        HIP_TRY(hipMemcpy((unsigned char*)s->d_arena + E.tables[t].off, tab[t], E.tables[t].bytes, hipMemcpyHostToDevice));
+        bytes += (long long)E.tables[t].bytes;
+    }
+    E.host.swap(next);
+    E.F = F;
+    commit_facts(s, F);
+    s->S = S;
+    s->sceneUpdates++;
+    s->sceneUpdateBytes = bytes;
+    return FRAYHIP_OK;
+}
+
 void frayhip_scene_destroy(frayhip_scene* s)
 {
     if (!s) return;
+    delete s->edit;
     if (s->d_arena) (void)hipFree(s->d_arena);
     if (s->d_work) (void)hipFree(s->d_work);
     frayhip_detail::seed_table_free(s);

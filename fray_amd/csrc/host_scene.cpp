@@ -138,6 +138,13 @@ struct Xform {   // Transform, matrix.h:72-98
         inv = mat_inverse(m);
     }
     void translate(double x, double y, double z) { off[0] += x; off[1] += y; off[2] += z; }
+    static Xform load(const frayhip_transform& T)
+    {
+        Xform X;
+        for (int i = 0; i < 3; i++) X.off[i] = T.offset[i];
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { X.m.a[i][j] = T.m[i * 3 + j]; X.inv.a[i][j] = T.invM[i * 3 + j]; }
+        return X;
+    }
     void store(frayhip_transform& T) const
     {
         for (int i = 0; i < 3; i++) T.offset[i] = off[i];
@@ -148,6 +155,24 @@ struct Xform {   // Transform, matrix.h:72-98
         for (int j = 0; j < 3; j++) out[j] = (p[0] * m.a[0][j] + p[1] * m.a[1][j] + p[2] * m.a[2][j]) + off[j];
     }
 };
+
+// RectLight::beginFrame (lights.cpp:37-46) on the light's stored transform: the parser's and frayhip_light_begin_frame's one copy
+void light_begin_frame(frayhip_light& L)
+{
+    for (int k = 0; k < 3; k++) L.center[k] = 0;
+    L.area = 0;
+    if (L.kind != FRAYHIP_LIGHT_RECT) return;
+    const Xform T = Xform::load(L.T);
+    const double o[3] = {0, 0, 0}, pa[3] = {-0.5, 0, -0.5}, pb[3] = {0.5, 0, -0.5}, pc[3] = {0.5, 0, 0.5};
+    double a[3], bb[3], c[3];
+    T.point(o, L.center); T.point(pa, a); T.point(pb, bb); T.point(pc, c);
+    double d1[3] = {bb[0] - a[0], bb[1] - a[1], bb[2] - a[2]}, d2[3] = {bb[0] - c[0], bb[1] - c[1], bb[2] - c[2]};
+    float width = (float)sqrt(d1[0] * d1[0] + d1[1] * d1[1] + d1[2] * d1[2]);
+    float height = (float)sqrt(d2[0] * d2[0] + d2[1] * d2[1] + d2[2] * d2[2]);
+    L.area = width * height;     // float product widened to double, as in the reference
+}
+// Reflection::beginFrame (shading.h:197-201)
+void shader_begin_frame(frayhip_shader& s) { s.deflectionScaling = pow(10.0, 2 - 4 * s.glossiness); }
 
 // ---- block model ------------------------------------------------------------------------------
 struct PropLine { int line; std::string name, value; bool used = false; };
@@ -499,15 +524,9 @@ struct Loader {
             b.getInt("xSubd", L.xSubd, 1);
             b.getInt("ySubd", L.ySubd, 1);
             b.getTransform(T);
-            const double o[3] = {0, 0, 0}, pa[3] = {-0.5, 0, -0.5}, pb[3] = {0.5, 0, -0.5}, pc[3] = {0.5, 0, 0.5};
-            double a[3], bb[3], c[3];
-            T.point(o, L.center); T.point(pa, a); T.point(pb, bb); T.point(pc, c);
-            double d1[3] = {bb[0] - a[0], bb[1] - a[1], bb[2] - a[2]}, d2[3] = {bb[0] - c[0], bb[1] - c[1], bb[2] - c[2]};
-            float width = (float)sqrt(d1[0] * d1[0] + d1[1] * d1[1] + d1[2] * d1[2]);
-            float height = (float)sqrt(d2[0] * d2[0] + d2[1] * d2[1] + d2[2] * d2[2]);
-            L.area = width * height;     // float product widened to double, as in the reference
         }
         T.store(L.T);
+        light_begin_frame(L);
         hs->lights.push_back(L);
     }
     void fillGeometry(Block& b, int sub)
@@ -680,8 +699,7 @@ struct Loader {
                 if (s.layer_count < 32) { hs->layers.push_back(L); s.layer_count++; }   // Layer layers[32]
             }
         }
-        // Reflection::beginFrame (shading.h:197-201)
-        s.deflectionScaling = pow(10.0, 2 - 4 * s.glossiness);
+        shader_begin_frame(s);
         hs->shaders[b.index] = s;
     }
     struct NodeTmp { frayhip_node n; bool hasShader; };
@@ -755,6 +773,16 @@ struct Loader {
     }
 };
 
+// the bodies of frayhip_transform_* / frayhip_light_begin_frame / frayhip_shader_begin_frame (include/frayhip.h), on the parser's own Xform
+template <class F> int edit_transform(frayhip_transform* T, F f)
+{
+    if (!T) return FRAYHIP_E_ARG;
+    Xform X = Xform::load(*T);
+    f(X);
+    X.store(*T);
+    return FRAYHIP_OK;
+}
+
 }  // namespace
 
 void HostScene::finalize()
@@ -809,3 +837,13 @@ HostScene* parse_scene_file(const char* path, std::string& err)
 }
 
 }  // namespace frayhost
+
+// include/frayhip.h "scene edits": the helpers a caller fills frayhip_transform and the derived fields with
+extern "C" {
+int frayhip_transform_identity(frayhip_transform* T) { return frayhost::edit_transform(T, [](frayhost::Xform& X) { X = frayhost::Xform(); }); }
+int frayhip_transform_scale(frayhip_transform* T, double x, double y, double z) { return frayhost::edit_transform(T, [&](frayhost::Xform& X) { X.scale(x, y, z); }); }
+int frayhip_transform_rotate(frayhip_transform* T, double yaw, double pitch, double roll) { return frayhost::edit_transform(T, [&](frayhost::Xform& X) { X.rotate(yaw, pitch, roll); }); }
+int frayhip_transform_translate(frayhip_transform* T, double x, double y, double z) { return frayhost::edit_transform(T, [&](frayhost::Xform& X) { X.translate(x, y, z); }); }
+int frayhip_light_begin_frame(frayhip_light* light) { if (!light) return FRAYHIP_E_ARG; frayhost::light_begin_frame(*light); return FRAYHIP_OK; }
+int frayhip_shader_begin_frame(frayhip_shader* shader) { if (!shader) return FRAYHIP_E_ARG; frayhost::shader_begin_frame(*shader); return FRAYHIP_OK; }
+}

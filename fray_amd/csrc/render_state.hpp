@@ -58,9 +58,13 @@ struct SeedTable {
     bool serving = false;             // the frame being rendered takes its seeds from the table
 };
 
+struct SceneEdit;                     // capi.hip: what frayhip_scene_update needs of the arena as built, and the fixed tables of the description to compare with
+
 struct frayhip_scene {
     void* d_arena = nullptr;
     size_t arena_bytes = 0;
+    SceneEdit* edit = nullptr;
+    long long sceneUpdates = 0, sceneUpdateBytes = 0;   // frayhip_scene_update calls since creation and the bytes the last one uploaded (get_option "scene_updates", "scene_update_bytes")
     DScene S{};
     frayhip_camera camera{};
     frayhip_settings settings{};

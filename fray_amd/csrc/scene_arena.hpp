@@ -2,6 +2,8 @@
 //
 //   arena_build   description -> the arena's bytes with every inner pointer still null, the list of its tables (one per block, in the
 //                 order they were laid out) and the scene facts that choose kernels (ArenaFacts);
+//   arena_update  the editable part of an edited description (include/frayhip.h, frayhip_scene_update) written again into an arena built earlier: the
+//                 tables whose size no mesh and no texel decides, by the very code arena_build filled them with, and the facts that follow;
 //   arena_place   given, for every table, where it can be written now and where it will live, writes the inner pointers (a mesh's arrays,
 //                 a tree-less node's triangles, a texture's texels) and fills the DScene.
 //
@@ -91,22 +93,21 @@ inline bool shader_uses_uv(const frayhip_scene_desc& d, int s, int depth = 0)
     return false;
 }
 
-}  // namespace detail
-
-// `d` has passed frayhip_scene_create's validation (every index in range, CSG trees at most FRAY_CSG_DEPTH deep).
-inline void arena_build(const frayhip_scene_desc& d, ArenaBuilt& B)
+// Everything of the arena that the EDITABLE part of a description decides (include/frayhip.h, frayhip_scene_update): the node tables with their gates and
+// segment planes, the primitives, shaders, layers, lights and texture records, and the scene facts that follow from them.  arena_build runs it on the
+// freshly laid out arena and arena_update on an arena built earlier, so an updated arena equals a fresh one byte for byte.  tab[t] is where table t
+// can be written.  Read besides `d`: the DMesh table (the header scalars of every mesh) and the DTri table of every mesh without a KD-tree and with
+// fewer than FRAY_GATE_MIN_TRIS triangles (arena_keeps_tris) -- never a mesh array or the texel pool of `d`.  Every inner pointer is written null
+// (arena_place); the unused tails of the gate and segment-plane tables are zeroed.  F: the t* indices and the counts are read, the editable facts written.
+inline bool arena_keeps_tris(const DMesh& M) { return !M.hasKd && M.nTris > 0 && M.nTris < FRAY_GATE_MIN_TRIS; }
+inline void fill_editable(const frayhip_scene_desc& d, const ArenaMeshTables* meshTables, ArenaFacts& F, unsigned char* const* tab)
 {
-    using detail::put3;
-    using detail::putX;
-    B.host.clear(); B.tables.clear(); B.meshTables.clear(); B.texelOffset.clear();
-    ArenaFacts& F = B.F;
-    memset(&F, 0, sizeof F);
+    const DMesh* const meshes = (const DMesh*)tab[F.tMeshes];
+    F.extGeometry = F.whittedNeedsRecursion = F.lightDraws = F.lightSampleCount = F.specFanMax = 0;
     for (int i = 0; i < d.n_nodes; i++) {
         int k = d.geoms[d.nodes[i].geom].kind;
         if (k == FRAYHIP_GEOM_CUBE || k == FRAYHIP_GEOM_CSG) F.extGeometry = 1;   // selects the <ST | 2> kernel variants
     }
-    detail::Arena A{B.host, B.tables};
-    // nodes
     std::vector<DNode> nodes(d.n_nodes);
     for (int i = 0; i < d.n_nodes; i++) {
         const frayhip_node& n = d.nodes[i];
@@ -129,27 +130,261 @@ inline void arena_build(const frayhip_scene_desc& d, ArenaBuilt& B)
         int sk = d.shaders[n.shader].kind;
         if (sk == FRAYHIP_SHADER_REFL || sk == FRAYHIP_SHADER_REFR || sk == FRAYHIP_SHADER_LAYERED) F.whittedNeedsRecursion = 1;
     }
-    size_t oNodes = A.reserve(nodes.size() * sizeof(DNode));                  // filled after the meshes: tree-less nodes hold a pointer (arena_place)
-    F.tNodes = A.last();
-    size_t oNodesX = A.reserve(nodes.size() * sizeof(DNodeX));
-    F.tNodesX = A.last();
-    size_t oGates = A.reserve(FRAY_MAX_GATES * sizeof(DGate));                // the path tracer's scheduling hint (DGate), filled with the nodes
-    F.tGates = A.last();
-    size_t oSegPlanes = A.reserve(FRAY_SEG_MAX_PLANES * sizeof(DSegPlane));   // the planes shadow segments are certified against (dev_segcert.hpp), filled with the nodes
-    F.tSegPlanes = A.last();
-    size_t oSegMasks = A.reserve(FRAY_SEG_MAX_NODES * sizeof(uint32_t));
-    F.tSegMasks = A.last();
-    std::vector<DPlane> planes(d.n_planes);
+    DPlane* const planes = (DPlane*)tab[F.tPlanes];
     for (int i = 0; i < d.n_planes; i++) { planes[i].limit = d.planes[i].limit; planes[i].height = d.planes[i].height; }
-    A.add(planes.data(), planes.size() * sizeof(DPlane));
-    F.tPlanes = A.last();
-    std::vector<DSphere> spheres(d.n_spheres);
+    DSphere* const spheres = (DSphere*)tab[F.tSpheres];
     for (int i = 0; i < d.n_spheres; i++) { put3(spheres[i].O, d.spheres[i].O); spheres[i].R = d.spheres[i].R; }
-    A.add(spheres.data(), spheres.size() * sizeof(DSphere));
-    F.tSpheres = A.last();
-    std::vector<DCube> cubes(d.n_cubes);
+    DCube* const cubes = (DCube*)tab[F.tCubes];
     for (int i = 0; i < d.n_cubes; i++) { put3(cubes[i].O, d.cubes[i].O); cubes[i].halfSide = d.cubes[i].halfSide; }
-    A.add(cubes.data(), cubes.size() * sizeof(DCube));
+    std::vector<DTexture> tex(d.n_textures);
+    for (int i = 0; i < d.n_textures; i++) {
+        const frayhip_texture& t = d.textures[i];
+        DTexture& o = tex[i];
+        o.kind = t.kind; o.width = t.width; o.height = t.height; o.pad = 0;
+        memcpy(o.color1, t.color1, sizeof o.color1);
+        memcpy(o.color2, t.color2, sizeof o.color2);
+        o.scaling = t.scaling; o.bumpIntensity = t.bumpIntensity; o.ior = t.ior;
+        o.texels = nullptr;   // arena_place
+    }
+    std::vector<DShader> shaders(d.n_shaders);
+    for (int i = 0; i < d.n_shaders; i++) {
+        const frayhip_shader& s = d.shaders[i];
+        DShader& o = shaders[i];
+        o.kind = s.kind; o.texture = s.texture;
+        memcpy(o.color, s.color, sizeof o.color);
+        memcpy(o.specularColor, s.specularColor, sizeof o.specularColor);
+        memcpy(o.mult, s.mult, sizeof o.mult);
+        o.numSamples = s.numSamples;
+        o.exponent = s.exponent; o.specularMultiplier = s.specularMultiplier; o.glossiness = s.glossiness;
+        o.deflectionScaling = s.deflectionScaling; o.ior = s.ior;
+        o.layerBegin = s.layer_begin; o.layerCount = s.layer_count;
+        o.usesUV = shader_uses_uv(d, i);
+        o.pad = 0;
+    }
+    if (!shaders.empty()) memcpy(tab[F.tShaders], shaders.data(), shaders.size() * sizeof(DShader));
+    std::vector<DLayer> layers(d.n_layers);
+    for (int i = 0; i < d.n_layers; i++) {
+        layers[i].shader = d.layers[i].shader; layers[i].texture = d.layers[i].texture;
+        memcpy(layers[i].opacity, d.layers[i].opacity, sizeof layers[i].opacity);
+        layers[i].pad = 0;
+    }
+    if (!layers.empty()) memcpy(tab[F.tLayers], layers.data(), layers.size() * sizeof(DLayer));
+    std::vector<DLight> lights(d.n_lights);
+    bool anyLightDraws = false;
+    for (int i = 0; i < d.n_lights; i++) {
+        const frayhip_light& l = d.lights[i];
+        DLight& o = lights[i];
+        o.kind = l.kind; o.xSubd = l.xSubd; o.ySubd = l.ySubd; o.pad = 0;
+        memcpy(o.color, l.color, sizeof o.color);
+        o.power = l.power;
+        put3(o.pos, l.pos);
+        putX(o.T, l.T);
+        put3(o.center, l.center);
+        o.area = l.area;
+        F.lightSampleCount += l.kind == FRAYHIP_LIGHT_RECT ? l.xSubd * l.ySubd : 1;
+        if (l.kind == FRAYHIP_LIGHT_RECT) F.lightDraws = 1;
+        if (l.kind == FRAYHIP_LIGHT_RECT) anyLightDraws = true;          // RectLight::getNthSample draws two words per sample (lights.cpp:62-63)
+        o.areaXsize = 1.0 / l.xSubd;
+        o.areaYsize = 1.0 / l.ySubd;
+    }
+    // glossy fans may be drawn ahead (dev_whitted.hpp) where nothing under them is likely to draw: no light that samples, a fan of eight or more
+    F.specFanMax = 0;
+    if (!anyLightDraws)
+        for (int i = 0; i < d.n_shaders; i++)
+            if (d.shaders[i].kind == FRAYHIP_SHADER_REFL && d.shaders[i].glossiness != 1.0 && d.shaders[i].numSamples >= 8)
+                F.specFanMax = std::max(F.specFanMax, (int)d.shaders[i].numSamples);
+    if (!lights.empty()) memcpy(tab[F.tLights], lights.data(), lights.size() * sizeof(DLight));
+    std::vector<DNodeX> nodesX(nodes.size());
+    for (int i = 0; i < d.n_nodes; i++) {
+        DNode& N = nodes[i];
+        DNodeX& X = nodesX[i];
+        N.tlTris = 0; N.tlCulling = 0; N.tlPtr = nullptr; N.boxMax = 0; N.gated = 0; N.segNode = 0;
+        for (int k = 0; k < 3; k++) N.bmin[k] = N.bmax[k] = X.bminE[k] = X.bmaxE[k] = 0;
+        if (N.geomKind == FRAYHIP_GEOM_MESH && !meshes[N.geomIndex].hasKd) {
+            const DMesh& M = meshes[N.geomIndex];
+            N.tlTris = M.nTris; N.tlCulling = M.culling;      // (tlPtr: arena_place)
+            put3(N.bmin, M.bmin); put3(N.bmax, M.bmax);
+            N.boxMax = M.boxMax;
+            for (int k = 0; k < 3; k++) { X.bminE[k] = N.bmin[k] - 1e-6; X.bmaxE[k] = N.bmax[k] + 1e-6; }
+        }
+    }
+    // Bounds of a geometry tree in its own (local) space: every point an intersection of the tree can lie on.  Plus: both operands; Minus: the left one
+    // (a ray that has no intersection with the left operand is never inside the difference); And: either operand alone bounds the result, the smaller
+    // box is taken.  A Plane operand makes its tree unbounded (ok = false) unless the operator hides it.
+    struct GB { bool ok; double lo[3], hi[3]; };
+    std::function<GB(int, int)> bounds = [&](int g, int depth) -> GB {
+        GB b{true, {0, 0, 0}, {0, 0, 0}};
+        if (g < 0 || g >= d.n_geoms || depth > FRAY_CSG_DEPTH + 1) { b.ok = false; return b; }
+        const int kind = d.geoms[g].kind, idx = d.geoms[g].index;
+        if (kind == FRAYHIP_GEOM_PLANE) {
+            // never bounded here: Plane::intersect divides 0 by 0 for a horizontal ray that starts at the plane's height and then reports a hit at NaN
+            // (geometry.cpp:35-41: no comparison with NaN is true), wherever the ray is -- no box holds that
+            b.ok = false; return b;
+        } else if (kind == FRAYHIP_GEOM_SPHERE) {
+            for (int k = 0; k < 3; k++) { b.lo[k] = d.spheres[idx].O[k] - std::fabs(d.spheres[idx].R); b.hi[k] = d.spheres[idx].O[k] + std::fabs(d.spheres[idx].R); }
+        } else if (kind == FRAYHIP_GEOM_CUBE) {
+            for (int k = 0; k < 3; k++) { b.lo[k] = d.cubes[idx].O[k] - std::fabs(d.cubes[idx].halfSide); b.hi[k] = d.cubes[idx].O[k] + std::fabs(d.cubes[idx].halfSide); }
+        } else if (kind == FRAYHIP_GEOM_MESH) {
+            for (int k = 0; k < 3; k++) { b.lo[k] = meshes[idx].bmin[k]; b.hi[k] = meshes[idx].bmax[k]; }
+        } else if (kind == FRAYHIP_GEOM_CSG) {
+            const frayhip_csg& C = d.csgs[idx];
+            const GB L = bounds(C.left, depth + 1), R = bounds(C.right, depth + 1);
+            auto vol = [](const GB& q) { return (q.hi[0] - q.lo[0]) * (q.hi[1] - q.lo[1]) * (q.hi[2] - q.lo[2]); };
+            if (C.op == FRAYHIP_CSG_MINUS) return L;
+            if (C.op == FRAYHIP_CSG_AND) { if (L.ok && R.ok) return vol(L) <= vol(R) ? L : R; return L.ok ? L : R; }
+            if (!L.ok || !R.ok) { b.ok = false; return b; }
+            for (int k = 0; k < 3; k++) { b.lo[k] = std::min(L.lo[k], R.lo[k]); b.hi[k] = std::max(L.hi[k], R.hi[k]); }
+        } else b.ok = false;
+        for (int k = 0; k < 3; k++) if (!(std::isfinite(b.lo[k]) && std::isfinite(b.hi[k]) && b.lo[k] <= b.hi[k])) b.ok = false;
+        return b;
+    };
+    std::vector<GB> csgLocal(d.n_nodes, GB{false, {0, 0, 0}, {0, 0, 0}});
+    for (int i = 0; i < d.n_nodes; i++) {
+        DNodeX& X = nodesX[i];
+        for (int k = 0; k < 3; k++) X.cc[k] = X.ch[k] = 0;
+        X.cM = 0; X.csgBox = 0; X.padX = 0;
+        if (nodes[i].geomKind != FRAYHIP_GEOM_CSG) continue;
+        const GB b = bounds(d.nodes[i].geom, 0);
+        if (!b.ok) continue;
+        csgLocal[i] = b;
+        for (int k = 0; k < 3; k++) {
+            X.cc[k] = 0.5 * (b.lo[k] + b.hi[k]);
+            X.ch[k] = std::max(b.hi[k] - X.cc[k], X.cc[k] - b.lo[k]) * (1.0 + 1e-12) + 1e-5;       // the true extents and dev_misscert.hpp's constant margin
+            X.cM = std::max(X.cM, std::fabs(X.cc[k]) + X.ch[k]);
+        }
+        X.csgBox = X.cM < 1e9 ? 1 : 0;
+    }
+    // Nodes a next-event segment may skip by the planes of their triangles (dev_segcert.hpp): untransformed meshes without a KD-tree and too small for a gate,
+    // every triangle with finite, bounded coordinates and a normal that is not (nearly) zero.  Triangles whose N and fl(N . A) are equal bit for bit share a
+    // plane entry (a planar quad is one plane).  A scene that would need more entries or nodes than the tables hold gets none.
+    int nSegPlanes = 0, nSegNodes = 0;
+    {
+        DSegPlane planes[FRAY_SEG_MAX_PLANES];
+        double planeAmax[FRAY_SEG_MAX_PLANES];
+        uint32_t masks[FRAY_SEG_MAX_NODES];
+        int segNodeOf[FRAY_SEG_MAX_NODES];
+        bool fits = true;
+        for (int i = 0; i < d.n_nodes && fits; i++) {
+            const DNode& N = nodes[i];
+            if (!(N.tlTris > 0 && N.tlTris < FRAY_GATE_MIN_TRIS && N.xfIdentity)) continue;
+            const DTri* const tris = (const DTri*)tab[meshTables[N.geomIndex].tris];      // N = the triangle's ABcrossAC, A = its first vertex (arena_build)
+            bool ok = true;
+            for (int t = 0; t < N.tlTris && ok; t++) ok = segcert_triangle_ok(tris[t].N, tris[t].A);
+            if (!ok) continue;
+            if (nSegNodes == FRAY_SEG_MAX_NODES) { fits = false; break; }
+            uint32_t mask = 0;
+            for (int t = 0; t < N.tlTris; t++) {
+                const double* TN = tris[t].N;
+                const double* TA = tris[t].A;
+                const double k = segcert_offset(TN, TA), am = std::max(std::fabs(TA[0]), std::max(std::fabs(TA[1]), std::fabs(TA[2])));
+                int p = 0;
+                while (p < nSegPlanes && (memcmp(planes[p].N, TN, 3 * sizeof(double)) != 0 || memcmp(&planes[p].k, &k, sizeof k) != 0)) p++;
+                if (p == nSegPlanes) {
+                    if (nSegPlanes == FRAY_SEG_MAX_PLANES) { fits = false; break; }
+                    memcpy(planes[p].N, TN, 3 * sizeof(double)); planes[p].k = k; planeAmax[p] = 0;
+                    nSegPlanes++;
+                }
+                planeAmax[p] = std::max(planeAmax[p], am);
+                mask |= 1u << p;
+            }
+            if (!fits) break;
+            segNodeOf[nSegNodes] = i;
+            masks[nSegNodes++] = mask;
+        }
+        if (!fits) nSegPlanes = nSegNodes = 0;
+        for (int p = 0; p < nSegPlanes; p++) { const DSegPlane q = planes[p]; segcert_make(planes[p], q.N, q.k, planeAmax[p]); }
+        for (int j = 0; j < nSegNodes; j++) nodes[segNodeOf[j]].segNode = j + 1;
+        memset(tab[F.tSegPlanes], 0, FRAY_SEG_MAX_PLANES * sizeof(DSegPlane));
+        memset(tab[F.tSegMasks], 0, FRAY_SEG_MAX_NODES * sizeof(uint32_t));
+        if (nSegPlanes) memcpy(tab[F.tSegPlanes], planes, (size_t)nSegPlanes * sizeof(DSegPlane));
+        if (nSegNodes) memcpy(tab[F.tSegMasks], masks, (size_t)nSegNodes * sizeof(uint32_t));
+    }
+    if (!nodesX.empty()) memcpy(tab[F.tNodesX], nodesX.data(), nodesX.size() * sizeof(DNodeX));
+    // gates: world-space boxes of the meshes whose brute-force triangle loops are worth skipping for a whole wave (dev_scene.hpp DGate):
+    // the eight corners of the mesh's box through the node's transform (Transform::transformPoint, matrix.cpp:137-146), a hair wider
+    int nGates = 0;
+    bool gatesExact = false;
+    {
+        DGate gates[FRAY_MAX_GATES];
+        int gateNode[FRAY_MAX_GATES];
+        // ... and of the CsgOp nodes whose tree is bounded (their machine is the most expensive thing a ray can enter), unless the box is so large
+        // against the others that nearly every ray enters it anyway (a floor slab): larger than 30 times the smallest such box in some extent
+        double smallest = 1e300;
+        for (int i = 0; i < d.n_nodes; i++)
+            if (csgLocal[i].ok) for (int k = 0; k < 3; k++) smallest = std::min(smallest, std::max(csgLocal[i].hi[k] - csgLocal[i].lo[k], 1e-9));
+        for (int i = 0; i < d.n_nodes && nGates < FRAY_MAX_GATES; i++) {
+            const DNode& N = nodes[i];
+            double bmin[3], bmax[3];
+            if (N.tlTris >= FRAY_GATE_MIN_TRIS) { put3(bmin, N.bmin); put3(bmax, N.bmax); }
+            else if (csgLocal[i].ok) {
+                bool huge = false;
+                for (int k = 0; k < 3; k++) { bmin[k] = csgLocal[i].lo[k]; bmax[k] = csgLocal[i].hi[k]; huge = huge || bmax[k] - bmin[k] > 30.0 * smallest; }
+                if (huge) continue;
+            } else continue;
+            DGate g;
+            for (int k = 0; k < 3; k++) { g.lo[k] = 1e300; g.hi[k] = -1e300; }
+            for (int c = 0; c < 8; c++) {
+                const double p[3] = {c & 1 ? bmax[0] : bmin[0], c & 2 ? bmax[1] : bmin[1], c & 4 ? bmax[2] : bmin[2]};
+                for (int k = 0; k < 3; k++) {
+                    const double w = p[0] * N.T.m[k] + p[1] * N.T.m[3 + k] + p[2] * N.T.m[6 + k] + N.T.off[k];
+                    g.lo[k] = std::min(g.lo[k], w); g.hi[k] = std::max(g.hi[k], w);
+                }
+            }
+            // an untransformed node: the box is the geometry's own, in the space the reference tests it in -- the producers' FP32 certificate applies
+            g.exact = N.xfIdentity ? 1 : 0;
+            g.Mf = 0;
+            for (int k = 0; k < 3; k++) {
+                const double c = 0.5 * (bmin[k] + bmax[k]), half = std::max(bmax[k] - c, c - bmin[k]);
+                g.cf[k] = (float)c;
+                g.hf[k] = std::nextafterf((float)(half * (1.0 + 1e-12) + 1e-5 + std::fabs(c - (double)g.cf[k])), INFINITY);
+                g.Mf = std::max(g.Mf, std::nextafterf(std::fabs(g.cf[k]) + g.hf[k], INFINITY));
+            }
+            if (!(g.Mf < 1e9f)) g.exact = 0;
+            for (int k = 0; k < 3; k++) { const double e = 1e-6 * (1.0 + std::fabs(g.lo[k]) + std::fabs(g.hi[k])); g.lo[k] -= e; g.hi[k] += e; }
+            gateNode[nGates] = i;
+            gates[nGates++] = g;
+        }
+        gatesExact = nGates > 0;
+        for (int q = 0; q < nGates; q++) gatesExact = gatesExact && gates[q].exact;
+        if (gatesExact)
+            for (int q = 0; q < nGates; q++) nodes[gateNode[q]].gated = 1;
+        memset(tab[F.tGates], 0, FRAY_MAX_GATES * sizeof(DGate));
+        if (nGates) memcpy(tab[F.tGates], gates, (size_t)nGates * sizeof(DGate));
+    }
+    if (!nodes.empty()) memcpy(tab[F.tNodes], nodes.data(), nodes.size() * sizeof(DNode));
+    if (!tex.empty()) memcpy(tab[F.tTex], tex.data(), tex.size() * sizeof(DTexture));
+
+    F.nGates = nGates; F.gatesExact = gatesExact ? 1 : 0;
+    F.nSegPlanes = nSegPlanes; F.nSegNodes = nSegNodes;
+}
+
+}  // namespace detail
+
+// `d` has passed frayhip_scene_create's validation (every index in range, CSG trees at most FRAY_CSG_DEPTH deep).
+inline void arena_build(const frayhip_scene_desc& d, ArenaBuilt& B)
+{
+    using detail::put3;
+    B.host.clear(); B.tables.clear(); B.meshTables.clear(); B.texelOffset.clear();
+    ArenaFacts& F = B.F;
+    memset(&F, 0, sizeof F);
+    detail::Arena A{B.host, B.tables};
+    // the tables that the editable part of a description decides are laid out here, zero-filled, and written by detail::fill_editable below -- the
+    // function arena_update runs again
+    A.reserve((size_t)d.n_nodes * sizeof(DNode));                             // (tree-less nodes hold a pointer: arena_place)
+    F.tNodes = A.last();
+    A.reserve((size_t)d.n_nodes * sizeof(DNodeX));
+    F.tNodesX = A.last();
+    A.reserve(FRAY_MAX_GATES * sizeof(DGate));                                // the path tracer's scheduling hint (DGate)
+    F.tGates = A.last();
+    A.reserve(FRAY_SEG_MAX_PLANES * sizeof(DSegPlane));                       // the planes shadow segments are certified against (dev_segcert.hpp)
+    F.tSegPlanes = A.last();
+    A.reserve(FRAY_SEG_MAX_NODES * sizeof(uint32_t));
+    F.tSegMasks = A.last();
+    A.reserve((size_t)d.n_planes * sizeof(DPlane));
+    F.tPlanes = A.last();
+    A.reserve((size_t)d.n_spheres * sizeof(DSphere));
+    F.tSpheres = A.last();
+    A.reserve((size_t)d.n_cubes * sizeof(DCube));
     F.tCubes = A.last();
     std::vector<DCsg> csgs(d.n_csgs);
     for (int i = 0; i < d.n_csgs; i++) {
@@ -241,234 +476,20 @@ inline void arena_build(const frayhip_scene_desc& d, ArenaBuilt& B)
     }
     A.add(d.texels, (size_t)d.n_texels * sizeof(float));
     F.tTexels = A.last();
-    std::vector<DTexture> tex(d.n_textures);
     B.texelOffset.resize(d.n_textures);
-    for (int i = 0; i < d.n_textures; i++) {
-        const frayhip_texture& t = d.textures[i];
-        DTexture& o = tex[i];
-        o.kind = t.kind; o.width = t.width; o.height = t.height; o.pad = 0;
-        memcpy(o.color1, t.color1, sizeof o.color1);
-        memcpy(o.color2, t.color2, sizeof o.color2);
-        o.scaling = t.scaling; o.bumpIntensity = t.bumpIntensity; o.ior = t.ior;
-        o.texels = nullptr;   // arena_place
-        B.texelOffset[i] = t.texel_offset;
-    }
-    std::vector<DShader> shaders(d.n_shaders);
-    for (int i = 0; i < d.n_shaders; i++) {
-        const frayhip_shader& s = d.shaders[i];
-        DShader& o = shaders[i];
-        o.kind = s.kind; o.texture = s.texture;
-        memcpy(o.color, s.color, sizeof o.color);
-        memcpy(o.specularColor, s.specularColor, sizeof o.specularColor);
-        memcpy(o.mult, s.mult, sizeof o.mult);
-        o.numSamples = s.numSamples;
-        o.exponent = s.exponent; o.specularMultiplier = s.specularMultiplier; o.glossiness = s.glossiness;
-        o.deflectionScaling = s.deflectionScaling; o.ior = s.ior;
-        o.layerBegin = s.layer_begin; o.layerCount = s.layer_count;
-        o.usesUV = detail::shader_uses_uv(d, i);
-        o.pad = 0;
-    }
-    A.add(shaders.data(), shaders.size() * sizeof(DShader));
+    for (int i = 0; i < d.n_textures; i++) B.texelOffset[i] = d.textures[i].texel_offset;
+    A.reserve((size_t)d.n_shaders * sizeof(DShader));
     F.tShaders = A.last();
-    std::vector<DLayer> layers(d.n_layers);
-    for (int i = 0; i < d.n_layers; i++) {
-        layers[i].shader = d.layers[i].shader; layers[i].texture = d.layers[i].texture;
-        memcpy(layers[i].opacity, d.layers[i].opacity, sizeof layers[i].opacity);
-        layers[i].pad = 0;
-    }
-    A.add(layers.data(), layers.size() * sizeof(DLayer));
+    A.reserve((size_t)d.n_layers * sizeof(DLayer));
     F.tLayers = A.last();
-    std::vector<DLight> lights(d.n_lights);
-    bool anyLightDraws = false;
-    for (int i = 0; i < d.n_lights; i++) {
-        const frayhip_light& l = d.lights[i];
-        DLight& o = lights[i];
-        o.kind = l.kind; o.xSubd = l.xSubd; o.ySubd = l.ySubd; o.pad = 0;
-        memcpy(o.color, l.color, sizeof o.color);
-        o.power = l.power;
-        put3(o.pos, l.pos);
-        putX(o.T, l.T);
-        put3(o.center, l.center);
-        o.area = l.area;
-        F.lightSampleCount += l.kind == FRAYHIP_LIGHT_RECT ? l.xSubd * l.ySubd : 1;
-        if (l.kind == FRAYHIP_LIGHT_RECT) F.lightDraws = 1;
-        if (l.kind == FRAYHIP_LIGHT_RECT) anyLightDraws = true;          // RectLight::getNthSample draws two words per sample (lights.cpp:62-63)
-        o.areaXsize = 1.0 / l.xSubd;
-        o.areaYsize = 1.0 / l.ySubd;
-    }
-    // glossy fans may be drawn ahead (dev_whitted.hpp) where nothing under them is likely to draw: no light that samples, a fan of eight or more
-    F.specFanMax = 0;
-    if (!anyLightDraws)
-        for (int i = 0; i < d.n_shaders; i++)
-            if (d.shaders[i].kind == FRAYHIP_SHADER_REFL && d.shaders[i].glossiness != 1.0 && d.shaders[i].numSamples >= 8)
-                F.specFanMax = std::max(F.specFanMax, (int)d.shaders[i].numSamples);
-    A.add(lights.data(), lights.size() * sizeof(DLight));
+    A.reserve((size_t)d.n_lights * sizeof(DLight));
     F.tLights = A.last();
     size_t oMeshes = A.reserve(meshes.size() * sizeof(DMesh));              // the tables that hold pointers: written here with the pointers null
     F.tMeshes = A.last();
-    size_t oTex = A.reserve(tex.size() * sizeof(DTexture));
+    A.reserve((size_t)d.n_textures * sizeof(DTexture));
     F.tTex = A.last();
-
     if (!meshes.empty()) memcpy(A.host.data() + oMeshes, meshes.data(), meshes.size() * sizeof(DMesh));
-    std::vector<DNodeX> nodesX(nodes.size());
-    for (int i = 0; i < d.n_nodes; i++) {
-        DNode& N = nodes[i];
-        DNodeX& X = nodesX[i];
-        N.tlTris = 0; N.tlCulling = 0; N.tlPtr = nullptr; N.boxMax = 0; N.gated = 0; N.segNode = 0;
-        for (int k = 0; k < 3; k++) N.bmin[k] = N.bmax[k] = X.bminE[k] = X.bmaxE[k] = 0;
-        if (N.geomKind == FRAYHIP_GEOM_MESH && !meshes[N.geomIndex].hasKd) {
-            const DMesh& M = meshes[N.geomIndex];
-            N.tlTris = M.nTris; N.tlCulling = M.culling;      // (tlPtr: arena_place)
-            put3(N.bmin, M.bmin); put3(N.bmax, M.bmax);
-            N.boxMax = M.boxMax;
-            for (int k = 0; k < 3; k++) { X.bminE[k] = N.bmin[k] - 1e-6; X.bmaxE[k] = N.bmax[k] + 1e-6; }
-        }
-    }
-    // Bounds of a geometry tree in its own (local) space: every point an intersection of the tree can lie on.  Plus: both operands; Minus: the left one
-    // (a ray that has no intersection with the left operand is never inside the difference); And: either operand alone bounds the result, the smaller
-    // box is taken.  A Plane operand makes its tree unbounded (ok = false) unless the operator hides it.
-    struct GB { bool ok; double lo[3], hi[3]; };
-    std::function<GB(int, int)> bounds = [&](int g, int depth) -> GB {
-        GB b{true, {0, 0, 0}, {0, 0, 0}};
-        if (g < 0 || g >= d.n_geoms || depth > FRAY_CSG_DEPTH + 1) { b.ok = false; return b; }
-        const int kind = d.geoms[g].kind, idx = d.geoms[g].index;
-        if (kind == FRAYHIP_GEOM_PLANE) {
-            // never bounded here: Plane::intersect divides 0 by 0 for a horizontal ray that starts at the plane's height and then reports a hit at NaN
-            // (geometry.cpp:35-41: no comparison with NaN is true), wherever the ray is -- no box holds that
-            b.ok = false; return b;
-        } else if (kind == FRAYHIP_GEOM_SPHERE) {
-            for (int k = 0; k < 3; k++) { b.lo[k] = d.spheres[idx].O[k] - std::fabs(d.spheres[idx].R); b.hi[k] = d.spheres[idx].O[k] + std::fabs(d.spheres[idx].R); }
-        } else if (kind == FRAYHIP_GEOM_CUBE) {
-            for (int k = 0; k < 3; k++) { b.lo[k] = d.cubes[idx].O[k] - std::fabs(d.cubes[idx].halfSide); b.hi[k] = d.cubes[idx].O[k] + std::fabs(d.cubes[idx].halfSide); }
-        } else if (kind == FRAYHIP_GEOM_MESH) {
-            for (int k = 0; k < 3; k++) { b.lo[k] = d.meshes[idx].bbox_min[k]; b.hi[k] = d.meshes[idx].bbox_max[k]; }
-        } else if (kind == FRAYHIP_GEOM_CSG) {
-            const frayhip_csg& C = d.csgs[idx];
-            const GB L = bounds(C.left, depth + 1), R = bounds(C.right, depth + 1);
-            auto vol = [](const GB& q) { return (q.hi[0] - q.lo[0]) * (q.hi[1] - q.lo[1]) * (q.hi[2] - q.lo[2]); };
-            if (C.op == FRAYHIP_CSG_MINUS) return L;
-            if (C.op == FRAYHIP_CSG_AND) { if (L.ok && R.ok) return vol(L) <= vol(R) ? L : R; return L.ok ? L : R; }
-            if (!L.ok || !R.ok) { b.ok = false; return b; }
-            for (int k = 0; k < 3; k++) { b.lo[k] = std::min(L.lo[k], R.lo[k]); b.hi[k] = std::max(L.hi[k], R.hi[k]); }
-        } else b.ok = false;
-        for (int k = 0; k < 3; k++) if (!(std::isfinite(b.lo[k]) && std::isfinite(b.hi[k]) && b.lo[k] <= b.hi[k])) b.ok = false;
-        return b;
-    };
-    std::vector<GB> csgLocal(d.n_nodes, GB{false, {0, 0, 0}, {0, 0, 0}});
-    for (int i = 0; i < d.n_nodes; i++) {
-        DNodeX& X = nodesX[i];
-        for (int k = 0; k < 3; k++) X.cc[k] = X.ch[k] = 0;
-        X.cM = 0; X.csgBox = 0; X.padX = 0;
-        if (nodes[i].geomKind != FRAYHIP_GEOM_CSG) continue;
-        const GB b = bounds(d.nodes[i].geom, 0);
-        if (!b.ok) continue;
-        csgLocal[i] = b;
-        for (int k = 0; k < 3; k++) {
-            X.cc[k] = 0.5 * (b.lo[k] + b.hi[k]);
-            X.ch[k] = std::max(b.hi[k] - X.cc[k], X.cc[k] - b.lo[k]) * (1.0 + 1e-12) + 1e-5;       // the true extents and dev_misscert.hpp's constant margin
-            X.cM = std::max(X.cM, std::fabs(X.cc[k]) + X.ch[k]);
-        }
-        X.csgBox = X.cM < 1e9 ? 1 : 0;
-    }
-    // Nodes a next-event segment may skip by the planes of their triangles (dev_segcert.hpp): untransformed meshes without a KD-tree and too small for a gate,
-    // every triangle with finite, bounded coordinates and a normal that is not (nearly) zero.  Triangles whose N and fl(N . A) are equal bit for bit share a
-    // plane entry (a planar quad is one plane).  A scene that would need more entries or nodes than the tables hold gets none.
-    int nSegPlanes = 0, nSegNodes = 0;
-    {
-        DSegPlane planes[FRAY_SEG_MAX_PLANES];
-        double planeAmax[FRAY_SEG_MAX_PLANES];
-        uint32_t masks[FRAY_SEG_MAX_NODES];
-        int segNodeOf[FRAY_SEG_MAX_NODES];
-        bool fits = true;
-        for (int i = 0; i < d.n_nodes && fits; i++) {
-            const DNode& N = nodes[i];
-            if (!(N.tlTris > 0 && N.tlTris < FRAY_GATE_MIN_TRIS && N.xfIdentity)) continue;
-            const frayhip_mesh& m = d.meshes[N.geomIndex];
-            bool ok = true;
-            for (int t = 0; t < m.n_triangles && ok; t++) ok = segcert_triangle_ok(m.triangles[t].ABcrossAC, m.vertices + 3 * (size_t)m.triangles[t].v[0]);
-            if (!ok) continue;
-            if (nSegNodes == FRAY_SEG_MAX_NODES) { fits = false; break; }
-            uint32_t mask = 0;
-            for (int t = 0; t < m.n_triangles; t++) {
-                const double* TN = m.triangles[t].ABcrossAC;
-                const double* TA = m.vertices + 3 * (size_t)m.triangles[t].v[0];
-                const double k = segcert_offset(TN, TA), am = std::max(std::fabs(TA[0]), std::max(std::fabs(TA[1]), std::fabs(TA[2])));
-                int p = 0;
-                while (p < nSegPlanes && (memcmp(planes[p].N, TN, 3 * sizeof(double)) != 0 || memcmp(&planes[p].k, &k, sizeof k) != 0)) p++;
-                if (p == nSegPlanes) {
-                    if (nSegPlanes == FRAY_SEG_MAX_PLANES) { fits = false; break; }
-                    memcpy(planes[p].N, TN, 3 * sizeof(double)); planes[p].k = k; planeAmax[p] = 0;
-                    nSegPlanes++;
-                }
-                planeAmax[p] = std::max(planeAmax[p], am);
-                mask |= 1u << p;
-            }
-            if (!fits) break;
-            segNodeOf[nSegNodes] = i;
-            masks[nSegNodes++] = mask;
-        }
-        if (!fits) nSegPlanes = nSegNodes = 0;
-        for (int p = 0; p < nSegPlanes; p++) { const DSegPlane q = planes[p]; segcert_make(planes[p], q.N, q.k, planeAmax[p]); }
-        for (int j = 0; j < nSegNodes; j++) nodes[segNodeOf[j]].segNode = j + 1;
-        if (nSegPlanes) memcpy(A.host.data() + oSegPlanes, planes, (size_t)nSegPlanes * sizeof(DSegPlane));
-        if (nSegNodes) memcpy(A.host.data() + oSegMasks, masks, (size_t)nSegNodes * sizeof(uint32_t));
-    }
-    if (!nodesX.empty()) memcpy(A.host.data() + oNodesX, nodesX.data(), nodesX.size() * sizeof(DNodeX));
-    // gates: world-space boxes of the meshes whose brute-force triangle loops are worth skipping for a whole wave (dev_scene.hpp DGate):
-    // the eight corners of the mesh's box through the node's transform (Transform::transformPoint, matrix.cpp:137-146), a hair wider
-    int nGates = 0;
-    bool gatesExact = false;
-    {
-        DGate gates[FRAY_MAX_GATES];
-        int gateNode[FRAY_MAX_GATES];
-        // ... and of the CsgOp nodes whose tree is bounded (their machine is the most expensive thing a ray can enter), unless the box is so large
-        // against the others that nearly every ray enters it anyway (a floor slab): larger than 30 times the smallest such box in some extent
-        double smallest = 1e300;
-        for (int i = 0; i < d.n_nodes; i++)
-            if (csgLocal[i].ok) for (int k = 0; k < 3; k++) smallest = std::min(smallest, std::max(csgLocal[i].hi[k] - csgLocal[i].lo[k], 1e-9));
-        for (int i = 0; i < d.n_nodes && nGates < FRAY_MAX_GATES; i++) {
-            const DNode& N = nodes[i];
-            double bmin[3], bmax[3];
-            if (N.tlTris >= FRAY_GATE_MIN_TRIS) { put3(bmin, N.bmin); put3(bmax, N.bmax); }
-            else if (csgLocal[i].ok) {
-                bool huge = false;
-                for (int k = 0; k < 3; k++) { bmin[k] = csgLocal[i].lo[k]; bmax[k] = csgLocal[i].hi[k]; huge = huge || bmax[k] - bmin[k] > 30.0 * smallest; }
-                if (huge) continue;
-            } else continue;
-            DGate g;
-            for (int k = 0; k < 3; k++) { g.lo[k] = 1e300; g.hi[k] = -1e300; }
-            for (int c = 0; c < 8; c++) {
-                const double p[3] = {c & 1 ? bmax[0] : bmin[0], c & 2 ? bmax[1] : bmin[1], c & 4 ? bmax[2] : bmin[2]};
-                for (int k = 0; k < 3; k++) {
-                    const double w = p[0] * N.T.m[k] + p[1] * N.T.m[3 + k] + p[2] * N.T.m[6 + k] + N.T.off[k];
-                    g.lo[k] = std::min(g.lo[k], w); g.hi[k] = std::max(g.hi[k], w);
-                }
-            }
-            // an untransformed node: the box is the geometry's own, in the space the reference tests it in -- the producers' FP32 certificate applies
-            g.exact = N.xfIdentity ? 1 : 0;
-            g.Mf = 0;
-            for (int k = 0; k < 3; k++) {
-                const double c = 0.5 * (bmin[k] + bmax[k]), half = std::max(bmax[k] - c, c - bmin[k]);
-                g.cf[k] = (float)c;
-                g.hf[k] = std::nextafterf((float)(half * (1.0 + 1e-12) + 1e-5 + std::fabs(c - (double)g.cf[k])), INFINITY);
-                g.Mf = std::max(g.Mf, std::nextafterf(std::fabs(g.cf[k]) + g.hf[k], INFINITY));
-            }
-            if (!(g.Mf < 1e9f)) g.exact = 0;
-            for (int k = 0; k < 3; k++) { const double e = 1e-6 * (1.0 + std::fabs(g.lo[k]) + std::fabs(g.hi[k])); g.lo[k] -= e; g.hi[k] += e; }
-            gateNode[nGates] = i;
-            gates[nGates++] = g;
-        }
-        gatesExact = nGates > 0;
-        for (int q = 0; q < nGates; q++) gatesExact = gatesExact && gates[q].exact;
-        if (gatesExact)
-            for (int q = 0; q < nGates; q++) nodes[gateNode[q]].gated = 1;
-        if (nGates) memcpy(A.host.data() + oGates, gates, (size_t)nGates * sizeof(DGate));
-    }
-    if (!nodes.empty()) memcpy(A.host.data() + oNodes, nodes.data(), nodes.size() * sizeof(DNode));
-    if (!tex.empty()) memcpy(A.host.data() + oTex, tex.data(), tex.size() * sizeof(DTexture));
 
-    F.nGates = nGates; F.gatesExact = gatesExact ? 1 : 0;
-    F.nSegPlanes = nSegPlanes; F.nSegNodes = nSegNodes;
     F.nNodes = d.n_nodes; F.nLights = d.n_lights; F.nMeshes = d.n_meshes; F.nTextures = d.n_textures;
     F.envPresent = d.environment.present;
     F.envLoaded = d.environment.loaded;
@@ -478,6 +499,29 @@ inline void arena_build(const frayhip_scene_desc& d, ArenaBuilt& B)
         F.envHeight[f] = d.environment.height[f];
         F.envTexelOffset[f] = d.environment.texel_offset[f];
     }
+    std::vector<unsigned char*> tab(B.tables.size());
+    for (size_t t = 0; t < B.tables.size(); t++) tab[t] = B.host.data() + B.tables[t].off;
+    detail::fill_editable(d, B.meshTables.data(), F, tab.data());
+}
+
+// The editable part of `d` written again into an arena built earlier (frayhip_scene_update; `d` has passed its checks: the fixed part is what it was at
+// arena_build, the editable part in range).  tab[t]: where table t can be written -- needed for the tables of arena_editable_tables, and to be read for the
+// DMesh table and the DTri table of every mesh with detail::arena_keeps_tris; the others may be null.  F: the facts of the arena as built, updated in place.
+inline void arena_update(const frayhip_scene_desc& d, const ArenaMeshTables* meshTables, ArenaFacts& F, unsigned char* const* tab)
+{
+    detail::fill_editable(d, meshTables, F, tab);
+}
+// ... on the arena itself, inner pointers null as arena_build left them
+inline void arena_update(const frayhip_scene_desc& d, ArenaBuilt& B)
+{
+    std::vector<unsigned char*> tab(B.tables.size());
+    for (size_t t = 0; t < B.tables.size(); t++) tab[t] = B.host.data() + B.tables[t].off;
+    arena_update(d, B.meshTables.data(), B.F, tab.data());
+}
+// the tables arena_update writes: none of them grows with a mesh or with the texel pool
+inline std::vector<int32_t> arena_editable_tables(const ArenaFacts& F)
+{
+    return {F.tNodes, F.tNodesX, F.tGates, F.tSegPlanes, F.tSegMasks, F.tPlanes, F.tSpheres, F.tCubes, F.tShaders, F.tLayers, F.tLights, F.tTex};
 }
 
 // write[t]: where table t can be written now (the staging copy, or the table itself); addr[t]: where the kernels, or the host harness, will find it.

@@ -8,6 +8,8 @@ import numpy as np
 
 from . import abi
 
+P = C.POINTER
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FRAYHIP_LIB: A/B-test another build of the same library (development only)
 _LIB_PATH = os.environ.get("FRAYHIP_LIB") or os.path.join(_HERE, "libfrayhip.so")
@@ -288,6 +290,49 @@ def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, st
     return (hist, signal, var, st.as_dict()) if stats else (hist, signal, var)
 
 
+class Transform:
+    """The reference's Transform (matrix.h:72-98) over the C helpers frayhip_transform_*: the parser's own arithmetic, so that
+    Transform().scale(...).rotate(...).translate(...) in the order of a block's lines gives the bytes parseScene stores.  Starts as the identity,
+    or as a copy of `init` (an abi.Transform, or a node / light, whose T is taken).  store(target) writes it to a node's or a light's T (or to an
+    abi.Transform); a rect light's center and area are then light_begin_frame's to refresh."""
+
+    def __init__(self, init=None):
+        self.T = abi.Transform()
+        if init is None:
+            _check(lib.frayhip_transform_identity(C.byref(self.T)))
+        else:
+            C.memmove(C.byref(self.T), C.byref(getattr(init, "T", init)), C.sizeof(abi.Transform))
+
+    def scale(self, x, y, z):
+        _check(lib.frayhip_transform_scale(C.byref(self.T), float(x), float(y), float(z)))
+        return self
+
+    def rotate(self, yaw, pitch, roll):
+        _check(lib.frayhip_transform_rotate(C.byref(self.T), float(yaw), float(pitch), float(roll)))
+        return self
+
+    def translate(self, x, y, z):
+        _check(lib.frayhip_transform_translate(C.byref(self.T), float(x), float(y), float(z)))
+        return self
+
+    def store(self, target):
+        dst = target if isinstance(target, abi.Transform) else target.T
+        C.memmove(C.byref(dst), C.byref(self.T), C.sizeof(abi.Transform))
+        return target
+
+
+def light_begin_frame(light):
+    """RectLight::beginFrame on an abi.Light (Scene.lights[i]): center and area from its T (frayhip_light_begin_frame).  Returns the light."""
+    _check(lib.frayhip_light_begin_frame(C.byref(light)))
+    return light
+
+
+def shader_begin_frame(shader):
+    """Reflection::beginFrame on an abi.Shader (Scene.shaders[i]): deflectionScaling from its glossiness (frayhip_shader_begin_frame)."""
+    _check(lib.frayhip_shader_begin_frame(C.byref(shader)))
+    return shader
+
+
 class Accumulation:
     """The state of a resumable frame (include/frayhip.h "resumable frames"): `state`, float32 [H, W, 4] -- per pixel the FP32 sum of its samples'
     colours and the second moment of their luminance -- as a numpy array (Scene.render_samples then goes through the host entry) or a torch tensor
@@ -387,6 +432,20 @@ class Scene:
     def camera(self):
         return self.desc.camera
 
+    def _table(self, name, rec):
+        """A mutable ctypes view of one of the host scene's tables: edits land in self.desc's arrays, and update() pushes them."""
+        n = getattr(self.desc, "n_" + name)
+        return C.cast(getattr(self.desc, name), P(rec * n)).contents if n else (rec * 0)()
+
+    nodes = property(lambda self: self._table("nodes", abi.Node), doc="desc.nodes[] as a mutable array of abi.Node")
+    lights = property(lambda self: self._table("lights", abi.Light), doc="desc.lights[] (abi.Light)")
+    shaders = property(lambda self: self._table("shaders", abi.Shader), doc="desc.shaders[] (abi.Shader)")
+    layers = property(lambda self: self._table("layers", abi.Layer), doc="desc.layers[] (abi.Layer)")
+    textures = property(lambda self: self._table("textures", abi.Texture), doc="desc.textures[] (abi.Texture): color1, color2, scaling, bumpIntensity and ior are editable")
+    spheres = property(lambda self: self._table("spheres", abi.Sphere), doc="desc.spheres[] (abi.Sphere)")
+    planes = property(lambda self: self._table("planes", abi.Plane), doc="desc.planes[] (abi.Plane)")
+    cubes = property(lambda self: self._table("cubes", abi.Cube), doc="desc.cubes[] (abi.Cube)")
+
     @property
     def frame_size(self):
         return self.desc.settings.frameWidth, self.desc.settings.frameHeight
@@ -412,6 +471,15 @@ class Scene:
         reference re-derives the camera every frame, so callers may move it between render() calls)."""
         self._need_dev()
         _check(lib.frayhip_scene_set_view(self._dev, C.byref(self.desc.camera), C.byref(self.desc.settings)))
+        return self
+
+    def update(self):
+        """Pushes the editable tables of self.desc -- nodes, planes, spheres, cubes, shaders, layers, lights and the textures' parameters, as edited
+        through the views above -- to the uploaded scene (frayhip_scene_update): the handle then renders and answers queries exactly as one
+        created from the edited description would, and keeps its workspace, options and seed table.  The camera and the settings stay
+        beginFrame()'s."""
+        self._need_dev()
+        _check(lib.frayhip_scene_update(self._dev, C.byref(self.desc)))
         return self
 
     def endRender(self):

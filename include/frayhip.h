@@ -278,6 +278,42 @@ void frayhip_scene_destroy(frayhip_scene* s);
  * Camera::beginFrame re-derives everything per frame anyway).  Either pointer may be NULL. */
 int  frayhip_scene_set_view(frayhip_scene* s, const frayhip_camera* camera, const frayhip_settings* settings);
 
+/* ---- scene edits (stand behind the reference's mutable Scene: callers edit scene.nodes[i]->T, a light or a shader between frames and
+ *      RectLight::beginFrame / Reflection::beginFrame re-derive the per-frame data, lights.cpp:37-46, shading.h:197-201) ----------------------
+ * Replaces the EDITABLE part of an uploaded scene with what `desc` holds now.  After the call every entry point behaves exactly -- pictures, hit
+ * records, work counters and the read-only figures of frayhip_scene_get_option -- as on a handle frayhip_scene_create(desc) would have made.
+ * Editable: nodes[] (every field: geom may name any existing entry of geoms[], shader, bump_tex, T); planes[], spheres[], cubes[]; shaders[],
+ *   layers[], lights[] (every field, a light's kind and subdivision included); of textures[]: color1, color2, scaling, bumpIntensity, ior.
+ * Fixed (a difference is FRAYHIP_E_ARG, and frayhip_last_error() names the table): every element count, n_texels included; geoms[] and csgs[];
+ *   every mesh's header scalars -- and by contract its arrays, which the call does not look at; every texture's kind, width, height and
+ *   texel_offset; environment.  desc->camera and desc->settings are not read: frayhip_scene_set_view changes them.
+ * What is read: the editable arrays, geoms[], csgs[], the mesh headers and the texture records.  No mesh array pointer and not desc->texels is
+ *   dereferenced (they may dangle); host time and uploaded bytes do not depend on the triangle, KD-node, leaf-reference or texel counts.
+ * The editable part gets frayhip_scene_create's range checks.  Every check, and the building of the new tables, comes before the first byte
+ *   is uploaded: a call that returns FRAYHIP_E_ARG has changed nothing.  A scene whose frame is being rendered refuses the call
+ *   (FRAYHIP_E_ARG), as frayhip_scene_set_view does.  A HIP failure during the upload returns its code, and the handle may then only be
+ *   destroyed: its tables are partly the new ones.
+ * The call blocks.  It runs after everything the scene's earlier calls enqueued (every render and query entry returns with its streams
+ *   synchronised).  Kept: the workspace, the streams and their scratch arenas, every option, and the seed table (its key does not involve the
+ *   scene's content).
+ * frayhip_scene_get_option figures: "scene_updates" (updates since creation), "scene_update_bytes" (bytes the last update uploaded),
+ *   "arena_bytes" (the size of the scene's device arena). */
+int  frayhip_scene_update(frayhip_scene* s, const frayhip_scene_desc* desc);
+
+/* The parser's own arithmetic, for callers who edit a description: host only, no device is touched.  FRAYHIP_E_ARG for a NULL pointer.
+ * frayhip_transform_*: Transform of matrix.h:72-98, on {m, invM, offset} in place -- identity resets; scale multiplies m by diag(x, y, z) from
+ *   the right and inverts; rotate (degrees: yaw, pitch, roll) multiplies by rotZ(roll) rotX(pitch) rotY(yaw) and inverts; translate adds to
+ *   the offset.  The calls in the order of a block's scale / rotate / translate lines give the bytes frayhip_scene_parse stores.
+ * frayhip_light_begin_frame: RectLight::beginFrame (lights.cpp:37-46) -- center and area from T (area keeps the float * float product); a
+ *   point light gets the parser's zeros.
+ * frayhip_shader_begin_frame: Reflection::beginFrame (shading.h:197-201) -- deflectionScaling from glossiness. */
+int  frayhip_transform_identity(frayhip_transform* T);
+int  frayhip_transform_scale(frayhip_transform* T, double x, double y, double z);
+int  frayhip_transform_rotate(frayhip_transform* T, double yaw, double pitch, double roll);
+int  frayhip_transform_translate(frayhip_transform* T, double x, double y, double z);
+int  frayhip_light_begin_frame(frayhip_light* light);
+int  frayhip_shader_begin_frame(frayhip_shader* shader);
+
 /* Tunables of an uploaded scene (value ranges checked, FRAYHIP_E_ARG otherwise):
  *   "pt_lanes"      1..4   path-tracing batches in flight at once, each on its own HIP stream (default 4;
  *                          1 serialises every launch, which is what a per-kernel profile wants)
