@@ -286,6 +286,7 @@ DScene frame_scene(const frayhip_scene* s)
     S.saturation = set.saturation;
     S.skipNullSegments = s->skipNullSegments ? 1 : 0;
     S.segmentPlanes = s->segmentPlanes ? 1 : 0;
+    S.certifiedSegments = (s->certifiedSegments && s->segmentPlanes && S.segCertAll) ? 1 : 0;      // (no effect while "segment_planes" is 0)
     return S;
 }
 
@@ -631,6 +632,7 @@ int frayhip_scene_create(const frayhip_scene_desc* desc, frayhip_scene** out)
     if (const char* e = getenv("FRAYHIP_FP_CONTRACT")) sc->fpContract = atol(e) == 1;
     if (const char* e = getenv("FRAYHIP_SKIP_NULL_SEGMENTS")) sc->skipNullSegments = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_SEGMENT_PLANES")) sc->segmentPlanes = atol(e) != 0;
+    if (const char* e = getenv("FRAYHIP_CERTIFIED_SEGMENTS")) sc->certifiedSegments = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_FUSED_WHITTED_MAX")) { long v = atol(e); if (v >= 0 && v <= 1024) sc->fusedWhittedMax = (int)v; }
     if (const char* e = getenv("FRAYHIP_CSG_LANES")) { long v = atol(e); if (v >= 1 && v <= FRAY_PT_LANES) sc->csgLanes = (int)v; }
     if (const char* e = getenv("FRAYHIP_SEED_TABLE_MIB")) { long v = atol(e); if (v >= 0 && v <= (1 << 20)) sc->seedTableCapBytes = (size_t)v << 20; }
@@ -652,6 +654,9 @@ int frayhip_scene_get_option(frayhip_scene* s, const char* name, int64_t* value)
     else if (n == "shadow_segments") *value = s->lastShadowSegments;
     else if (n == "segment_planes") *value = s->segmentPlanes ? 1 : 0;
     else if (n == "segment_plane_nodes") *value = s->S.nSegNodes;
+    else if (n == "certified_segments") *value = s->certifiedSegments ? 1 : 0;
+    else if (n == "certified_segments_eligible") *value = s->S.segCertAll;
+    else if (n == "shadow_segments_certified") *value = s->lastShadowCertified;
     else if (n == "shadow_nodes_skipped") *value = s->lastShadowNodesSkipped;
     else if (n == "seed_table_mib") *value = (int64_t)(s->seedTableCapBytes >> 20);
     else if (n == "seed_table_bytes") *value = (int64_t)s->seedTab.bytes;
@@ -703,6 +708,9 @@ int frayhip_scene_set_option(frayhip_scene* s, const char* name, int64_t value)
     } else if (n == "segment_planes") {
         if (value != 0 && value != 1) { set_error("frayhip_scene_set_option: segment_planes must be 0 or 1"); return FRAYHIP_E_ARG; }
         s->segmentPlanes = value != 0;
+    } else if (n == "certified_segments") {
+        if (value != 0 && value != 1) { set_error("frayhip_scene_set_option: certified_segments must be 0 or 1"); return FRAYHIP_E_ARG; }
+        s->certifiedSegments = value != 0;
     } else {
         set_error("frayhip_scene_set_option: unknown option " + n);
         return FRAYHIP_E_ARG;

@@ -203,6 +203,8 @@ struct DScene {
     int32_t nSegPlanes, nSegNodes;
     int32_t segmentPlanes;         // option "segment_planes": k_pt_shadow's timed variants for untransformed scenes skip, per wave, the nodes whose planes no live segment crosses
     int32_t skipNullSegments;      // option "skip_null_segments": the timed path-tracing kernels do not queue a next-event segment whose contribution is +0 in all three channels (dev_shade.hpp nee_prepare)
+    int32_t segCertAll;            // every node is a segment-plane node or lies in an exact gate (scene_arena.hpp fill_editable): a segment that passes every plane and every gate is visible
+    int32_t certifiedSegments;     // option "certified_segments" (and "segment_planes", and segCertAll): path_shade stores the term of such a segment itself instead of queueing it
 };
 
 // Work decomposition of a frame: the reference's 48x48 buckets (sdl.cpp:243-262), of which this

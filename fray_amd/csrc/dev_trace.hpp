@@ -1107,6 +1107,68 @@ FD uint32_t segment_skip_nodes(const DScene& S, V3 a, V3 b, bool live)
     return skipNodes;
 }
 
+// Which end of its wave's queue segment a ray goes to (QMeta, dev_queues.hpp; kernels.hpp): true = it may enter one of the scene's gates (DGate: the boxes
+// of the meshes with long brute-force triangle loops).  A slab test in FP32 on the world-space box -- a scheduling hint, nothing else.
+// Round 5: when every gate of the scene is EXACT (DGate::exact: untransformed nodes) the test is dev_misscert.hpp's FP32 certificate instead, "gate-free" is
+// then proven, and the consumers skip the gated nodes for the rays filed at the front (closest_hit / visible, `gateFree`).
+// Returns 0 for a gate-free ray, else 1 + the index of the first gate it may enter.
+#ifdef __HIP__
+#define FRAY_RCPF(x) __builtin_amdgcn_rcpf(x)
+#else
+#define FRAY_RCPF(x) (1.0f / (x))          // the host harnesses (tests/native) compile this header as plain C++; the hint decides nothing there
+#endif
+FD uint32_t ray_gate_class(const DScene& S, V3 o, V3 d)
+{
+    const int ng = S.nGates;
+    if (ng == 0) return 0u;
+    const float ox = (float)o.x, oy = (float)o.y, oz = (float)o.z;
+    if (S.gatesExact) {
+        const float dx = (float)d.x, dy = (float)d.y, dz = (float)d.z;
+        const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz)), dsum = fabsf(dx) + fabsf(dy) + fabsf(dz);
+        uint32_t first = 0;
+        for (int g = ng - 1; g >= 0; g--) {
+            const FRAY_RO DGate& G = S.gates[g];
+            if (!ray_surely_misses_box_f32(G.cf[0], G.cf[1], G.cf[2], G.hf[0], G.hf[1], G.hf[2], G.Mf, ox, oy, oz, dx, dy, dz, omax, dsum)) first = (uint32_t)g + 1u;
+        }
+        return !(omax < 1e9f) && !first ? 1u : first;
+    }
+    const float rx = FRAY_RCPF((float)d.x), ry = FRAY_RCPF((float)d.y), rz = FRAY_RCPF((float)d.z);
+    uint32_t first = 0;
+    for (int g = ng - 1; g >= 0; g--) {
+        const FRAY_RO DGate& G = S.gates[g];
+        const float ax = ((float)G.lo[0] - ox) * rx, bx = ((float)G.hi[0] - ox) * rx;
+        const float ay = ((float)G.lo[1] - oy) * ry, by = ((float)G.hi[1] - oy) * ry;
+        const float az = ((float)G.lo[2] - oz) * rz, bz = ((float)G.hi[2] - oz) * rz;
+        const float t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), 0.0f));
+        const float t1 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
+        if (!(t0 > t1 * 1.0001f + 1e-3f)) first = (uint32_t)g + 1u;          // NaNs (a direction component of 0 on a box face) count as "may enter"
+    }
+    return first;
+}
+
+// Certified segments (option "certified_segments", kernels.hpp path_shade): one lane's own next-event segment stays on one side of EVERY plane entry of the
+// scene by the margin (dev_segcert.hpp, with seg_cert_scale's guard).  In a scene whose nodes are all segment-plane nodes or exactly gated ones
+// (DScene::segCertAll) such a segment, when its ray also misses every gate (ray_gate_class == 0 with gatesExact, or no gates), has visible(a, b) == true as the reference
+// computes it: no node can report anything nearer than b.  Per lane, no ballots, no masks (all entries must pass); the plane records are scalar operands.
+FD bool segment_certified(const DScene& S, V3 a, V3 b)
+{
+    const int nP = S.nSegPlanes;
+    const V3 e = b - a;                 // (visible()'s own first step)
+    const double m = seg_cert_scale(a.x, a.y, a.z, b.x, b.y, b.z, e.x, e.y, e.z);
+    bool ok = m == m;                   // (0) failed: NaN
+    for (int p = 0; p < nP; p++) {
+        const FRAY_RO DSegPlane& P = S.segPlanes[p];
+        ok = ok & seg_same_side(P.N[0], P.N[1], P.N[2], P.k, P.t0, P.t1, m, a.x, a.y, a.z, b.x, b.y, b.z);
+    }
+    return ok;
+}
+// ... and the whole rule as path_shade applies it: the frame's switch (DScene::certifiedSegments: the option, "segment_planes" and segCertAll), the producer's
+// gate class of the segment's ray (0 = proven to miss every gate, or no gates) and the planes
+FD bool segment_surely_visible(const DScene& S, V3 a, V3 b, uint32_t gateClass)
+{
+    return S.certifiedSegments && gateClass == 0u && segment_certified(S, a, b);
+}
+
 // SEGP: compiled with the test for the nodes in `skipNodes` (segment_skip_nodes above; k_pt_shadow only -- every other kernel's visible() is the code it was
 // without it).  The nodes not skipped run what they always ran.
 template <int ST, bool GATES = false, bool SEGP = false>

@@ -1080,39 +1080,7 @@ FD WaveShare wave_share(uint32_t n)
     return r;
 }
 
-// Which end of its wave's queue segment a ray goes to (QMeta, dev_queues.hpp): true = it may enter one of the scene's gates (DGate: the boxes
-// of the meshes with long brute-force triangle loops).  A slab test in FP32 on the world-space box -- a scheduling hint, nothing else.
-// Round 5: when every gate of the scene is EXACT (DGate::exact: untransformed nodes) the test is dev_misscert.hpp's FP32 certificate instead, "gate-free" is
-// then proven, and the consumers skip the gated nodes for the rays filed at the front (closest_hit / visible, `gateFree`).
-// Returns 0 for a gate-free ray, else 1 + the index of the first gate it may enter.
-FD uint32_t ray_gate_class(const DScene& S, V3 o, V3 d)
-{
-    const int ng = S.nGates;
-    if (ng == 0) return 0u;
-    const float ox = (float)o.x, oy = (float)o.y, oz = (float)o.z;
-    if (S.gatesExact) {
-        const float dx = (float)d.x, dy = (float)d.y, dz = (float)d.z;
-        const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz)), dsum = fabsf(dx) + fabsf(dy) + fabsf(dz);
-        uint32_t first = 0;
-        for (int g = ng - 1; g >= 0; g--) {
-            const FRAY_RO DGate& G = S.gates[g];
-            if (!ray_surely_misses_box_f32(G.cf[0], G.cf[1], G.cf[2], G.hf[0], G.hf[1], G.hf[2], G.Mf, ox, oy, oz, dx, dy, dz, omax, dsum)) first = (uint32_t)g + 1u;
-        }
-        return !(omax < 1e9f) && !first ? 1u : first;
-    }
-    const float rx = __builtin_amdgcn_rcpf((float)d.x), ry = __builtin_amdgcn_rcpf((float)d.y), rz = __builtin_amdgcn_rcpf((float)d.z);
-    uint32_t first = 0;
-    for (int g = ng - 1; g >= 0; g--) {
-        const FRAY_RO DGate& G = S.gates[g];
-        const float ax = ((float)G.lo[0] - ox) * rx, bx = ((float)G.hi[0] - ox) * rx;
-        const float ay = ((float)G.lo[1] - oy) * ry, by = ((float)G.hi[1] - oy) * ry;
-        const float az = ((float)G.lo[2] - oz) * rz, bz = ((float)G.hi[2] - oz) * rz;
-        const float t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), 0.0f));
-        const float t1 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
-        if (!(t0 > t1 * 1.0001f + 1e-3f)) first = (uint32_t)g + 1u;          // NaNs (a direction component of 0 on a box face) count as "may enter"
-    }
-    return first;
-}
+// (ray_gate_class, which end of its wave's queue segment a ray goes to: dev_trace.hpp, where the host harness of the certified segments can see it)
 
 // Where the lanes of one batch of 64 append to a wave's queue segment: the gate-free rays at the front (in order), the others at the back (in
 // reverse), ranked by ballot -- no global counter.  `nF` / `nB`: entries so far at either end (wave-uniform).
@@ -1122,7 +1090,7 @@ struct SegEnds { uint32_t begin, chunk, nF, nB; };
 // safe (two groups would both count from zero: measured -- 2 % of the segments of the instrumented kernel variant overwrote each other).  The
 // wave's two counters live in LDS and every appending lane takes its own slot with an LDS atomic; the order inside the segment is then
 // arbitrary, which changes nothing (every path carries its own sample slot).
-struct SegEndsShared { uint32_t begin, chunk; uint32_t* n; };        // n[0] front count, n[1] back count: this wave's pair in LDS
+struct SegEndsShared { uint32_t begin, chunk; uint32_t* n; };        // n[0] front count, n[1] back count: this wave's pair in LDS; n[2]: the segments certified instead of appended (path_shade)
 FD uint32_t seg_take(const SegEndsShared& E, bool back)
 {
     const uint32_t k = atomicAdd(E.n + (back ? 1 : 0), 1u);
@@ -1172,13 +1140,30 @@ FD void path_shade(const DScene& S, PathStateT<G>& ps, const HitT<ST>& h, const 
             C3 sc;
             shadow = nee_prepare(S, ps.d, info, ps.pm, sh, ps.rnd, ps.tab, sa, sb, sc, !(ST & 1) && S.skipNullSegments != 0);   // the counting variants trace every segment the reference traces
             if (shadow) {
+                // Certified segments (flag word 0 only: the counting variant queues every segment the reference traces; DScene::certifiedSegments is the option,
+                // "segment_planes" and the scene's segCertAll together): the segment's ray misses every gate and its ends lie on one side of every plane entry, so
+                // visible() is true as the reference computes it (dev_trace.hpp segment_surely_visible) and the term k_pt_shadow would store is sc, bit for bit.  No queue
+                // entry; the lane is counted the way the appends are, in LDS.  Every random draw has been made already.
+                // The planes are evaluated BEFORE the gate class in the exact translation units and after it (gate-free lanes only) in the contracted one: the
+                // register allocator's choice, not the source's -- the other order spills two more VGPRs here and eight more there (profiles/certified_segments/README.md).
+                bool planesPass = false;
+                if constexpr (ST == 0 && FRAY_ARITH == 0) { if (S.certifiedSegments) planesPass = segment_certified(S, sa, sb); }
                 shadowBack = ray_gate_class(S, sa, sb - sa);
-                const uint32_t j = seg_take(shadowEnds, shadowBack != 0);
-                SQ.ax[j] = sa.x; SQ.ay[j] = sa.y; SQ.az[j] = sa.z;
-                SQ.bx[j] = sb.x; SQ.by[j] = sb.y; SQ.bz[j] = sb.z;
-                SQ.cr[j] = sc.r; SQ.cg[j] = sc.g; SQ.cb[j] = sc.b;
-                SQ.slot[j] = ps.slot;
-                if constexpr (FRAY_SORT && sort_variant(ST)) SQ.cls[j] = (unsigned char)ray_sort_class<ST>(sb - sa, shadowBack);
+                if constexpr (ST == 0) {
+                    if (FRAY_ARITH == 0 ? planesPass && shadowBack == 0 : segment_surely_visible(S, sa, sb, shadowBack)) {
+                        own = sc;
+                        shadow = false;
+                        atomicAdd(shadowEnds.n + 2, 1u);
+                    }
+                }
+                if (ST != 0 || shadow) {                      // (every other flag word: the code it was)
+                    const uint32_t j = seg_take(shadowEnds, shadowBack != 0);
+                    SQ.ax[j] = sa.x; SQ.ay[j] = sa.y; SQ.az[j] = sa.z;
+                    SQ.bx[j] = sb.x; SQ.by[j] = sb.y; SQ.bz[j] = sb.z;
+                    SQ.cr[j] = sc.r; SQ.cg[j] = sc.g; SQ.cb[j] = sc.b;
+                    SQ.slot[j] = ps.slot;
+                    if constexpr (FRAY_SORT && sort_variant(ST)) SQ.cls[j] = (unsigned char)ray_sort_class<ST>(sb - sa, shadowBack);
+                }
             }
         }
         PathRay win, wout;
@@ -1211,7 +1196,8 @@ struct LongRng { uint32_t* cols; uint32_t nPaths; DFrame F; int nItems, s0; };
 // FIRST: the batch's first bounce makes its own camera rays (what k_pt_init does for the other cases: stereo, long generators) instead of
 // reading them from a queue -- no 92-byte path record written and read back per camera sample, one launch less per batch.
 struct FirstArgs { DCamera C; DFrame F; int nItems, s0; uint32_t n; const uint32_t* x397; unsigned short* termCount; };
-struct BounceArgs { DScene S; PathQueue Qin, Qout; ShadowQueue SQ; QMetaRO metaIn; QMeta* metaOut; QMeta* metaShadow; TermBuf TB; StereoBuf SB; LongRng LR; DStats* st; FirstArgs FA; };
+// segCertified (may be null): the batch lane's count of next-event segments path_shade certified instead of queueing (render_state.hpp kSegCertifiedOffset), one atomic per wave
+struct BounceArgs { DScene S; PathQueue Qin, Qout; ShadowQueue SQ; QMetaRO metaIn; QMeta* metaOut; QMeta* metaShadow; TermBuf TB; StereoBuf SB; LongRng LR; DStats* st; FirstArgs FA; unsigned long long* segCertified; };
 // ARITH: how the translation unit was compiled -- 0 = the reference's arithmetic (-ffp-contract=off: every hit record and every colour is the CPU reference build's, bit
 // for bit), 1 = -ffp-contract=fast (render_contract.hip: multiply-add pairs fused; only for rays AFTER a sample's first closest hit, i.e. colour within
 // north_star's 1e-4 RMS, option "fp_contract").  The parameter only names the kernel apart in profiles; the code is the same source.
@@ -1235,8 +1221,8 @@ static __global__ __launch_bounds__(256, waves_for(ST, kd_variant(ST) ? FRAY_BOU
     const WaveShare ws = wave_share(FIRST ? A.FA.n : metaIn.p->n);
     const uint32_t lane = threadIdx.x & 63u;
     SegEnds outEnds{ws.begin, ws.chunk, 0, 0};                                            // wave-uniform
-    __shared__ uint32_t shadowCount[4][2];
-    if (lane < 2) shadowCount[threadIdx.x >> 6][lane] = 0;
+    __shared__ uint32_t shadowCount[4][ST == 0 ? 3 : 2];                                  // (flag word 0: and the segments certified, path_shade)
+    if (lane < (ST == 0 ? 3u : 2u)) shadowCount[threadIdx.x >> 6][lane] = 0;
     const SegEndsShared shadowEnds{ws.begin, ws.chunk, shadowCount[threadIdx.x >> 6]};
     uint32_t seg = (!FIRST && ws.begin < ws.end) ? seg_first(off, nSeg, ws.begin) : 0;
 #ifdef FRAY_STAMPS
@@ -1348,6 +1334,11 @@ static __global__ __launch_bounds__(256, waves_for(ST, kd_variant(ST) ? FRAY_BOU
     if (lane == 0) {
         metaOut->cnt[ws.w] = outEnds.nF + outEnds.nB; metaOut->nf[ws.w] = outEnds.nF;
         metaShadow->cnt[ws.w] = shadowCount[threadIdx.x >> 6][0] + shadowCount[threadIdx.x >> 6][1]; metaShadow->nf[ws.w] = shadowCount[threadIdx.x >> 6][0];
+        if constexpr (ST == 0) {
+            unsigned long long* const total = KARG(BounceArgs, kernel_args<BounceArgs>(), segCertified);
+            const uint32_t nCert = shadowCount[threadIdx.x >> 6][2];
+            if (total && nCert) atomicAdd(total, (unsigned long long)nCert);
+        }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         metaOut->chunk = ws.chunk; metaOut->nSeg = ws.W; metaShadow->chunk = ws.chunk; metaShadow->nSeg = ws.W;

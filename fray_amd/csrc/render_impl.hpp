@@ -534,6 +534,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 QMeta* meta;
                 unsigned long long* segTotal;       // this lane's running total of shadow-queue entries (render_state.hpp kSegTotalsOffset)
                 unsigned long long* segSkipped;     // ... and of the nodes its shadow launches skipped by the segment-plane certificate (kSegSkippedOffset)
+                unsigned long long* segCertified;   // ... and of the segments its bounce launches certified instead of queueing (kSegCertifiedOffset)
             } lane[FRAY_PT_LANES];
             unsigned char* p = (unsigned char*)sc->d_work;
             float* sum = (float*)p; p += ((size_t)nItems * 12 + 255) / 256 * 256;
@@ -543,6 +544,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 L.meta = sc->d_qmeta + 3 * k;
                 L.segTotal = (unsigned long long*)((unsigned char*)sc->d_stats + kSegTotalsOffset) + k;
                 L.segSkipped = (unsigned long long*)((unsigned char*)sc->d_stats + kSegSkippedOffset) + k;
+                L.segCertified = (unsigned long long*)((unsigned char*)sc->d_stats + kSegCertifiedOffset) + k;
                 p = carve_queue(p, nQueue, L.Q[0]);
                 p = carve_queue(p, nQueue, L.Q[1]);
                 p = carve_shadow(p, nQueue, L.SQ);
@@ -594,7 +596,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                         const LongRng LR{L.mtCols, (uint32_t)nPaths, F, nItems, s0};
                         const TermBuf TB{L.terms, L.termCount, (uint32_t)nPaths, b};
                         const FirstArgs FA{C, F, nItems, s0, (uint32_t)((size_t)nItems * cn), x397, L.termCount};
-                        const BounceArgs BA{S, L.Q[b & 1], L.Q[(b + 1) & 1], L.SQ, mIn, L.meta + ((b + 1) & 1), L.meta + 2, TB, save, LR, sc->d_stats, FA};
+                        const BounceArgs BA{S, L.Q[b & 1], L.Q[(b + 1) & 1], L.SQ, mIn, L.meta + ((b + 1) & 1), L.meta + 2, TB, save, LR, sc->d_stats, FA, L.segCertified};
                         // option "fp_contract": bounces after a sample's first closest hit (and every visibility query) are colour, bounded by RMS and not by
                         // bits -- they run the kernels compiled with fused multiply-adds (render_contract.hip; not built for the Cube / CSG variants, which
                         // measured slower with it)
@@ -651,12 +653,17 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
     HIP_TRY(hipEventRecord(sc->evB, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     drain.armed = false;                    // every lane was joined into `stream` above
-    struct Back { DStats ds[2]; unsigned long long segTotal[FRAY_PT_LANES], segSkipped[FRAY_PT_LANES]; } back;         // the two counter blocks, the lanes' shadow-queue totals and skipped nodes: one copy
-    static_assert(offsetof(Back, segTotal) == kSegTotalsOffset && offsetof(Back, segSkipped) == kSegSkippedOffset, "the shadow-queue totals and the skipped nodes follow the counter blocks");
+    struct Back { DStats ds[2]; unsigned long long segTotal[FRAY_PT_LANES], segSkipped[FRAY_PT_LANES], segCertified[FRAY_PT_LANES]; } back;         // the two counter blocks, the lanes' shadow-queue totals, skipped nodes and certified segments: one copy
+    static_assert(offsetof(Back, segTotal) == kSegTotalsOffset && offsetof(Back, segSkipped) == kSegSkippedOffset && offsetof(Back, segCertified) == kSegCertifiedOffset,
+                  "the shadow-queue totals, the skipped nodes and the certified segments follow the counter blocks");
     HIP_TRY(hipMemcpy(&back, sc->d_stats, sizeof back, hipMemcpyDeviceToHost));
     const DStats (&dsv)[2] = back.ds;
     sc->lastShadowSegments = 0;
     for (int k = 0; k < FRAY_PT_LANES; k++) sc->lastShadowSegments += (long long)back.segTotal[k];
+    // "shadow_segments" is what the timed kernels decided: the queue's entries and the segments certified in their place
+    sc->lastShadowCertified = 0;
+    for (int k = 0; k < FRAY_PT_LANES; k++) sc->lastShadowCertified += (long long)back.segCertified[k];
+    sc->lastShadowSegments += sc->lastShadowCertified;
     sc->lastShadowNodesSkipped = 0;
     for (int k = 0; k < FRAY_PT_LANES; k++) sc->lastShadowNodesSkipped += (long long)back.segSkipped[k];
     {

@@ -80,8 +80,10 @@ struct frayhip_scene {
     long long lastContracted = 0;     // the last frame's launches of contracted kernels (frayhip_scene_get_option "contracted_launches")
     bool skipNullSegments = true;     // option "skip_null_segments": the timed path-tracing kernels queue no next-event segment whose contribution is +0 in every channel (dev_shade.hpp nee_prepare)
     bool segmentPlanes = true;        // option "segment_planes": k_pt_shadow skips, per wave, the eligible nodes whose triangles' planes no live segment crosses (dev_segcert.hpp)
+    bool certifiedSegments = true;    // option "certified_segments": path_shade stores the term of a next-event segment proven unoccluded itself instead of queueing it (dev_trace.hpp segment_certified; needs segmentPlanes and DScene::segCertAll)
+    long long lastShadowCertified = 0;   // the last frame's next-event segments decided that way (frayhip_scene_get_option "shadow_segments_certified"); they are part of lastShadowSegments
     long long lastShadowNodesSkipped = 0;   // the last frame's sum over k_pt_shadow's wave iterations of the nodes skipped that way (frayhip_scene_get_option "shadow_nodes_skipped")
-    long long lastShadowSegments = 0; // the last frame's shadow-queue entries over all its launches (frayhip_scene_get_option "shadow_segments"; render_impl frames)
+    long long lastShadowSegments = 0; // the last frame's next-event segments the timed kernels decided, shadow-queue entries over all its launches plus the certified ones (frayhip_scene_get_option "shadow_segments"; render_impl frames)
     long long lastFans[4] = {0, 0, 0, 0};   // the last frame's fans filed, children traced ahead, children looked up, fans given up part of the way (frayhip_scene_get_option)
     int lightSampleCount = 0;         // sum over lights of Light::getNumSamples(): segments a Lambert / Phong hit queues (wavefront Whitted)
     bool extGeometry = false;         // Cube / CSG nodes present
@@ -117,10 +119,12 @@ namespace frayhip_detail {
 // d_stats: two DStats blocks, then (256-byte aligned) the work cursors; one memset clears all of it per frame
 // ... and, in the gap before the cursors, one running total of shadow-queue entries per batch lane (k_scan adds each launch's total to its lane's word:
 // the launches of a lane are ordered by its stream, so no atomic is needed); and after those, per batch lane, the nodes k_pt_shadow's waves skipped by the
-// segment-plane certificate (one atomic per wave at the kernel's end)
+// segment-plane certificate (one atomic per wave at the kernel's end); and after those, per batch lane, the next-event segments k_pt_bounce's waves certified
+// instead of queueing (the same pattern)
 constexpr size_t kSegTotalsOffset = 2 * sizeof(DStats);
 constexpr size_t kSegSkippedOffset = kSegTotalsOffset + FRAY_PT_LANES * sizeof(unsigned long long);
-constexpr size_t kCursorOffset = (kSegSkippedOffset + FRAY_PT_LANES * sizeof(unsigned long long) + 255) / 256 * 256;
+constexpr size_t kSegCertifiedOffset = kSegSkippedOffset + FRAY_PT_LANES * sizeof(unsigned long long);
+constexpr size_t kCursorOffset = (kSegCertifiedOffset + FRAY_PT_LANES * sizeof(unsigned long long) + 255) / 256 * 256;
 constexpr size_t kStatsBytes = kCursorOffset + 3 * sizeof(DCursors);     // sets of tile cursors: a batch's closest-hit and any-hit kernels; the three passes of speculative Whitted
 
 DCamera camera_begin_frame(const frayhip_camera& c, int W, int H);

@@ -31,7 +31,7 @@ struct ArenaMeshTables { int32_t tris, attrs, kd, kdBox, refs, ltris, ltris32; }
 // Plain data: what a description leaves behind besides the tables themselves.
 struct ArenaFacts {
     int32_t extGeometry, kdMeshes, textured, whittedNeedsRecursion, lightDraws, lightSampleCount, specFanMax;
-    int32_t nGates, gatesExact, nSegPlanes, nSegNodes;
+    int32_t nGates, gatesExact, nSegPlanes, nSegNodes, segCertAll;
     int32_t nNodes, nLights, nMeshes, nTextures;
     int32_t envPresent, envLoaded, envWidth[6], envHeight[6];
     int64_t envTexelOffset[6];
@@ -356,6 +356,48 @@ inline void fill_editable(const frayhip_scene_desc& d, const ArenaMeshTables* me
 
     F.nGates = nGates; F.gatesExact = gatesExact ? 1 : 0;
     F.nSegPlanes = nSegPlanes; F.nSegNodes = nSegNodes;
+    // Certified segments (kernels.hpp path_shade, dev_trace.hpp segment_certified): EVERY node is one a next-event segment can be proven to pass -- by the planes
+    // of its triangles (segNode) or by its exact gate (gated, which implies gatesExact).  Any other node (a sphere, a plane, a Cube / CSG node without a gate, a
+    // transformed or a KD mesh, a scene with too many planes, nodes or gates for the tables, an inexact gate) clears it.  Recomputed here with the tables it
+    // follows from, so an updated arena (arena_update) carries the flag of its own nodes.
+    bool segCertAll = true;
+    for (int i = 0; i < d.n_nodes; i++) segCertAll = segCertAll && (nodes[i].segNode != 0 || nodes[i].gated != 0);
+    // ... and every plane entry can pass for SOME next-event segment.  Such a segment ends on a light, and the rule needs every entry: an entry in whose plane
+    // every light lies whole (a point light's position, a RectLight's four corners -- its samples are convex combinations of them -- all within t0 of it,
+    // the least margin seg_same_side asks of an end) passes for no segment, and path_shade would evaluate the certificate for nothing.  Without a light there
+    // are no segments.  The lights are this function's too, so a moved light (arena_update) changes the flag like a moved node.
+    segCertAll = segCertAll && d.n_lights > 0;
+    const DSegPlane* const entries = (const DSegPlane*)tab[F.tSegPlanes];
+    for (int p = 0; p < nSegPlanes && segCertAll; p++) {
+        const DSegPlane& P = entries[p];
+        bool off = false;               // some light has a point off this plane
+        for (int i = 0; i < d.n_lights && !off; i++) {
+            const frayhip_light& l = d.lights[i];
+            for (int c = 0; c < (l.kind == FRAYHIP_LIGHT_RECT ? 4 : 1) && !off; c++) {
+                const double px = c & 1 ? 0.5 : -0.5, pz = c & 2 ? 0.5 : -0.5;          // light_nth_sample (dev_shade.hpp): (px, 0, pz) through T
+                double w[3];
+                for (int k = 0; k < 3; k++) w[k] = l.kind == FRAYHIP_LIGHT_RECT ? px * l.T.m[k] + pz * l.T.m[6 + k] + l.T.offset[k] : l.pos[k];
+                off = std::fabs(P.N[0] * w[0] + P.N[1] * w[1] + P.N[2] * w[2] - P.k) > P.t0;
+            }
+        }
+        segCertAll = off;
+    }
+    // ... and a segment STARTS 1e-6 off the surface it was sampled on (dev_shade.hpp nee_prepare: a = x + norm * 1e-6).  On a gated node that start lies inside
+    // the gate; on a plane node it clears the node's own planes only where 1e-6 |N|_2 exceeds their margin (at least t0, which grows with the coordinates: in a
+    // room of extent 5e6 it is 1e-4 |N|_2).  Some plane node must be able to start a certified segment, or none exists.
+    const uint32_t* const nodeMasks = (const uint32_t*)tab[F.tSegMasks];
+    bool starts = false;
+    for (int j = 0; j < nSegNodes && !starts; j++) {
+        bool clear = true;
+        for (int p = 0; p < nSegPlanes; p++)
+            if (nodeMasks[j] >> p & 1u) {
+                const DSegPlane& P = entries[p];
+                clear = clear && 1e-6 * std::sqrt(P.N[0] * P.N[0] + P.N[1] * P.N[1] + P.N[2] * P.N[2]) > P.t0;
+            }
+        starts = clear;
+    }
+    segCertAll = segCertAll && starts;
+    F.segCertAll = segCertAll ? 1 : 0;
 }
 
 }  // namespace detail
@@ -553,7 +595,7 @@ inline void arena_place(const ArenaFacts& F, const ArenaMeshTables* meshTables, 
     S.nGates = F.nGates; S.gatesExact = F.gatesExact;
     S.segPlanes = (const FRAY_RO DSegPlane*)addr[F.tSegPlanes];
     S.segNodeMasks = (const FRAY_RO uint32_t*)addr[F.tSegMasks];
-    S.nSegPlanes = F.nSegPlanes; S.nSegNodes = F.nSegNodes;
+    S.nSegPlanes = F.nSegPlanes; S.nSegNodes = F.nSegNodes; S.segCertAll = F.segCertAll;
     S.planes = (const FRAY_RO DPlane*)addr[F.tPlanes];
     S.spheres = (const FRAY_RO DSphere*)addr[F.tSpheres];
     S.cubes = (const FRAY_RO DCube*)addr[F.tCubes];

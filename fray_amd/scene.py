@@ -491,6 +491,7 @@ class Scene:
         """frayhip_scene_set_option: "pt_lanes" (1..4 batches in flight), "pt_budget_mib" (queue memory), "speculate_fans" (0 / 1), "fp_contract" (0 / 1: relaxed arithmetic
         for path-traced rays after a sample's first closest hit, include/frayhip.h), "skip_null_segments" (0 / 1: next-event samples that are black by bit pattern are not traced),
         "segment_planes" (0 / 1: the path tracer's any-hit kernel skips, per wave, the small untransformed meshes whose triangles' planes no next-event segment of the wave crosses),
+        "certified_segments" (0 / 1: in a scene of such meshes and exactly gated ones only, the bounce kernel stores the term of a next-event segment proven unoccluded itself, without a query),
         "seed_table_mib" (cap of the table that keeps the samples' seeding words across frames of one seed, size and bucket share; 0 = off)."""
         self._need_dev()
         _check(lib.frayhip_scene_set_option(self._dev, name.encode(), int(value)))
@@ -498,7 +499,7 @@ class Scene:
 
     def get_option(self, name):
         """frayhip_scene_get_option: an option's value, or a figure of the last frame ("fans_filed", "fan_children", "fan_children_looked_up", "fans_given_up", "contracted_launches", "shadow_segments",
-        "segment_plane_nodes", "shadow_nodes_skipped", "seed_table_bytes", "seed_launches", "seed_planes_reused", "batch_lanes")."""
+        "shadow_segments_certified", "certified_segments_eligible", "segment_plane_nodes", "shadow_nodes_skipped", "seed_table_bytes", "seed_launches", "seed_planes_reused", "batch_lanes")."""
         self._need_dev()
         v = C.c_int64(0)
         _check(lib.frayhip_scene_get_option(self._dev, name.encode(), C.byref(v)))

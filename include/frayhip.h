@@ -350,6 +350,16 @@ int  frayhip_shader_begin_frame(frayhip_shader* shader);
  *                          tests/test_segcert.py) the reference's own arithmetic cannot report a hit of such a triangle nearer than the segment's end, so the
  *                          picture is the same bit for bit, in both arithmetics (tests/test_gpu_segment_planes.py).  0 asks every node, as do the counting
  *                          kernels always: node_tests and tri_tests stay the reference's counts.
+ *   "certified_segments" 0 / 1  path tracing, the timed bounce kernel of the same leanest variants, in a scene whose EVERY node is either eligible for
+ *                          "segment_planes" or a mesh inside an exact gate (an untransformed mesh without a KD-tree of six triangles or more; at most
+ *                          eight): a next-event segment whose ray provably misses every gate and whose ends lie on one side of every plane of the
+ *                          scene by the margin is unoccluded as the reference's own arithmetic computes it, so the kernel that sampled it stores its
+ *                          term at once and the segment is neither queued nor traced (default 1).  The picture is the same bit for bit, in both
+ *                          arithmetics (tests/test_gpu_certified_segments.py; tests/test_certified_segments_host.py runs the rule on the host).  No
+ *                          effect while "segment_planes" is 0, in any other scene (a sphere, a plane, a Cube / CSG node, a transformed or a KD mesh,
+ *                          too many planes or gates, no light, a plane that contains every light whole, or coordinates so large that a segment's start, 1e-6 off
+ *                          its surface, is inside the margin of that surface's own plane on every such mesh: "certified_segments_eligible" reads 0) and on the counting kernels, which queue every segment:
+ *                          shadow_rays stays the reference's count.  frayhip_scene_update recomputes the eligibility with the node tables and the lights.
  *   "seed_table_mib" 0..1048576  the cap, in MiB, of the scene's seed table (default 4096).  Every camera sample's generator starts from x[397] of the
  *                          mt19937 seeding recurrence of sample_seed(seed, pixel, sample) -- a word that depends on the contract seed, the frame size and the
  *                          bucket share and on nothing else, and that costs a 397-step chain (k_seed) per sample.  The table keeps these words, 4 bytes per
@@ -362,13 +372,15 @@ int  frayhip_shader_begin_frame(frayhip_shader* shader);
  *                          fails, renders as without the table; the workspace takes the table's memory back before it plans smaller batches.
  *                          0 = off: nothing is held, every batch seeds its own words.  Radiance queries, adaptive and feature frames do not use the table.
  * The environment variables FRAYHIP_PT_LANES / FRAYHIP_PT_BUDGET_MIB / FRAYHIP_SPECULATE_FANS / FRAYHIP_FP_CONTRACT / FRAYHIP_SKIP_NULL_SEGMENTS /
- * FRAYHIP_SEGMENT_PLANES / FRAYHIP_SEED_TABLE_MIB preset them at frayhip_scene_create. */
+ * FRAYHIP_SEGMENT_PLANES / FRAYHIP_CERTIFIED_SEGMENTS / FRAYHIP_SEED_TABLE_MIB preset them at frayhip_scene_create. */
 int  frayhip_scene_set_option(frayhip_scene* s, const char* name, int64_t value);
 /* Reads an option back, or one of the last frame's read-only figures: "fans_filed" (camera samples whose first fan was drawn ahead),
  * "fan_children" (rays traced ahead), "fan_children_looked_up" (results used), "fans_given_up" (fans in which a ray drew a random
  * number after all, so that the rest of the fan was traced in place), "contracted_launches" (launches of the last frame that ran a kernel of
- * the "fp_contract" build), "shadow_segments" (entries of the next-event queues over the launches of the last frayhip_render / frayhip_render_progressive
- * frame: the visibility queries it actually traced), "segment_plane_nodes" (the scene's nodes eligible for option "segment_planes"; fixed at
+ * the "fp_contract" build), "shadow_segments" (the next-event segments the timed kernels of the last frayhip_render / frayhip_render_progressive
+ * frame decided: the entries of its next-event queues, i.e. the visibility queries it actually traced, plus "shadow_segments_certified", the segments
+ * option "certified_segments" decided without a query), "certified_segments_eligible" (1 when every node of the scene, as last uploaded or updated, is a
+ * plane node or an exactly gated one, some light has a point off every plane and some plane node's own margins are below 1e-6), "segment_plane_nodes" (the scene's nodes eligible for option "segment_planes"; fixed at
  * frayhip_scene_create), "shadow_nodes_skipped" (the last such frame's sum, over the wave iterations of its any-hit launches -- 64 segments each -- of the
  * nodes skipped under that option), "whitted_path" (how the last Whitted frame ran: 0 = the recursive kernel, 1 = shade / visible / gather launches, 2 = fused), "pt_budget_effective_mib" (the queue budget frames currently plan with: pt_budget_mib clamped to the device's
  * free memory, halved when an allocation failed and the frame could be planned again), "seed_table_bytes" (what the seed table currently holds on the
