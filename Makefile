@@ -26,7 +26,7 @@ HOST_OBJ := $(HOST_SRC:.cpp=.o)
 #   query<st>.o     query_variant.hip      the ray query kernels (frayhip_trace_rays / frayhip_visible)
 #   shade<st>.o     shade_variant.hip      the radiance query (frayhip_shade_rays)
 #   adaptive<st>.o  adaptive_variant.hip   adaptive frames (frayhip_render_adaptive)
-#   features<st>.o  features_variant.hip   feature frames (frayhip_render_features)
+#   features<st>.o  features_variant.hip   feature frames (frayhip_render_features) and, as a second instantiation, feature + motion frames (frayhip_render_features_motion)
 ST_WORDS := 0 1 2 3 4 5 8 9
 ST_SETS  := variant:render_variant query:query_variant shade:shade_variant adaptive:adaptive_variant features:features_variant
 ST_OBJ   := $(foreach set,$(ST_SETS),$(foreach st,$(ST_WORDS),fray_amd/csrc/$(firstword $(subst :, ,$(set)))$(st).o))

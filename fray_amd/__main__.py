@@ -11,6 +11,8 @@ src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --he
                          python -m fray_amd scene.fray -o out.bmp --frames N --move NODE DX DY DZ [--move ...] [--denoise]   (N frames of one uploaded
                                                                                           scene, node NODE moved by (DX, DY, DZ) more in each: frame k sees it
                                                                                           at k times that; plain frames unless --denoise)
+                         python -m fray_amd scene.fray -o out.bmp --denoise --frames N --move NODE DX DY DZ --motion-vectors   (the same sequence,
+                                                                                          its history fetched where the moved nodes' surfaces were)
                          python -m fray_amd scene.fray -o out.bmp --accumulate FILE.npz [--spp N] [--noise-out FILE.npy] [--time-limit SECONDS]
                                                                                          (N more samples per pixel on top of the state in FILE.npz, which
                                                                                           is started when it does not exist; the picture of all of them)"""
@@ -63,6 +65,9 @@ def build_parser():
                     help="with --frames: translate node NODE (its index among the scene's nodes) by (DX, DY, DZ) more in every frame -- frame 0 is the "
                          "scene file's, frame k sees the node k steps on; the uploaded scene is edited in place (Scene.update).  May be repeated.  "
                          "Without --denoise the frames are plain frames of the edited scene, all with seed SEED")
+    ap.add_argument("--motion-vectors", action="store_true",
+                    help="with --denoise --frames N --move ...: render the motion frame with the features (Scene.render_sequence(edit=...)) and "
+                         "accumulate through it, so that a moved node's pixels keep their history")
     ap.add_argument("--accumulate", metavar="FILE.npz",
                     help="resumable frame (Scene.render_samples): continue the state saved in FILE.npz by --spp more samples per pixel (default: the "
                          "scene's own count), or start it when the file does not exist; writes FILE.npz and the picture of all samples so far.  A "
@@ -103,6 +108,8 @@ def check_args(ap, a):
         ap.error("--frames needs --denoise: a sequence is rendered with temporal accumulation and the filter")
     if a.move and a.frames is None:
         ap.error("--move needs --frames")
+    if a.motion_vectors and not (a.denoise and a.frames is not None and a.move):
+        ap.error("--motion-vectors needs --denoise --frames N --move ...")
     if a.move and (a.adaptive is not None or a.accumulate or a.probe or a.time_limit is not None):
         ap.error("--move cannot be combined with --adaptive, --accumulate, --probe or --time-limit")
     for m in a.move or []:
@@ -198,7 +205,9 @@ def main(argv=None):
         return 0
     if a.frames is not None:
         start = abi.Camera.from_buffer_copy(s.camera)
-        for k, (img, _raw, info) in enumerate(s.render_sequence(orbit(start, a.frames, a.yaw_step), seed=a.seed, feature_samples=a.feature_samples)):
+        edit = (lambda _k, scene: move_nodes(scene, a.move)) if a.motion_vectors else None
+        for k, (img, _raw, info) in enumerate(s.render_sequence(orbit(start, a.frames, a.yaw_step), seed=a.seed, feature_samples=a.feature_samples,
+                                                                edit=edit)):
             path = sequence_path(a.output, k)
             img = img.cpu().numpy()
             if lib.frayhip_save_bmp(path.encode(), img.ctypes.data, img.shape[1], img.shape[0]):
@@ -207,7 +216,7 @@ def main(argv=None):
             print("frame %d: yaw %+.2f, frame %.1f ms, features %.1f ms, accumulation %.2f ms, filter %.2f ms (kernels); wrote %s"
                   % (k, k * a.yaw_step, info["render"]["ms_kernels"], info["features"]["ms_kernels"], info["temporal"]["ms_kernels"],
                      info["denoise"]["ms_kernels"], path), flush=True)
-            if a.move and k + 1 < a.frames:
+            if a.move and not a.motion_vectors and k + 1 < a.frames:
                 move_nodes(s, a.move)           # the generator renders the next frame when it is asked for it: after this edit
         print("Rendered %d frames in %.2fs" % (a.frames, time.time() - t0))
         return 0

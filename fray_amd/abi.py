@@ -183,6 +183,7 @@ class Denoise(C.Structure):
 
 
 FEAT_CHANNELS = 10      # FRAYHIP_FEAT_CHANNELS: position[3], normal[3], albedo[3], depth
+MOTION_CHANNELS = 8     # FRAYHIP_MOTION_CHANNELS: {P'.xyz, moved}, {n'.xyz, 0}
 
 
 class View(C.Structure):
@@ -239,6 +240,8 @@ SYMBOLS = {
     "frayhip_render_samples_device": (C.c_int, [VP, P(Frame), P(Samples), P(Progressive), VP, VP, VP, VP, P(Stats)]),
     "frayhip_render_features": (C.c_int, [VP, P(Frame), C.c_int, VP, P(Stats)]),
     "frayhip_render_features_device": (C.c_int, [VP, P(Frame), C.c_int, VP, VP, P(Stats)]),
+    "frayhip_render_features_motion": (C.c_int, [VP, P(Frame), C.c_int, P(Transform), C.c_int, VP, VP, P(Stats)]),
+    "frayhip_render_features_motion_device": (C.c_int, [VP, P(Frame), C.c_int, P(Transform), C.c_int, VP, VP, VP, P(Stats)]),
     "frayhip_denoise_defaults": (C.c_int, [P(Denoise)]),
     "frayhip_denoise": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(Denoise), VP, P(Stats)]),
     "frayhip_denoise_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(Denoise), VP, VP, P(Stats)]),
@@ -248,6 +251,8 @@ SYMBOLS = {
     "frayhip_temporal_defaults": (C.c_int, [P(Temporal)]),
     "frayhip_temporal_accumulate": (C.c_int, [C.c_int, C.c_int, VP, VP, P(View), VP, P(Temporal), VP, VP, VP, P(Stats)]),
     "frayhip_temporal_accumulate_device": (C.c_int, [C.c_int, C.c_int, VP, VP, P(View), VP, P(Temporal), VP, VP, VP, VP, P(Stats)]),
+    "frayhip_temporal_accumulate_motion": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(View), VP, P(Temporal), VP, VP, VP, P(Stats)]),
+    "frayhip_temporal_accumulate_motion_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(View), VP, P(Temporal), VP, VP, VP, VP, P(Stats)]),
     "frayhip_camera_rays": (C.c_int, [VP, i64, VP, C.c_int, VP, VP]),
     "frayhip_camera_rays_device": (C.c_int, [VP, i64, VP, C.c_int, VP, VP, VP]),
     "frayhip_trace_rays": (C.c_int, [VP, i64, VP, VP, C.c_int, VP, VP, VP, P(Stats)]),

@@ -366,6 +366,10 @@ struct SceneEdit {
     frayhip_environment environment;
 };
 
+namespace frayhip_detail {
+const DNode* host_nodes(const frayhip_scene* s) { return (const DNode*)(s->edit->host.data() + s->edit->hostOff[s->edit->F.tNodes]); }
+}  // namespace frayhip_detail
+
 namespace {
 
 using frayhip_detail::kStatsBytes;
@@ -778,6 +782,7 @@ void frayhip_scene_destroy(frayhip_scene* s)
     if (s->d_work) (void)hipFree(s->d_work);
     frayhip_detail::seed_table_free(s);
     if (s->d_stats) (void)hipFree(s->d_stats);
+    if (s->d_motionTab) (void)hipFree(s->d_motionTab);
     if (s->d_qmeta) (void)hipFree(s->d_qmeta);
     if (s->evA) (void)hipEventDestroy(s->evA);
     if (s->evB) (void)hipEventDestroy(s->evB);

@@ -62,6 +62,8 @@ FRAY_EXTERN_ST(int render_impl, (frayhip_scene*, const frayhip_frame*, float*, i
 int frame_spp(const frayhip_scene* s);
 // The scene record of a frame: the scene's with the view's ambient light, maxTraceDepth, gi and saturation
 DScene frame_scene(const frayhip_scene* s);
+// The host copy of the uploaded scene's node table (frayhip_scene_update keeps it current): S.nNodes records, inner pointers not to be followed
+const DNode* host_nodes(const frayhip_scene* s);
 // Size and bucket grid of a frame; frame_record: with the call's buckets (stride <= 0: 1; nBuckets < 0: a bad range) and the frame's spp, seed and jitter
 inline DFrame frame_grid(int W, int H)
 {

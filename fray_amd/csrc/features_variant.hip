@@ -1,10 +1,13 @@
-// Feature frames (frayhip_render_features, include/frayhip.h) for one kernel flag word: the Makefile compiles this file eight times,
+// Feature frames (frayhip_render_features, frayhip_render_features_motion, include/frayhip.h) for one kernel flag word: the Makefile compiles this file eight times,
 // -DFRAY_ST=0..5, 8, 9, into features<ST>.o.  Objects of their own: the frame kernels of render_variant.hip are compiled exactly as they were
 // without them (kernels.hpp is not touched, only included here once more).
 //
-//   k_features<ST>   per pixel of the frame's buckets, the first hit of the frame's camera samples 0 .. n-1 (k_pt_init's / k_whitted's film
+//   k_features<ST, MOTION>
+//                    per pixel of the frame's buckets, the first hit of the frame's camera samples 0 .. n-1 (k_pt_init's / k_whitted's film
 //                    position and camera or thin-lens ray, same seed), the hit's position, normal after the bump, albedo and depth, summed in
-//                    FP32 in sample order and divided by n; persistent waves claiming 8x8 tiles as k_primary does
+//                    FP32 in sample order and divided by n; persistent waves claiming 8x8 tiles as k_primary does.  MOTION: a second row per pixel,
+//                    where the hit point and its normal were in the previous frame's state of the scene (the hit node's previous transform), summed
+//                    the same way.  MOTION = false is the kernel as it was: the motion code is compiled out, not branched over.
 #include "features.hpp"
 #include "kernels.hpp"
 
@@ -12,6 +15,7 @@
 #error "compile with -DFRAY_ST=0..5, 8 or 9"
 #endif
 
+using frayhip_detail::DPrevXform;
 using frayhip_detail::FeatureArgs;
 
 // Waves per SIMD: k_query_closest's (query_variant.hip), whose loop this is with a camera ray in front and the record's shading behind, except in
@@ -50,7 +54,7 @@ FD C3 shader_albedo(const DScene& S, int shader, V3 d, const HitInfo& info, Cnt&
     return result;
 }
 
-template <int ST>
+template <int ST, bool MOTION>
 static __global__ __launch_bounds__(256, features_waves(ST)) void k_features(FeatureArgs A)
 {
     Cnt c = zero_cnt();
@@ -108,11 +112,36 @@ static __global__ __launch_bounds__(256, features_waves(ST)) void k_features(Fea
                                                     alb.r, alb.g, alb.b, (float)depth};
 #pragma unroll
             for (int k = 0; k < FRAYHIP_FEAT_CHANNELS; k++) out[k] = i == 0 ? v[k] : out[k] + v[k];
+            if constexpr (MOTION) {
+                // where this point of the hit node was in the previous state: Transform::untransformPoint of the node's transform now, then
+                // transformPoint of its previous one; the normal goes the way Node::intersect carries one (through m, not rescaled).  Only the
+                // lanes whose node moved read the table; everything else repeats the feature row's position and normal.
+                float mv = 0.0f;
+                if (h.node >= 0) {
+                    if (KARG(FeatureArgs, AP, moved)[h.node]) {
+                        const FRAY_RO DNode& N = S.nodes[h.node];
+                        const DPrevXform& X = KARG(FeatureArgs, AP, prev)[h.node];
+                        ip = mulM(mulM(ip - ld3(N.T.off), N.T.inv), X.m) + ld3(X.off);
+                        norm = mulM(mulM(norm, N.T.inv), X.m);
+                        mv = 1.0f;
+                    }
+                }
+                // the sums live in the motion row, as the feature sums live in theirs
+                float* const mo = KARG(FeatureArgs, AP, motion) + (size_t)p * FRAYHIP_MOTION_CHANNELS;
+                const float w[FRAYHIP_MOTION_CHANNELS] = {(float)ip.x, (float)ip.y, (float)ip.z, mv, (float)norm.x, (float)norm.y, (float)norm.z, 0.0f};
+#pragma unroll
+                for (int k = 0; k < FRAYHIP_MOTION_CHANNELS; k++) mo[k] = i == 0 ? w[k] : mo[k] + w[k];
+            }
         }
         if (n > 1) {
             const float fn = (float)n;
 #pragma unroll
             for (int k = 0; k < FRAYHIP_FEAT_CHANNELS; k++) out[k] = out[k] / fn;
+            if constexpr (MOTION) {
+                float* const mo = KARG(FeatureArgs, AP, motion) + (size_t)p * FRAYHIP_MOTION_CHANNELS;
+#pragma unroll
+                for (int k = 0; k < FRAYHIP_MOTION_CHANNELS; k++) mo[k] = mo[k] / fn;
+            }
         }
     }
     if (ST & 1) flush_stats(A.st, c);
@@ -120,9 +149,11 @@ static __global__ __launch_bounds__(256, features_waves(ST)) void k_features(Fea
 }
 
 namespace frayhip_detail {
-template <int ST> void launch_features(hipStream_t stream, const FeatureArgs& A)
+template <int ST> void launch_features(hipStream_t stream, const FeatureArgs& A, bool motion)
 {
-    hipLaunchKernelGGL(k_features<ST>, dim3(persistent_grid((size_t)A.nItems, features_waves(ST))), dim3(256), 0, stream, A);
+    const dim3 grid(persistent_grid((size_t)A.nItems, features_waves(ST)));
+    if (motion) hipLaunchKernelGGL((k_features<ST, true>), grid, dim3(256), 0, stream, A);
+    else hipLaunchKernelGGL((k_features<ST, false>), grid, dim3(256), 0, stream, A);
 }
-template void launch_features<FRAY_ST>(hipStream_t, const FeatureArgs&);
+template void launch_features<FRAY_ST>(hipStream_t, const FeatureArgs&, bool);
 }  // namespace frayhip_detail

@@ -93,6 +93,10 @@ struct frayhip_scene {
     void* d_work = nullptr;
     size_t work_bytes = 0;
     DStats* d_stats = nullptr;
+    // frayhip_render_features_motion: the call's table of previous transforms and moved bytes, kept between calls and grown with the node count
+    void* d_motionTab = nullptr;
+    size_t motionTabBytes = 0;
+    std::vector<unsigned char> motionTabHost;     // what the upload reads: lives as long as the stream may read it
     QMeta* d_qmeta = nullptr;         // [3] segment tables: ping-pong path queues + shadow queue
     hipEvent_t evA = nullptr, evB = nullptr;
     std::vector<hipEvent_t> evPool, evPoolShadow;

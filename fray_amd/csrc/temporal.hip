@@ -1,12 +1,14 @@
 // C ABI, temporal accumulation (include/frayhip.h "temporal accumulation"): frayhip_view_from_camera, frayhip_temporal_defaults,
-// frayhip_temporal_accumulate and frayhip_temporal_accumulate_device.  The temporal stage of SVGF: the previous frame's accumulated signal and
+// frayhip_temporal_accumulate, frayhip_temporal_accumulate_motion and their _device entries.  The temporal stage of SVGF: the previous frame's accumulated signal and
 // luminance moments reprojected through the feature frame's world positions, surface tests on the four bilinear taps, the exponential blend,
 // and the variance the a-trous levels take (frayhip_denoise_signal).  Scene-free, FP32 throughout; the Makefile builds this object as it builds
 // denoise.o (-ffp-contract=off, correctly rounded divide and sqrt), so every product and sum below is rounded where it is written
 // (tests/temporal_ref.py restates it in numpy, and the two agree bit for bit).
 //
 //   k_tp_accumulate  per pixel: the signal, the projection into the previous view, four taps of three float4 rows each, the blend; writes the
-//                    three history rows, the signal, and the temporal variance where N >= variance_history
+//                    three history rows, the signal, and the temporal variance where N >= variance_history.  <MOTION>: the point projected and
+//                    the surface the taps are tested against are the motion frame's P' and n' (two float4 rows) instead of the feature frame's
+//                    position and normal; <false> is the kernel as it was
 //   k_tp_variance    per pixel with N < variance_history: the 7x7 window of the finished history (rows 1 and 2: position, normal, m1, m2),
 //                    taken from an LDS tile that the 16x16 block stages first; a block without such a pixel stages nothing
 // k_tp_accumulate's taps are read through L1 / L2, as the filter's.  k_tp_variance with the same direct reads took 0.214 ms at 1080p where
@@ -27,6 +29,7 @@ struct TemporalCall {
     int W, H;
     const float* rgb;
     const float* feat;
+    const float4* motion;       // k_tp_accumulate<true> only: two rows a pixel
     const float4* histIn;       // null: first frame
     float4* histOut;
     float* signal;
@@ -36,6 +39,7 @@ struct TemporalCall {
     float maxHistory, alphaMin, filmOffset, planeTolerance, normalMinDot;
 };
 
+template <bool MOTION>
 static __global__ __launch_bounds__(256) void k_tp_accumulate(TemporalCall T)
 {
     const int W = T.W, H = T.H;
@@ -56,10 +60,23 @@ static __global__ __launch_bounds__(256) void k_tp_accumulate(TemporalCall T)
     const float l2 = l * l;
 
     float sb = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hn = 0.0f, h1 = 0.0f, h2 = 0.0f;
-    const bool miss = nx == 0.0f && ny == 0.0f && nz == 0.0f;
+    bool miss = nx == 0.0f && ny == 0.0f && nz == 0.0f;
+    // what is carried into the previous view: the pixel's own position and unit normal, or where they were (P', n' scaled as the normal is)
+    float Qx = Px, Qy = Py, Qz = Pz, mx = nx, my = ny, mz = nz;
+    if constexpr (MOTION) {
+        const float4 r0 = T.motion[2 * p], r1 = T.motion[2 * p + 1];
+        Qx = r0.x; Qy = r0.y; Qz = r0.z;
+        mx = r1.x; my = r1.y; mz = r1.z;
+        const float mm = mx * mx + my * my + mz * mz;
+        if (mm > 0.0f) {
+            const float s = sqrtf(mm);
+            mx = mx / s; my = my / s; mz = mz / s;
+        }
+        miss = miss || (mx == 0.0f && my == 0.0f && mz == 0.0f);
+    }
     if (T.histIn && !miss) {
         const frayhip_view& V = T.view;
-        const float dx = Px - V.pos[0], dy = Py - V.pos[1], dz = Pz - V.pos[2];
+        const float dx = Qx - V.pos[0], dy = Qy - V.pos[1], dz = Qz - V.pos[2];
         const float zc = tp_dot(dx, dy, dz, V.front[0], V.front[1], V.front[2]);
         if (zc > 0.0f) {
             const float xc = tp_dot(dx, dy, dz, V.right[0], V.right[1], V.right[2]);
@@ -82,8 +99,8 @@ static __global__ __launch_bounds__(256) void k_tp_accumulate(TemporalCall T)
                         const float4* hq = T.histIn + ((size_t)yq * W + xq) * 3;
                         const float4 q0 = hq[0], q1 = hq[1], q2 = hq[2];
                         if (q2.x == 0.0f && q2.y == 0.0f && q2.z == 0.0f) continue;
-                        if (!(tp_dot(nx, ny, nz, q2.x, q2.y, q2.z) >= T.normalMinDot)) continue;
-                        if (!(fabsf(tp_dot(q1.x - Px, q1.y - Py, q1.z - Pz, nx, ny, nz)) <= tol)) continue;
+                        if (!(tp_dot(mx, my, mz, q2.x, q2.y, q2.z) >= T.normalMinDot)) continue;
+                        if (!(fabsf(tp_dot(q1.x - Qx, q1.y - Qy, q1.z - Qz, mx, my, mz)) <= tol)) continue;
                         const float b = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty);
                         sb += b;
                         hr += b * q0.x; hg += b * q0.y; hb += b * q0.z; hn += b * q0.w;
@@ -180,13 +197,16 @@ bool overlaps(const void* a, size_t an, const void* b, size_t bn)
 bool finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
 // Every check of both entries, in this order; none touches the device.
+// WITH_MOTION: the _motion entries, whose motion frame is an input like feat; NO_MOTION: the others (motion is null).
+enum MotionInput { NO_MOTION, WITH_MOTION };
 int check(const char* who, int W, int H, const float* rgb, const float* feat, const frayhip_view* view, const float* histIn, const struct frayhip_temporal* p,
-          const float* histOut, const float* signal, const float* variance, bool device)
+          const float* histOut, const float* signal, const float* variance, bool device, MotionInput mi, const float* motion)
 {
     if (W < 1 || H < 1) return bad(who, "width and height must be >= 1");
     if ((long long)W * H > (1ll << 30)) return bad(who, "more than 2^30 pixels");
     if (!rgb) return bad(who, "null rgb");
     if (!feat) return bad(who, "null feat");
+    if (mi == WITH_MOTION && !motion) return bad(who, "null motion");
     if (!p) return bad(who, "null parameters");
     if (!histOut) return bad(who, "null hist_out");
     if (!signal) return bad(who, "null signal");
@@ -196,6 +216,7 @@ int check(const char* who, int W, int H, const float* rgb, const float* feat, co
         for (const void* q : {(const void*)rgb, (const void*)feat, (const void*)signal, (const void*)variance})
             if (misaligned(q, 4)) return bad(who, "device pointer to floats not 4-byte aligned");
         if (misaligned(histIn, 16) || misaligned(histOut, 16)) return bad(who, "device pointer to a history not 16-byte aligned");
+        if (misaligned(motion, 16)) return bad(who, "device pointer to a motion frame not 16-byte aligned");
     }
     if (view) {
         if (view->width != W || view->height != H) return bad(who, "prev_view's size is not the frame's");
@@ -211,7 +232,8 @@ int check(const char* who, int W, int H, const float* rgb, const float* feat, co
     if (!std::isfinite(p->plane_tolerance) || p->plane_tolerance < 0) return bad(who, "plane_tolerance must be finite and >= 0");
     if (!(p->normal_min_dot >= -1 && p->normal_min_dot <= 1)) return bad(who, "normal_min_dot must be -1..1");
     const size_t n = (size_t)W * H;
-    const struct { const void* q; size_t bytes; } ins[3] = {{rgb, 12 * n}, {feat, 4 * FRAYHIP_FEAT_CHANNELS * n}, {histIn, 4 * FRAYHIP_HISTORY_CHANNELS * n}};
+    const struct { const void* q; size_t bytes; } ins[4] = {{rgb, 12 * n}, {feat, 4 * FRAYHIP_FEAT_CHANNELS * n}, {histIn, 4 * FRAYHIP_HISTORY_CHANNELS * n},
+                                                            {motion, 4 * FRAYHIP_MOTION_CHANNELS * n}};
     const struct { const void* q; size_t bytes; const char* name; } outs[3] = {{histOut, 4 * FRAYHIP_HISTORY_CHANNELS * n, "hist_out"}, {signal, 12 * n, "signal"},
                                                                                  {variance, 4 * n, "variance"}};
     for (int o = 0; o < 3; o++) {
@@ -229,13 +251,14 @@ struct Events {
 };
 
 // The device path of both entries (device pointers, checked)
+// motion: the motion frame of the _motion entries, or null
 int run(int W, int H, const float* rgb, const float* feat, const frayhip_view* view, const float* histIn, const struct frayhip_temporal* prm, float* histOut,
-        float* signal, float* variance, hipStream_t stream, frayhip_stats* st, std::chrono::steady_clock::time_point t0)
+        float* signal, float* variance, hipStream_t stream, frayhip_stats* st, std::chrono::steady_clock::time_point t0, const float* motion = nullptr)
 {
     const size_t n = (size_t)W * H;
     TemporalCall T{};
     T.W = W; T.H = H;
-    T.rgb = rgb; T.feat = feat;
+    T.rgb = rgb; T.feat = feat; T.motion = (const float4*)motion;
     T.histIn = (const float4*)histIn; T.histOut = (float4*)histOut;
     T.signal = signal; T.variance = variance;
     if (view) T.view = *view;
@@ -248,7 +271,8 @@ int run(int W, int H, const float* rgb, const float* feat, const frayhip_view* v
     struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{stream};
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     HIP_TRY(hipEventRecord(E.a, stream));
-    hipLaunchKernelGGL(k_tp_accumulate, grid, block, 0, stream, T);
+    if (motion) hipLaunchKernelGGL(k_tp_accumulate<true>, grid, block, 0, stream, T);
+    else hipLaunchKernelGGL(k_tp_accumulate<false>, grid, block, 0, stream, T);
     HIP_TRY(hipGetLastError());
     if (prm->variance_history > 1) {         // N >= 1 always: with variance_history 1 no pixel takes the spatial estimate
         hipLaunchKernelGGL(k_tp_variance, dim3((unsigned)((W + 15) / 16) * (unsigned)((H + 15) / 16)), block, 0, stream, T);
@@ -320,7 +344,7 @@ int frayhip_temporal_accumulate_device(int width, int height, const float* d_rgb
                                        const struct frayhip_temporal* p, float* d_hist_out, float* d_signal, float* d_variance, void* hip_stream, frayhip_stats* st)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    if (const int rc = check("frayhip_temporal_accumulate_device", width, height, d_rgb, d_feat, prev_view, d_hist_in, p, d_hist_out, d_signal, d_variance, true))
+    if (const int rc = check("frayhip_temporal_accumulate_device", width, height, d_rgb, d_feat, prev_view, d_hist_in, p, d_hist_out, d_signal, d_variance, true, NO_MOTION, nullptr))
         return rc;
     return run(width, height, d_rgb, d_feat, prev_view, d_hist_in, p, d_hist_out, d_signal, d_variance, (hipStream_t)hip_stream, st, t0);
 }
@@ -330,7 +354,7 @@ int frayhip_temporal_accumulate(int width, int height, const float* rgb, const f
 {
     const auto t0 = std::chrono::steady_clock::now();
     const char* who = "frayhip_temporal_accumulate";
-    if (const int rc = check(who, width, height, rgb, feat, prev_view, hist_in, p, hist_out, signal, variance, false)) return rc;
+    if (const int rc = check(who, width, height, rgb, feat, prev_view, hist_in, p, hist_out, signal, variance, false, NO_MOTION, nullptr)) return rc;
     const size_t n = (size_t)width * height;
     const size_t HC = FRAYHIP_HISTORY_CHANNELS;
     // one allocation, the histories first (16-byte rows): hist_out, hist_in when given, then rgb, feat, signal, variance
@@ -346,6 +370,47 @@ int frayhip_temporal_accumulate(int width, int height, const float* rgb, const f
     HIP_TRY(hipMemcpy(d_feat, feat, n * 4 * FRAYHIP_FEAT_CHANNELS, hipMemcpyHostToDevice));
     if (d_hin) HIP_TRY(hipMemcpy(d_hin, hist_in, n * 4 * HC, hipMemcpyHostToDevice));
     if (const int rc = run(width, height, d_rgb, d_feat, prev_view, d_hin, p, d_hout, d_signal, d_var, nullptr, st, t0)) return rc;
+    HIP_TRY(hipMemcpy(hist_out, d_hout, n * 4 * HC, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(signal, d_signal, n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(variance, d_var, n * 4, hipMemcpyDeviceToHost));
+    if (st) st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return FRAYHIP_OK;
+}
+
+int frayhip_temporal_accumulate_motion_device(int width, int height, const float* d_rgb, const float* d_feat, const float* d_motion, const frayhip_view* prev_view,
+                                              const float* d_hist_in, const struct frayhip_temporal* p, float* d_hist_out, float* d_signal, float* d_variance,
+                                              void* hip_stream, frayhip_stats* st)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (const int rc = check("frayhip_temporal_accumulate_motion_device", width, height, d_rgb, d_feat, prev_view, d_hist_in, p, d_hist_out, d_signal, d_variance, true,
+                             WITH_MOTION, d_motion))
+        return rc;
+    return run(width, height, d_rgb, d_feat, prev_view, d_hist_in, p, d_hist_out, d_signal, d_variance, (hipStream_t)hip_stream, st, t0, d_motion);
+}
+
+int frayhip_temporal_accumulate_motion(int width, int height, const float* rgb, const float* feat, const float* motion, const frayhip_view* prev_view,
+                                       const float* hist_in, const struct frayhip_temporal* p, float* hist_out, float* signal, float* variance, frayhip_stats* st)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const char* who = "frayhip_temporal_accumulate_motion";
+    if (const int rc = check(who, width, height, rgb, feat, prev_view, hist_in, p, hist_out, signal, variance, false, WITH_MOTION, motion)) return rc;
+    const size_t n = (size_t)width * height;
+    const size_t HC = FRAYHIP_HISTORY_CHANNELS, MC = FRAYHIP_MOTION_CHANNELS;
+    // one allocation, the 16-byte rows first: hist_out, hist_in when given, motion, then rgb, feat, signal, variance
+    DeviceArrays B(std::string(who) + ": out of device memory");
+    float* d_hout;
+    if (const int rc = B.alloc(d_hout, n * (HC + (hist_in ? HC : 0) + MC + 3 + FRAYHIP_FEAT_CHANNELS + 3 + 1))) return rc;
+    float* d_hin = hist_in ? d_hout + HC * n : nullptr;
+    float* d_motion = d_hout + HC * n * (hist_in ? 2 : 1);
+    float* d_rgb = d_motion + MC * n;
+    float* d_feat = d_rgb + 3 * n;
+    float* d_signal = d_feat + FRAYHIP_FEAT_CHANNELS * n;
+    float* d_var = d_signal + 3 * n;
+    HIP_TRY(hipMemcpy(d_rgb, rgb, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_feat, feat, n * 4 * FRAYHIP_FEAT_CHANNELS, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_motion, motion, n * 4 * MC, hipMemcpyHostToDevice));
+    if (d_hin) HIP_TRY(hipMemcpy(d_hin, hist_in, n * 4 * HC, hipMemcpyHostToDevice));
+    if (const int rc = run(width, height, d_rgb, d_feat, prev_view, d_hin, p, d_hout, d_signal, d_var, nullptr, st, t0, d_motion)) return rc;
     HIP_TRY(hipMemcpy(hist_out, d_hout, n * 4 * HC, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(signal, d_signal, n * 12, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(variance, d_var, n * 4, hipMemcpyDeviceToHost));

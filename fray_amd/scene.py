@@ -261,32 +261,46 @@ def view_from_camera(camera, width, height):
     return v
 
 
-def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, stream=None, **params):
+def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, stream=None, motion=None, **params):
     """The temporal stage of include/frayhip.h (frayhip_temporal_accumulate): rgb [H, W, 3] and feat [H, W, 10] of the current frame, prev_view
     (view_from_camera of the previous frame's camera) and hist_in [H, W, 12] (the previous call's history), both None for the first frame;
     float32.  numpy arrays go through the host entry; torch tensors on the GPU through the device entry, on `stream` (None: the current
     stream).  params: see temporal_params.  Returns (hist_out [H, W, 12], signal [H, W, 3], variance [H, W]) of the inputs' kind -- signal and
-    variance are denoise_signal's inputs -- and with stats=True also the stats dict (ms_total, ms_kernels)."""
+    variance are denoise_signal's inputs -- and with stats=True also the stats dict (ms_total, ms_kernels).
+    motion: the motion frame [H, W, 8] of Scene.render_features_motion, of the inputs' kind (a tensor's storage 16-byte aligned): the history is
+    fetched where the pixel's surface point was before the scene's nodes moved (frayhip_temporal_accumulate_motion).  None: exactly the call
+    above."""
     p = temporal_params(**params)
     if (prev_view is None) != (hist_in is None):
         raise ValueError("temporal_accumulate: prev_view and hist_in must both be given or both be None")
     if prev_view is not None and not isinstance(prev_view, abi.View):
         raise TypeError("temporal_accumulate: prev_view must be an abi.View (view_from_camera), got %s" % type(prev_view).__name__)
     named = [("rgb", rgb, 3), ("feat", feat, abi.FEAT_CHANNELS)] + ([("hist_in", hist_in, abi.HISTORY_CHANNELS)] if hist_in is not None else [])
+    if motion is not None:
+        named.append(("motion", motion, abi.MOTION_CHANNELS))
     ins, (H, W), tensors = _frame_inputs("temporal_accumulate", named)
     hin = ins[2] if hist_in is not None else None
+    mot = ins[-1] if motion is not None else None
     view = C.byref(prev_view) if prev_view is not None else None
     st = abi.Stats()
     if not tensors:
         hist, signal, var = (np.empty((H, W, abi.HISTORY_CHANNELS), np.float32), np.empty((H, W, 3), np.float32), np.empty((H, W), np.float32))
-        _check(lib.frayhip_temporal_accumulate(W, H, _ptr(ins[0]), _ptr(ins[1]), view, _ptr(hin), C.byref(p), hist.ctypes.data, signal.ctypes.data,
-                                               var.ctypes.data, C.byref(st)))
+        if mot is not None:
+            _check(lib.frayhip_temporal_accumulate_motion(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(mot), view, _ptr(hin), C.byref(p), hist.ctypes.data,
+                                                          signal.ctypes.data, var.ctypes.data, C.byref(st)))
+        else:
+            _check(lib.frayhip_temporal_accumulate(W, H, _ptr(ins[0]), _ptr(ins[1]), view, _ptr(hin), C.byref(p), hist.ctypes.data, signal.ctypes.data,
+                                                   var.ctypes.data, C.byref(st)))
     else:
         with _DeviceCall(ins[0].device, stream) as call:
             new = lambda *shape: call.torch.empty(shape, dtype=call.torch.float32, device=ins[0].device)
             hist, signal, var = new(H, W, abi.HISTORY_CHANNELS), new(H, W, 3), new(H, W)
-            _check(lib.frayhip_temporal_accumulate_device(W, H, _ptr(ins[0]), _ptr(ins[1]), view, _ptr(hin), C.byref(p), hist.data_ptr(),
-                                                          signal.data_ptr(), var.data_ptr(), call.handle, C.byref(st)))
+            if mot is not None:
+                _check(lib.frayhip_temporal_accumulate_motion_device(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(mot), view, _ptr(hin), C.byref(p),
+                                                                     hist.data_ptr(), signal.data_ptr(), var.data_ptr(), call.handle, C.byref(st)))
+            else:
+                _check(lib.frayhip_temporal_accumulate_device(W, H, _ptr(ins[0]), _ptr(ins[1]), view, _ptr(hin), C.byref(p), hist.data_ptr(),
+                                                              signal.data_ptr(), var.data_ptr(), call.handle, C.byref(st)))
     return (hist, signal, var, st.as_dict()) if stats else (hist, signal, var)
 
 
@@ -792,6 +806,47 @@ class Scene:
         _check(lib.frayhip_render_features(self._dev, C.byref(fr), int(n_samples), feat.ctypes.data, C.byref(st)))
         return (feat, st.as_dict()) if stats else feat
 
+    def node_transforms(self):
+        """A copy of the current nodes' frayhip_transform records (self.desc's, as update() pushes them), as a ctypes array of abi.Transform: the
+        snapshot a caller takes before editing the nodes, for render_features_motion."""
+        nodes = self.nodes
+        out = (abi.Transform * len(nodes))()
+        for i, n in enumerate(nodes):
+            C.memmove(C.byref(out[i]), C.byref(n.T), C.sizeof(abi.Transform))
+        return out
+
+    def _prev_transforms(self, who, prev_transforms):
+        """prev_transforms as a ctypes array of abi.Transform (node_transforms()' kind, or a sequence of abi.Transform records)."""
+        if isinstance(prev_transforms, C.Array) and prev_transforms._type_ is abi.Transform:
+            return prev_transforms
+        seq = list(prev_transforms)
+        if not all(isinstance(t, abi.Transform) for t in seq):
+            raise TypeError("%s: prev_transforms must be Scene.node_transforms() or a sequence of abi.Transform" % who)
+        out = (abi.Transform * len(seq))()
+        for i, t in enumerate(seq):
+            C.memmove(C.byref(out[i]), C.byref(t), C.sizeof(abi.Transform))
+        return out
+
+    def render_features_motion(self, prev_transforms, n_samples=4, seed=42, bucket_first=0, bucket_stride=1, stats=False, out=None):
+        """The feature frame and the motion frame of one traced pass (frayhip_render_features_motion): (feat [H, W, 10], motion [H, W, 8]), float32.
+        prev_transforms: the nodes' transforms when the previous frame was rendered -- node_transforms() taken before the edit.  feat is
+        render_features(...), bit for bit; motion holds per pixel {P'.xyz, moved}, {n'.xyz, 0}: where the first hit and its normal were in that
+        previous state (the hit itself for a node that did not move), and the share of the pixel's samples that hit a moved node.
+        out: a (feat, motion) pair of arrays to fill instead of new zeroed ones.  With stats=True returns (feat, motion, stats dict)."""
+        self._need_dev()
+        W, H = self.frame_size
+        prev = self._prev_transforms("render_features_motion", prev_transforms)
+        feat, motion = out if out is not None else (np.zeros((H, W, abi.FEAT_CHANNELS), np.float32), np.zeros((H, W, abi.MOTION_CHANNELS), np.float32))
+        for a, ch in ((feat, abi.FEAT_CHANNELS), (motion, abi.MOTION_CHANNELS)):
+            if a.shape != (H, W, ch) or a.dtype != np.float32 or not a.flags.c_contiguous:
+                raise ValueError("render_features_motion: out must be C-contiguous float32 arrays shaped %s and %s"
+                                 % ((H, W, abi.FEAT_CHANNELS), (H, W, abi.MOTION_CHANNELS)))
+        st = abi.Stats()
+        fr = self._frame(abi.MODE_RENDER, seed, bucket_first, bucket_stride, 0, stats)
+        _check(lib.frayhip_render_features_motion(self._dev, C.byref(fr), int(n_samples), prev, len(prev), feat.ctypes.data, motion.ctypes.data,
+                                                  C.byref(st)))
+        return (feat, motion, st.as_dict()) if stats else (feat, motion)
+
     def render_denoised(self, seed=42, feature_samples=4, **params):
         """A denoised frame: (denoised, raw, stats).  raw is the ordinary frame (= render(seed), bit for bit), rendered progressively; with an even
         spp >= 2 its preview at spp / 2 samples is the filter's rgb_half (the exact spp/2 frame, no second render), otherwise the filter runs without
@@ -821,7 +876,7 @@ class Scene:
         out, dst = denoise(raw, feat, half, stats=True, **params)
         return out, raw, {"render": rst, "features": fst, "denoise": dst, "rgb_half": half, "features_frame": feat}
 
-    def render_sequence(self, cameras, seed=42, feature_samples=4, temporal=None, **denoise_params):
+    def render_sequence(self, cameras, seed=42, feature_samples=4, temporal=None, edit=None, **denoise_params):
         """A generator over a fly-through of a static scene with temporal accumulation (include/frayhip.h "temporal accumulation"): for the k-th
         abi.Camera of `cameras` it sets the view, renders the feature frame and the frame with seed + k (equal seeds would accumulate the same
         noise every frame), accumulates onto the previous frame's history reprojected into this view, runs the a-trous levels on the accumulated
@@ -831,7 +886,11 @@ class Scene:
         temporal: a dict of temporal_params fields.  film_offset defaults to where a pixel's samples lie on average: 0.5 for gi and DOF frames
         (uniform jitter), 0.3 for a Whitted frame with wantAA (the mean of the five AA offsets), 0 for a plain Whitted frame.  The filter and
         the accumulation share `demodulate` (denoise_params; default 1).  Stereo frames and long generators are refused (FrayError) as
-        render_features refuses them.  The scene's camera is restored when the generator ends or is closed."""
+        render_features refuses them.  The scene's camera is restored when the generator ends or is closed.
+        edit: None (a static scene: exactly the launches above), or a callable edit(k, scene) that is called before frame k >= 1, after the
+        snapshot of node_transforms(); it may edit the description's tables and must call scene.update() itself if it does.  With edit given,
+        every frame renders the features and the motion frame in one pass (frayhip_render_features_motion; frame 0 against its own transforms),
+        accumulates through the motion frame, and info also holds "motion" [H, W, 8].  What was edited stays edited when the generator ends."""
         self._need_dev()
         import torch
         W, H = self.frame_size
@@ -854,18 +913,31 @@ class Scene:
                     raise TypeError("render_sequence: cameras must yield abi.Camera records, got %s" % type(cam).__name__)
                 C.memmove(C.byref(self.desc.camera), C.byref(cam), C.sizeof(abi.Camera))
                 self.beginFrame()
+                motion = None
+                if edit is not None:
+                    prev = self.node_transforms()
+                    if k:
+                        edit(k, self)
                 feat = torch.empty((H, W, abi.FEAT_CHANNELS), dtype=torch.float32, device="cuda")
                 raw = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
                 fst, rst = abi.Stats(), abi.Stats()
                 fr = self._frame(abi.MODE_RENDER, (seed + k) & 0xFFFFFFFF, 0, 1, 0, False)
-                _check(lib.frayhip_render_features_device(self._dev, C.byref(fr), n_feat, feat.data_ptr(), handle, C.byref(fst)))
+                if edit is not None:
+                    motion = torch.empty((H, W, abi.MOTION_CHANNELS), dtype=torch.float32, device="cuda")
+                    _check(lib.frayhip_render_features_motion_device(self._dev, C.byref(fr), n_feat, prev, len(prev), feat.data_ptr(),
+                                                                     motion.data_ptr(), handle, C.byref(fst)))
+                else:
+                    _check(lib.frayhip_render_features_device(self._dev, C.byref(fr), n_feat, feat.data_ptr(), handle, C.byref(fst)))
                 _check(lib.frayhip_render_device(self._dev, C.byref(fr), raw.data_ptr(), None, None, handle, C.byref(rst)))
-                hist, signal, var, tst = temporal_accumulate(raw, feat, view, hist, stats=True, stream=stream, **tparams)
+                hist, signal, var, tst = temporal_accumulate(raw, feat, view, hist, stats=True, stream=stream, motion=motion, **tparams)
                 out, dst = denoise_signal(signal, var, feat, stats=True, stream=stream, **denoise_params)
                 view = view_from_camera(self.desc.camera, W, H)
-                yield out, raw, {"features_frame": feat, "history": hist, "signal": signal, "variance": var, "view": view,
-                                 "film_offset": tparams["film_offset"], "render": rst.as_dict(), "features": fst.as_dict(), "temporal": tst,
-                                 "denoise": dst}
+                info = {"features_frame": feat, "history": hist, "signal": signal, "variance": var, "view": view,
+                        "film_offset": tparams["film_offset"], "render": rst.as_dict(), "features": fst.as_dict(), "temporal": tst,
+                        "denoise": dst}
+                if edit is not None:
+                    info["motion"] = motion
+                yield out, raw, info
         finally:
             if self.desc is not None:
                 C.memmove(C.byref(self.desc.camera), C.byref(saved), C.sizeof(abi.Camera))

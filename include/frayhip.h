@@ -679,6 +679,34 @@ int  frayhip_render_features(frayhip_scene* s, const frayhip_frame* f, int n_sam
 int  frayhip_render_features_device(frayhip_scene* s, const frayhip_frame* f, int n_samples, float* d_feat,
                                     void* hip_stream, frayhip_stats* st);
 
+/* ---- motion frames (where the first hit was in the previous frame's state of the scene) ------------------------------------------------------
+ * frayhip_render_features with a second output for temporal accumulation across frayhip_scene_update: prev_T (a HOST pointer in both entries,
+ * n_prev records, n_prev = the uploaded scene's node count) holds the transforms the scene's nodes had when the previous frame was rendered.
+ * Node i is MOVED when any of the 21 doubles of prev_T[i] differs by bit pattern from the node's current {offset, m, invM}.
+ * One traced pass writes both frames.  feat is what frayhip_render_features writes, bit for bit.  motion: eight floats per pixel, two 16-byte
+ * rows, motion[(y * W + x) * FRAYHIP_MOTION_CHANNELS + k]:  0..2 P', 3 moved, 4..6 n', 7 zero.  Per sample:
+ *   a node that is not moved   P' = the sample's ip, n' = its norm after the bump (the FP64 values the feature frame converts), moved = 0
+ *   moved node i               P' = ((ip - off_now) * invM_now) * m_prev + off_prev      Transform::untransformPoint of the transform now, then
+ *                              n' = (norm * invM_now) * m_prev                            transformPoint of the previous one; moved = 1
+ *                              FP64, no contraction; each product is Vector * Matrix of matrix.h:53-60, (v.x m[0][j] + v.y m[1][j]) + v.z m[2][j];
+ *                              n' is carried the way Node::intersect carries a normal (through m, not the inverse transpose) and not rescaled
+ *   rect light, or miss        P', n' as the feature frame's position and normal, moved = 0
+ * Each value is converted to float per sample, summed in float in sample order and divided by (float)n_samples, as the feature channels are
+ * (so `moved` is the share of the pixel's samples that hit a moved node).  maxTraceDepth < 0: all zeros.
+ * The previous {offset, m} and a moved byte per node go to a small device table that every call fills; the scene keeps its allocation, so
+ * a call in a sequence allocates nothing.
+ * Everything else is frayhip_render_features' contract: buckets, untouched pixels outside them, options and last-frame figures left alone, *st,
+ * and the stream contract of the _device entry (both device pointers 4-byte aligned).
+ * FRAYHIP_E_ARG, before the device is touched: what frayhip_render_features refuses, a NULL prev_T or motion, n_prev != the node count, a
+ *   non-finite double in prev_T, feat and motion overlapping.  FRAYHIP_E_UNSUPPORTED: as there.
+ * Not covered: moved lights; shadows and reflections of moved objects (their pixels' first hits did not move, so they ghost as in a static
+ *   sequence); motion blur; vertex edits (frayhip_scene_update does not take them). */
+#define FRAYHIP_MOTION_CHANNELS 8   /* per pixel, two 16-byte rows: {P'.xyz, moved}, {n'.xyz, 0} */
+int  frayhip_render_features_motion(frayhip_scene* s, const frayhip_frame* f, int n_samples, const frayhip_transform* prev_T, int n_prev,
+                                    float* feat, float* motion, frayhip_stats* st);
+int  frayhip_render_features_motion_device(frayhip_scene* s, const frayhip_frame* f, int n_samples, const frayhip_transform* prev_T, int n_prev,
+                                           float* d_feat, float* d_motion, void* hip_stream, frayhip_stats* st);
+
 /* ---- denoising (edge-avoiding a-trous wavelet filter, scene-free) --------------------------------------------------------------------------
  * A spatial SVGF-style filter of an rgb frame (W*H*3 floats) guided by a feature frame (W*H*FRAYHIP_FEAT_CHANNELS floats, as
  * frayhip_render_features writes it), FP32 throughout, no contraction.  Level k = 0 .. levels - 1 takes the taps q = p + 2^k (i, j),
@@ -794,8 +822,22 @@ int  frayhip_temporal_accumulate(int width, int height, const float* rgb, const 
 int  frayhip_temporal_accumulate_device(int width, int height, const float* d_rgb, const float* d_feat, const frayhip_view* prev_view,
                                         const float* d_hist_in, const struct frayhip_temporal* p, float* d_hist_out, float* d_signal,
                                         float* d_variance, void* hip_stream, frayhip_stats* st);
-/* Not covered: SVGF's wider 3 x 3 retry when no bilinear tap counts, feeding a filtered level back into the history, moving objects (the scene
- * is static between frames), specular motion vectors (what a mirror shows moves with the camera while its first hit does not), learned
+/* The same with a motion frame (frayhip_render_features_motion; W*H*FRAYHIP_MOTION_CHANNELS floats, 16-byte aligned on the device): step 2
+ * projects the pixel's P' into prev_view instead of P, and the taps are tested against P' and against n' scaled to unit length the way the
+ * normal is (exactly zero stays zero): n' . n_q >= normal_min_dot and |(P_q - P') . n'| <= plane_tolerance * |P' - pos_prev|.  A pixel whose
+ * current normal is exactly zero takes no history, and neither does one whose n' is exactly zero.  hist_out stores the CURRENT position and unit
+ * normal; steps 1, 3 and 4 (k_tp_variance on the finished hist_out) are unchanged.  With a motion frame whose P', n' equal feat's position and
+ * normal (nothing moved) every output bit is frayhip_temporal_accumulate's.  FRAYHIP_E_ARG: that entry's list, and a NULL, overlapping (with an
+ * output) or misaligned motion. */
+int  frayhip_temporal_accumulate_motion(int width, int height, const float* rgb, const float* feat, const float* motion, const frayhip_view* prev_view,
+                                        const float* hist_in, const struct frayhip_temporal* p, float* hist_out, float* signal, float* variance,
+                                        frayhip_stats* st);
+int  frayhip_temporal_accumulate_motion_device(int width, int height, const float* d_rgb, const float* d_feat, const float* d_motion,
+                                               const frayhip_view* prev_view, const float* d_hist_in, const struct frayhip_temporal* p,
+                                               float* d_hist_out, float* d_signal, float* d_variance, void* hip_stream, frayhip_stats* st);
+/* Not covered: SVGF's wider 3 x 3 retry when no bilinear tap counts, feeding a filtered level back into the history, moved lights and the
+ * shadows and reflections of moved objects (only a pixel's own first hit is carried back: frayhip_render_features_motion), motion blur,
+ * specular motion vectors (what a mirror shows moves with the camera while its first hit does not), learned
  * denoisers, adaptive and stereo frames, and denoising across ranks (gather the frame and its features first: frayhip_gather_buckets takes a
  * channel count). */
 
