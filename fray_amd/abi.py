@@ -17,6 +17,13 @@ SHADER_CONST, SHADER_LAMBERT, SHADER_PHONG, SHADER_REFL, SHADER_REFR, SHADER_LAY
 LIGHT_POINT, LIGHT_RECT = range(2)
 MODE_PRIMARY_ID, MODE_RENDER = 0, 1
 FRAME_STATS = 1
+# the names frayhip_scene_set_option accepts, and what frayhip_scene_get_option reports besides them (tests/test_call_history.py holds both to capi.hip)
+OPTION_NAMES = ("pt_lanes", "pt_budget_mib", "speculate_fans", "fused_whitted_max", "fp_contract", "seed_table_mib", "skip_null_segments",
+                "segment_planes", "certified_segments")
+FIGURE_NAMES = ("contracted_launches", "shadow_segments", "segment_plane_nodes", "certified_segments_eligible", "shadow_segments_certified",
+                "shadow_nodes_skipped", "seed_table_bytes", "seed_launches", "seed_planes_reused", "batch_lanes", "whitted_path",
+                "pt_budget_effective_mib", "scene_updates", "scene_update_bytes", "arena_bytes", "fans_filed", "fan_children",
+                "fan_children_looked_up", "fans_given_up")
 
 
 class Transform(C.Structure):

@@ -502,7 +502,8 @@ class Scene:
             self._dev = C.c_void_p()
 
     def set_option(self, name, value):
-        """frayhip_scene_set_option: "pt_lanes" (1..4 batches in flight), "pt_budget_mib" (queue memory), "speculate_fans" (0 / 1), "fp_contract" (0 / 1: relaxed arithmetic
+        """frayhip_scene_set_option: "pt_lanes" (1..4 batches in flight), "pt_budget_mib" (queue memory), "speculate_fans" (0 / 1), "fused_whitted_max" (0..1024: the light samples per hit
+        up to which a Whitted frame without recursive shaders and KD meshes runs the fused shade kernel), "fp_contract" (0 / 1: relaxed arithmetic
         for path-traced rays after a sample's first closest hit, include/frayhip.h), "skip_null_segments" (0 / 1: next-event samples that are black by bit pattern are not traced),
         "segment_planes" (0 / 1: the path tracer's any-hit kernel skips, per wave, the small untransformed meshes whose triangles' planes no next-event segment of the wave crosses),
         "certified_segments" (0 / 1: in a scene of such meshes and exactly gated ones only, the bounce kernel stores the term of a next-event segment proven unoccluded itself, without a query),

@@ -1,0 +1,229 @@
+"""An entry's answer must not depend on what the handle did before (DESIGN.md "What the call histories show").
+
+A frayhip_scene keeps a workspace that every entry carves up by a layout of its own, a statistics block with three sets of tile cursors, queue
+tables, a seed table under a key, a warm mask, an effective budget that shrinks, a motion table, event pools and lane streams (render_state.hpp).
+A kernel that reads a word it did not write this call -- a term count, a running sum, a cursor, a queue slot past the counted end, a seed plane of
+another key -- gets away with it on a handle that has done little else.  So here every operation of tests/call_history.py (a complete configuration
+plus one call) first runs as the first call of a fresh handle; the plain frames, hit records and primary hits of those baselines are held to the CPU
+oracle by the suite's rules; and then the operations run in orders that put every one directly after every other, on one handle, on two handles in
+turn, after the largest and the smallest workspace and on memory a destroyed handle has just given back.  Every answer must be the baseline's bytes."""
+import random
+import time
+
+import numpy as np
+import pytest
+
+import call_history as ch
+import hostlane as hl
+from test_gpu_parity import RMS_TOL, rms
+from test_gpu_rays import _check_records
+from test_trace_host import ADVERSARIAL, flag_word
+
+pytestmark = pytest.mark.gpu
+
+SEED = 11
+ARC = 201               # calls per arc of the circuit: eight arcs a scene, measured 0.17 to 0.95 s each (DESIGN.md "What the call histories show")
+WORDS = dict(ch.SCENES_BY_WORD)
+
+# Figures of frayhip_scene_get_option that may depend on what ran before, each for a reason in the code:
+HISTORY_FIGURES = (
+    "seed_launches",            # seed_batch launches k_seed only for planes the table does not hold valid: a frame after one of the same key launches none
+    "seed_planes_reused",       # ... and counts the planes it took from the table instead
+    "seed_table_bytes",         # seed_table_begin keeps the allocation across keys and only grows it
+    "scene_updates",            # frayhip_scene_update counts its calls since creation
+    "scene_update_bytes",       # ... and keeps the bytes of the last one
+)
+# ... "arena_bytes" is compared until the handle's first update (not_compared below): the arena is sized at creation, and the issue lets it move across edits;
+# "pt_budget_effective_mib" is always compared: every operation sets pt_budget_mib, which makes work_budget() clamp again at the next frame;
+# and a figure "of the last frame" is compared after the calls that write it (call_history.OWNED): any other call leaves the frame before's in place.
+# This last rule departs from the issue's list, which holds shadow_segments, shadow_segments_certified, shadow_nodes_skipped, contracted_launches, batch_lanes,
+# whitted_path and the fan figures equal after EVERY call: they are equal after every call that writes them, and after any other call they are the frame
+# before's by construction (after render_adaptive too, which writes only the contracted and fan figures: DESIGN.md names that as a quirk of adaptive_impl).
+# Everything else -- the arrays, the stats counters, every other figure -- must be equal.
+
+
+def not_compared(handle, op):
+    out = ["fig:" + k for k in HISTORY_FIGURES]
+    out += ["fig:" + k for k in ch.LAST_FRAME_FIGURES if k not in ch.OWNED[op.kind]]
+    if handle.edited:
+        out.append("fig:arena_bytes")
+    return out
+
+
+def circuit(name):
+    return ch.arcs(ch.euler(len(ch.operations(name)), SEED + WORDS[name]), ARC)
+
+
+def free_bytes():
+    import torch
+    return torch.cuda.mem_get_info()[0]
+
+
+class Case:
+    """a scene's handle, its operations and their baselines: each operation as the first call of a fresh handle"""
+
+    def __init__(self, fray, name, tmp):
+        self.name = name
+        self.handle = ch.Handle(fray, name, ADVERSARIAL[name][0](tmp))
+        assert flag_word(self.handle.s.desc) == WORDS[name]
+        self.ops = ch.operations(name)
+        self.base, self.seconds = [], []
+        for op in self.ops:
+            self.handle.renew()
+            before, t0 = free_bytes(), time.perf_counter()
+            self.base.append(self.handle.run(op))
+            self.seconds.append(time.perf_counter() - t0)
+            op.work = max(0, before - free_bytes())          # what the call left allocated behind the handle: the workspace, above all
+        self.index = {op.name: i for i, op in enumerate(self.ops)}
+
+    def answer(self, op_name):
+        return self.base[self.index[op_name]]
+
+    def check(self, found, seconds, calls):
+        print("%s: %d calls in %.2f s, %d differ" % (self.name, calls, seconds, len(found)))
+        assert not found, "%d of %d calls differ from their baselines:\n  %s" % (len(found), calls, "\n  ".join(repr(f) for f in found[:12]))
+
+
+@pytest.fixture(scope="module")
+def cases(fray, gpu, tmp_path_factory):
+    made = {}
+
+    def get(name):
+        if name not in made:
+            t0 = time.perf_counter()
+            made[name] = Case(fray, name, tmp_path_factory.mktemp("call_history_" + name))
+            c = made[name]
+            slow = sorted(zip(c.seconds, (o.name for o in c.ops)), reverse=True)[:3]
+            big = sorted(((o.work, o.name) for o in c.ops), reverse=True)[:2]
+            print("%s: %d baselines in %.2f s (the calls %.2f s; slowest %s; largest workspace %s)"
+                  % (name, len(c.ops), time.perf_counter() - t0, sum(c.seconds), ", ".join("%s %.0f ms" % (n, 1e3 * s) for s, n in slow),
+                     ", ".join("%s %.0f MiB" % (n, w / 2.0 ** 20) for w, n in big)))
+        return made[name]
+    yield get
+    for c in made.values():
+        c.handle.close()
+
+
+# ---- the baselines, against the oracle ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ch.SCENES)
+def test_baselines_equal_the_oracle(fray, abi, oracle, cases, name):
+    """the plain path-traced frame, the Whitted frame, the primary hits and the hit records of each scene by the suite's own rules (test_gpu_parity, test_gpu_rays):
+    the comparisons below are the GPU against itself, and this is what ties them to the reference"""
+    c = cases(name)
+    h = c.handle.renew()
+
+    def described(op_name):
+        h.configure(c.ops[c.index[op_name]])
+        return h.s.desc
+    ref, _ = oracle.render(described("pt"), abi.MODE_RENDER, seed=42)
+    img = c.answer("pt")["rgb"]
+    same = float((img == ref).all(axis=2).mean())
+    print("%s pt: %.2f %% of the pixels bit-identical to the oracle, rms %s" % (name, 100 * same, rms(img, ref)))
+    assert np.all(np.isfinite(img)) and ref.mean() > 1e-3 and np.all(rms(img, ref) <= RMS_TOL), rms(img, ref)
+    assert same >= 0.995, same                      # test_textured_scene_without_kd_meshes_vs_oracle's share: a last-place difference of a direction may flip a branch
+    ref, _ = oracle.render(described("whitted"), abi.MODE_RENDER, seed=42)
+    img = c.answer("whitted")["rgb"]
+    assert ref.mean() > 1e-3 and np.all(rms(img, ref) <= RMS_TOL) and (img == ref).all(), (name, "whitted", rms(img, ref), float((img == ref).all(axis=2).mean()))
+    oi, od, _ = oracle.render(described("primary"), abi.MODE_PRIMARY_ID)
+    assert np.array_equal(c.answer("primary")["ids"], oi) and np.array_equal(c.answer("primary")["dist"], od), (name, "primary")
+    desc = described("trace-rays")
+    o, d = ch._rows(h, 2)
+    ids, rec = hl.oracle_probe(oracle, desc, o, d)
+    got = c.answer("trace-rays")
+    assert (ids != -1).mean() > 0.2
+    _check_records(h.s, {"hit_id": ids, "hit_rec": rec}, got["hit_id"], got["hit_rec"], name + " trace-rays")
+    assert np.array_equal(got["hit_dist"], got["hit_rec"][:, 0])
+
+
+def test_a_fresh_handle_has_the_defaults_and_accepts_every_option(fray, abi, cases):
+    """the library itself asked for the names of abi.OPTION_NAMES: each reads back call_history's default on a fresh handle and is accepted; another name is refused"""
+    s = cases("textured_plain").handle.renew().s
+    assert {k: s.get_option(k) for k in abi.OPTION_NAMES} == ch.OPTION_DEFAULTS
+    for k in abi.OPTION_NAMES:
+        s.set_option(k, ch.OPTION_DEFAULTS[k])
+    for k in abi.FIGURE_NAMES + ("no_such_option",):
+        with pytest.raises(fray.FrayError) as e:
+            s.set_option(k, 1)
+        assert e.value.code == abi.E_ARG and "unknown option" in str(e.value), k
+    for k in abi.FIGURE_NAMES:
+        s.get_option(k)
+
+
+def test_the_three_whitted_paths_occur(cases):
+    seen = {}
+    for name in ch.SCENES:
+        c = cases(name)
+        for op in c.ops:
+            if op.kind == "whitted":
+                seen.setdefault(c.answer(op.name)["fig:whitted_path"], []).append("%s:%s" % (name, op.name))
+    print(seen)
+    assert set(seen) == {0, 1, 2}, seen
+
+
+def test_the_circuits_cover_every_ordered_pair():
+    for name in ch.SCENES:
+        n = len(ch.operations(name))
+        assert n >= 15
+        assert ch.adjacent_pairs(circuit(name)) == {(a, b) for a in range(n) for b in range(n)}, name
+
+
+# ---- every operation directly after every other ----------------------------------------------------------------------------------------------------
+ARCS = [(name, k) for name in ch.SCENES for k in range(len(circuit(name)))]
+
+
+@pytest.mark.parametrize("name,k", ARCS, ids=["%s-arc%d" % a for a in ARCS])
+def test_circuit(cases, name, k):
+    c = cases(name)
+    arc = circuit(name)[k]
+    t0 = time.perf_counter()
+    found = ch.run_walk(c.handle.renew(), c.ops, arc, c.base, not_compared, label="%s arc %d" % (name, k))
+    c.check(found, time.perf_counter() - t0, len(arc))
+
+
+@pytest.mark.parametrize("name", ch.SCENES)
+def test_after_the_largest_and_the_smallest_workspace(cases, name):
+    c = cases(name)
+    walk = ch.big_then_small(c.ops)
+    print("%s: largest workspace %s, smallest %s" % (name, c.ops[walk[0]].name, c.ops[walk[2]].name))
+    t0 = time.perf_counter()
+    found = ch.run_walk(c.handle.renew(), c.ops, walk, c.base, not_compared, label=name + " big then small")
+    c.check(found, time.perf_counter() - t0, len(walk))
+
+
+# ---- two handles alive together: process-wide state ------------------------------------------------------------------------------------------------
+def test_two_handles_in_turn(cases):
+    a, b = cases("cornell_box"), cases("csg_nested")
+    a.handle.renew()
+    b.handle.renew()
+    walks = []
+    for c, seed in ((a, SEED), (b, SEED + 1)):
+        order = list(range(len(c.ops)))
+        random.Random(seed).shuffle(order)
+        walks.append(order + order[::-1])               # every operation twice, with other neighbours -- its own handle's, and the other handle's in between
+    calls = ch.two_handles(*walks)
+    t0 = time.perf_counter()
+    found = ch.run_two([a.handle, b.handle], [a.ops, b.ops], calls, [a.base, b.base], not_compared, label="cornell_box | csg_nested")
+    a.check(found, time.perf_counter() - t0, len(calls))
+
+
+# ---- memory a destroyed handle has just given back ---------------------------------------------------------------------------------------------------
+RECYCLED = ("pt", "pt-stats", "samples-3-5", "adaptive", "shade-paths")
+
+
+@pytest.mark.parametrize("name", ch.SCENES)
+def test_first_answers_on_recycled_memory(cases, name):
+    """the frame with the largest workspace per path (long generators, both eyes), the handle destroyed, a new one created at once, and its first answer
+    must be the baseline's.  That the allocator hands the new handle the old one's memory cannot be seen through the ABI (no entry reports an address);
+    what can be seen is printed: the device's free bytes before the frame, after it and after the handle was destroyed and made again."""
+    c = cases(name)
+    dirty = ch.Op("pt-deep-stereo", ch.frame(), dict(frameWidth=32, frameHeight=24, maxTraceDepth=40), camera=dict(stereoSeparation=True))
+    found, t0 = [], time.perf_counter()
+    for op_name in RECYCLED:
+        h = c.handle.renew()
+        f0 = free_bytes()
+        h.run(dirty)
+        f1 = free_bytes()
+        h.renew()
+        print("%s before %s: the frame took %.0f MiB, destroying its handle gave %.0f MiB back" % (name, op_name, (f0 - f1) / 2.0 ** 20, (free_bytes() - f1) / 2.0 ** 20))
+        found += ch.run_walk(h, c.ops, [c.index[op_name]], c.base, not_compared, label=name + " recycled", predecessor="(destroyed) pt-deep-stereo")
+    c.check(found, time.perf_counter() - t0, len(RECYCLED))
