@@ -15,7 +15,10 @@ src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --he
                                                                                           its history fetched where the moved nodes' surfaces were)
                          python -m fray_amd scene.fray -o out.bmp --accumulate FILE.npz [--spp N] [--noise-out FILE.npy] [--time-limit SECONDS]
                                                                                          (N more samples per pixel on top of the state in FILE.npz, which
-                                                                                          is started when it does not exist; the picture of all of them)"""
+                                                                                          is started when it does not exist; the picture of all of them)
+                         python -m fray_amd scene.fray -o out.bmp --components-out FILE.npz [--denoise --split]   (path-traced mono frames: direct and
+                                                                                         indirect light kept apart and saved with their noise estimates;
+                                                                                          --denoise --split: each filtered on its own, then added)"""
 import argparse
 import json
 import os
@@ -74,6 +77,12 @@ def build_parser():
                          "state of another size or seed is refused.  With --time-limit the state that was cut short is saved and can be continued")
     ap.add_argument("--noise-out", metavar="FILE.npy",
                     help="with --accumulate: also save the noise buffer, float32 [H, W] (the variance estimate of the mean's luminance)")
+    ap.add_argument("--components-out", metavar="FILE.npz",
+                    help="component frame (Scene.render_components; path-traced mono frames): render the frame's samples with direct and indirect light "
+                         "kept apart and save direct, indirect, noise_direct, noise_indirect, samples and seed; the picture is their sum")
+    ap.add_argument("--split", action="store_true",
+                    help="with --denoise: filter direct and indirect light apart and add the results (Scene.render_denoised_split); path-traced mono "
+                         "frames only, not with --adaptive")
     return ap
 
 
@@ -125,6 +134,32 @@ def check_args(ap, a):
         ap.error("--noise-out needs --accumulate")
     if a.spp is not None and a.accumulate and a.spp < 1:
         ap.error("--spp must be >= 1")
+    if a.split and a.adaptive is not None:
+        ap.error("--split cannot be combined with --adaptive")
+    if a.split and not a.denoise:
+        ap.error("--split needs --denoise")
+    if (a.split or a.components_out) and (a.frames is not None or a.accumulate or a.probe or a.adaptive is not None or a.time_limit is not None):
+        ap.error("--split and --components-out cannot be combined with --frames, --accumulate, --probe, --adaptive or --time-limit")
+    if a.components_out and a.denoise and not a.split:
+        ap.error("--components-out with --denoise needs --split")
+
+
+def check_components(ap, a, s):
+    """--split and --components-out, once the scene is parsed (before it is uploaded): a component frame is a mono path-traced frame."""
+    if not (a.split or a.components_out):
+        return
+    flag = "--split" if a.split else "--components-out"
+    if not s.settings.gi:
+        ap.error("%s needs a path-traced scene (gi on): a Whitted frame has no direct / indirect split" % flag)
+    if s.camera.stereoSeparation > 0:
+        ap.error("%s is not offered for stereo frames" % flag)
+
+
+def save_components(path, direct, indirect, noise_direct, noise_indirect, samples, seed):
+    with open(path, "wb") as f:
+        np.savez(f, direct=direct, indirect=indirect, noise_direct=noise_direct, noise_indirect=noise_indirect, samples=np.int64(samples),
+                 seed=np.uint32(int(seed) & 0xffffffff))
+    print("wrote", path)
 
 
 def load_accumulation(ap, a, s):
@@ -181,6 +216,7 @@ def main(argv=None):
             ap.error("--move: the scene has %d nodes, no node %d" % (s.desc.n_nodes, int(m[0])))
     if a.yaw_step is None:
         a.yaw_step = 0.0 if a.move else 1.0
+    check_components(ap, a, s)
     state = load_accumulation(ap, a, s) if a.accumulate else None
     s.beginRender(a.device)
     if a.probe:
@@ -220,7 +256,22 @@ def main(argv=None):
                 move_nodes(s, a.move)           # the generator renders the next frame when it is asked for it: after this edit
         print("Rendered %d frames in %.2fs" % (a.frames, time.time() - t0))
         return 0
-    if a.denoise:
+    if a.denoise and a.split:
+        img, raw, info = s.render_denoised_split(seed=a.seed, feature_samples=a.feature_samples)
+        st = info["render"]
+        spp_text = "%d spp, direct and indirect light denoised apart: features %.1f ms, filters %.1f + %.1f ms" % (
+            s.samples_per_pixel(), info["features"]["ms_kernels"], info["denoise_direct"]["ms_kernels"], info["denoise_indirect"]["ms_kernels"])
+        if a.features_out:
+            np.save(a.features_out, info["features_frame"])
+        if a.components_out:
+            save_components(a.components_out, info["direct_rgb"], info["indirect_rgb"], info["noise_direct"], info["noise_indirect"],
+                            s.samples_per_pixel(), a.seed)
+    elif a.components_out:
+        direct, indirect, _state, nd, ni, st = s.render_components(s.samples_per_pixel(), seed=a.seed, noise=True, stats=True)
+        img = direct + indirect
+        spp_text = "%d spp, direct and indirect light kept apart" % s.samples_per_pixel()
+        save_components(a.components_out, direct, indirect, nd, ni, s.samples_per_pixel(), a.seed)
+    elif a.denoise:
         img, raw, info = s.render_denoised(seed=a.seed, feature_samples=a.feature_samples)
         st = info["render"]
         spp_text = "%d spp, denoised%s: features %.1f ms, filter %.1f ms" % (

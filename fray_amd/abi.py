@@ -245,6 +245,8 @@ SYMBOLS = {
     "frayhip_render_device_adaptive": (C.c_int, [VP, P(Frame), P(Adaptive), VP, VP, VP, VP, P(Stats)]),
     "frayhip_render_samples": (C.c_int, [VP, P(Frame), P(Samples), P(Progressive), VP, VP, VP, P(Stats)]),
     "frayhip_render_samples_device": (C.c_int, [VP, P(Frame), P(Samples), P(Progressive), VP, VP, VP, VP, P(Stats)]),
+    "frayhip_render_components": (C.c_int, [VP, P(Frame), P(Samples), P(Progressive), VP, VP, VP, VP, VP, VP, P(Stats)]),
+    "frayhip_render_components_device": (C.c_int, [VP, P(Frame), P(Samples), P(Progressive), VP, VP, VP, VP, VP, VP, VP, P(Stats)]),
     "frayhip_render_features": (C.c_int, [VP, P(Frame), C.c_int, VP, P(Stats)]),
     "frayhip_render_features_device": (C.c_int, [VP, P(Frame), C.c_int, VP, VP, P(Stats)]),
     "frayhip_render_features_motion": (C.c_int, [VP, P(Frame), C.c_int, P(Transform), C.c_int, VP, VP, P(Stats)]),

@@ -137,7 +137,10 @@ struct Batches {
     int samples_after(int r) const { return std::min(total, first + (r + 1) * chunk); }          // ... batch r was resolved
     void mean(hipStream_t ls, int n, bool withNoise) const
     {
-        if (acc) launch_acc_mean(grid_for(nItems), ls, F, nItems, n, acc->accum, d_rgb, withNoise ? acc->noise : nullptr);
+        if (acc) {
+            launch_acc_mean(grid_for(nItems), ls, F, nItems, n, acc->accum, acc->accum2 ? acc->rgb1 : d_rgb, withNoise ? acc->noise : nullptr);
+            if (acc->accum2) launch_acc_mean(grid_for(nItems), ls, F, nItems, n, acc->accum2, acc->rgb2, withNoise ? acc->noise2 : nullptr);
+        }
         else hipLaunchKernelGGL(k_resolve_mean, dim3(grid_for(nItems)), dim3(256), 0, ls, F, nItems, n, (const float*)sum, d_rgb);
     }
     bool preview_due()
@@ -195,7 +198,7 @@ struct Batches {
     {
         if (acc) {
             acc->done = samplesDone;
-            if ((d_rgb || acc->noise) && nItems > 0 && samplesDone > 0) mean(stream, samplesDone, true);
+            if ((d_rgb || acc->noise || acc->rgb1 || acc->rgb2 || acc->noise2) && nItems > 0 && samplesDone > 0) mean(stream, samplesDone, true);
         } else if (cut_short() && d_rgb && sum && samplesDone > 0) mean(stream, samplesDone, false);
     }
 };
@@ -205,7 +208,7 @@ template <int ST>
 int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t* d_id, double* d_dist, hipStream_t stream, frayhip_stats* st, const Progress* prog,
                 AccumCall* acc)
 {
-    const char* const who = acc ? "frayhip_render_samples" : "frayhip_render";
+    const char* const who = acc ? acc->who : "frayhip_render";
     const auto t0 = std::chrono::steady_clock::now();
     const frayhip_settings& set = sc->settings;
     const int W = set.frameWidth, H = set.frameHeight;
@@ -252,6 +255,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
         if (set.maxTraceDepth < 0) {
             if (nItems > 0 && acc) launch_acc_black(grid_for(nItems), stream, F, nItems, first, spp, sc->camera.stereoSeparation > 0 ? 2 : 1, acc->accum, sc->d_stats);
             else if (nItems > 0) hipLaunchKernelGGL(k_black, dim3(grid_for(nItems)), dim3(256), 0, stream, F, nItems, sc->camera.stereoSeparation > 0 ? 2 : 1, d_rgb, sc->d_stats);
+            if (nItems > 0 && acc && acc->accum2) launch_acc_black(grid_for(nItems), stream, F, nItems, first, spp, 0, acc->accum2, sc->d_stats);          // no eyes: the samples were counted by the first launch
         } else if (!set.gi) {
             if (!acc && !F.jitter && spp > 5) { set_error("frayhip_render: bad sample count"); return FRAYHIP_E_ARG; }
             sc->lastWhittedPath = 0;
@@ -634,6 +638,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 // the running per-pixel sum takes the batches in sample order (evResolved is recorded after each resolve, Batches::run)
                 if (batch > 0 && nLanes > 1) HIP_TRY(hipStreamWaitEvent(ls, sc->evResolved[(batch - 1) % nLanes], 0));
                 if (acc && stereo) launch_acc_resolve(grid_for(nItems), ls, F, C, set.saturation, nItems, s0, cn, L.sampleRad, L.sampleRadR, acc->accum);
+                else if (acc && acc->accum2) launch_acc_resolve_terms_split(grid_for(nItems), ls, F, nItems, s0, cn, TermBuf{L.terms, L.termCount, (uint32_t)nPaths, 0}, acc->accum, acc->accum2);
                 else if (acc) launch_acc_resolve_terms(grid_for(nItems), ls, F, nItems, s0, cn, TermBuf{L.terms, L.termCount, (uint32_t)nPaths, 0}, acc->accum);
                 else if (stereo) hipLaunchKernelGGL(k_pt_resolve, dim3(grid_for(nItems)), dim3(256), 0, ls, F, C, set.saturation, nItems, s0, cn, L.sampleRad, L.sampleRadR, sum, d_rgb);
                 else hipLaunchKernelGGL(k_pt_resolve_terms, dim3(grid_for(nItems)), dim3(256), 0, ls, F, nItems, s0, cn, TermBuf{L.terms, L.termCount, (uint32_t)nPaths, 0}, sum, d_rgb);

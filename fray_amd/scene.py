@@ -743,6 +743,70 @@ class Scene:
         out = (rgb, state) + ((var,) if noise else ())
         return out + ((info,) if (stats or progress is not None) else ())
 
+    # ---- component frames (include/frayhip.h "component frames") ----
+    def render_components(self, count, state=None, seed=42, bucket_first=0, bucket_stride=1, spp_chunk=0, stats=False, progress=None, noise=False,
+                          stream=None):
+        """render_samples with direct and indirect light kept apart (frayhip_render_components; mono path-traced frames): `count` more samples per
+        pixel into a pair of states, state = (direct, indirect), two Accumulations of one kind (numpy: the host entry; GPU tensors: the device
+        entry, on `stream`), or None to start a numpy pair.  A sample's direct light is its path's first term, its indirect light the fold of the
+        others, and direct + indirect is render_samples' sample colour in one FP32 addition, bit for bit.
+
+        Returns (direct_rgb, indirect_rgb, state[, noise_direct, noise_indirect][, stats]): each rgb float32 [H, W, 3] is the mean of its
+        component over all samples the states hold, `state` is the pair given, updated in place, and noise=True adds each component's variance
+        estimate, float32 [H, W] (denoise_signal's variance, with demodulate=0).  The stats dict follows with stats=True or a progress callback.
+        progress: as render_samples, but no previews are offered.  A cancelled call returns normally with stats["cancelled"] set and both states
+        at the samples resolved.  ValueError when the two states disagree in seed, size, share, kind or samples_done, or belong to another
+        frame."""
+        who = "render_components"
+        count = int(count)
+        if count < 1:
+            raise ValueError("%s: count must be >= 1, got %d" % (who, count))
+        W, H = self.frame_size
+        if state is None:
+            state = (Accumulation.empty((W, H), seed, bucket_first, bucket_stride), Accumulation.empty((W, H), seed, bucket_first, bucket_stride))
+        elif not (isinstance(state, (tuple, list)) and len(state) == 2 and all(isinstance(a, Accumulation) for a in state)):
+            raise TypeError("%s: state must be a pair (direct, indirect) of Accumulations" % who)
+        sd, si = state
+        for a in (sd, si):
+            a.check(who, (W, H), seed, bucket_first, bucket_stride)
+        if sd is si or sd.state is si.state:
+            raise ValueError("%s: the direct and the indirect state are the same object" % who)
+        if sd.on_device != si.on_device:
+            raise ValueError("%s: one state is a numpy array and the other a GPU tensor" % who)
+        if sd.on_device and sd.state.device != si.state.device:
+            raise ValueError("%s: the states are on different devices" % who)
+        if sd.samples_done != si.samples_done:
+            raise ValueError("%s: the direct state holds %d samples per pixel, the indirect state %d" % (who, sd.samples_done, si.samples_done))
+        self._need_dev()
+        st = abi.Stats()
+        fr = self._frame(abi.MODE_RENDER, sd.seed, bucket_first, bucket_stride, spp_chunk, stats)
+        req = abi.Samples(sample_first=sd.samples_done, sample_count=count)
+        preq, run = None, None
+        if progress is not None:
+            preq, run = _progress_request(progress, -1, lambda p: {})
+        pp = C.byref(preq) if preq is not None else None
+        if not sd.on_device:
+            rgb = [np.zeros((H, W, 3), np.float32) for _ in range(2)]
+            var = [np.zeros((H, W), np.float32) if noise else None for _ in range(2)]
+            rc = lib.frayhip_render_components(self._dev, C.byref(fr), C.byref(req), pp, _ptr(sd.state), _ptr(si.state), _ptr(rgb[0]), _ptr(rgb[1]),
+                                               _ptr(var[0]), _ptr(var[1]), C.byref(st))
+        else:
+            with _DeviceCall(sd.state.device, stream) as call:
+                rgb = [call.torch.zeros((H, W, 3), dtype=call.torch.float32, device=sd.state.device) for _ in range(2)]
+                var = [call.torch.zeros((H, W), dtype=call.torch.float32, device=sd.state.device) if noise else None for _ in range(2)]
+                rc = lib.frayhip_render_components_device(self._dev, C.byref(fr), C.byref(req), pp, _ptr(sd.state), _ptr(si.state), _ptr(rgb[0]),
+                                                          _ptr(rgb[1]), _ptr(var[0]), _ptr(var[1]), call.handle, C.byref(st))
+        if rc in (abi.OK, abi.E_CANCELLED):
+            sd.samples_done = si.samples_done = req.samples_done
+        if run is not None:
+            info = run.finish(rc, st)
+            info["samples_done"] = sd.samples_done
+        else:
+            _check(rc)
+            info = st.as_dict()
+        out = (rgb[0], rgb[1], state) + ((var[0], var[1]) if noise else ())
+        return out + ((info,) if (stats or progress is not None) else ())
+
     # ---- adaptive frames (include/frayhip.h "adaptive frames") ----
     def _adaptive_request(self, threshold, min_spp, err_floor):
         """Checks the caller's values as the library does and clamps min_spp to the frame's spp."""
@@ -876,6 +940,26 @@ class Scene:
         feat, fst = self.render_features(min(int(feature_samples), spp), seed=seed, stats=True)
         out, dst = denoise(raw, feat, half, stats=True, **params)
         return out, raw, {"render": rst, "features": fst, "denoise": dst, "rgb_half": half, "features_frame": feat}
+
+    def render_denoised_split(self, seed=42, feature_samples=4, **params):
+        """A frame whose direct and indirect light are filtered apart: (denoised, raw, info).  The components of the frame's spp samples come from
+        render_components with their noise estimates, each goes through denoise_signal with the feature frame (demodulate=0: the states' noise is
+        in rgb's domain) and the two results are added in FP32.  raw = direct_rgb + indirect_rgb.  params: denoise_params, but demodulate=1 is
+        refused (ValueError).  info: the "render", "features", "denoise_direct" and "denoise_indirect" stats dicts, the filtered components
+        "direct" and "indirect", and their inputs "direct_rgb", "indirect_rgb", "noise_direct", "noise_indirect" and "features_frame"."""
+        if params.get("demodulate", 0):
+            raise ValueError("render_denoised_split: demodulate=1 is not offered: the components' noise is in rgb's domain, not demodulated")
+        params = dict(params, demodulate=0)
+        denoise_params(**params)                # unknown names are refused before anything is rendered
+        self._need_dev()
+        spp = self.samples_per_pixel()
+        d_rgb, i_rgb, _state, d_noise, i_noise, rst = self.render_components(spp, seed=seed, noise=True, stats=True)
+        feat, fst = self.render_features(min(int(feature_samples), spp), seed=seed, stats=True)
+        d_out, dst = denoise_signal(d_rgb, d_noise, feat, stats=True, **params)
+        i_out, ist = denoise_signal(i_rgb, i_noise, feat, stats=True, **params)
+        return d_out + i_out, d_rgb + i_rgb, {"render": rst, "features": fst, "denoise_direct": dst, "denoise_indirect": ist, "direct": d_out,
+                                              "indirect": i_out, "direct_rgb": d_rgb, "indirect_rgb": i_rgb, "noise_direct": d_noise,
+                                              "noise_indirect": i_noise, "features_frame": feat}
 
     def render_sequence(self, cameras, seed=42, feature_samples=4, temporal=None, edit=None, **denoise_params):
         """A generator over a fly-through of a static scene with temporal accumulation (include/frayhip.h "temporal accumulation"): for the k-th

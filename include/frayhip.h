@@ -651,6 +651,40 @@ int  frayhip_render_samples(frayhip_scene* s, const frayhip_frame* f, frayhip_sa
 int  frayhip_render_samples_device(frayhip_scene* s, const frayhip_frame* f, frayhip_samples* r, const frayhip_progressive* p,
                                    float* d_accum, float* d_rgb, float* d_noise, void* hip_stream, frayhip_stats* st);
 
+/* ---- component frames (direct and indirect light as two resumable states) ---------------------------------------------------------------------
+ * For a mono, path-traced frame (settings.gi on, stereoSeparation == 0): frayhip_render_samples with the samples' colours kept apart as direct
+ * and indirect light, at no extra ray.  Sample i of a pixel is a list of terms t[0 .. n-1], n >= 1 -- bounce b of its path writes term b -- and
+ * the frame's resolve adds their fold, innermost first.  Here, per channel, all FP32, without contraction:
+ *       d_i = t[0]                            as it is stored, no addition
+ *       n_i = fold(t[1 .. n-1])               result = (0, 0, 0); then result = t[k] + result for k = n-1 .. 1; (0, 0, 0) when n == 1
+ *   so c_i == d_i + n_i: one FP32 addition per channel gives the sample colour of frayhip_render / frayhip_render_samples, bit for bit.
+ *   Direct light is the next-event contribution at the camera ray's hit, or the colour of the light or the environment the camera ray sees
+ *   itself, or black where the reference returns black at depth 0.  Indirect light is everything a later bounce contributes; a first hit on a
+ *   mirror or on glass has direct light 0.
+ * Two states, each laid out and accumulated as frayhip_render_samples' state (rows {sum.r, sum.g, sum.b, m2}, FRAYHIP_ACCUM_CHANNELS floats; the
+ *   sum in sample order, l = ((r + g) + b) / 3.0f, m2 = m2 + l * l): accum_direct takes the d_i, accum_indirect the n_i.  The outputs per state
+ *   are that entry's: rgb_* = sum / (float)N and noise_* (the formula above, of that component's luminance, in rgb's domain: it goes into
+ *   frayhip_denoise_signal with demodulate = 0).  All four are optional.  rgb_direct after samples 0 .. N-1 is the value of the N-sample frame
+ *   of the same scene with maxTraceDepth = 0.
+ * The contract is frayhip_render_samples' throughout: which samples, buckets (pixels outside the call's buckets are untouched in all six
+ *   buffers), sample_first > 0 trusting the caller's states, the host entry's copy-in rule (per state), the seed table, spp_chunk, the options and
+ *   the last frame's figures, *st, the _device entry's pointers (both states 16-byte aligned) and stream contract, long generators
+ *   (maxTraceDepth >= 20) and black frames (maxTraceDepth < 0: +0 per sample into both states, the samples counted once).  p's callback and
+ *   cancel work as there; after a cancel both states hold the same resolved samples and r->samples_done says how many.
+ * The differences:
+ *   Previews are not offered: a p with preview_ms >= 0 is FRAYHIP_E_ARG, and every callback has preview == 0 and rgb == NULL.
+ *   FRAYHIP_E_ARG also answers a NULL or misaligned second state, and any overlap among the six buffers.
+ *   FRAYHIP_E_UNSUPPORTED: settings.gi off (a Whitted frame has no term list) and stereo frames (their resolve blends per-sample eye colours).
+ *   Option fp_contract: a sample's first closest hit and its shading never run the contracted kernels, and of its next-event segments the
+ *   contracted any-hit kernel decides only visible / occluded, so the direct state is unchanged bit for bit unless such an answer flips (none
+ *   does in any frame of the tests); the indirect state carries the option's documented bound. */
+int  frayhip_render_components(frayhip_scene* s, const frayhip_frame* f, frayhip_samples* r, const frayhip_progressive* p,
+                               float* accum_direct, float* accum_indirect, float* rgb_direct, float* rgb_indirect,
+                               float* noise_direct, float* noise_indirect, frayhip_stats* st);
+int  frayhip_render_components_device(frayhip_scene* s, const frayhip_frame* f, frayhip_samples* r, const frayhip_progressive* p,
+                                      float* d_accum_direct, float* d_accum_indirect, float* d_rgb_direct, float* d_rgb_indirect,
+                                      float* d_noise_direct, float* d_noise_indirect, void* hip_stream, frayhip_stats* st);
+
 /* ---- feature frames (first-hit guides for a denoiser) ---------------------------------------------------------------------------------------
  * For every pixel of the call's buckets (frame.bucket_first / bucket_stride, as frayhip_render; other pixels untouched), the FP32 mean, in
  * sample order, of the first-hit features of the frame's own camera samples 0 .. n_samples - 1: sample i is the film position and the pinhole
