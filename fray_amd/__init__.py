@@ -6,8 +6,10 @@ beginRender) and `render()` (src/main.cpp:373).  All rendering happens in the HI
 no CPU fallback -- if the library is missing or no GPU is present the calls fail loudly.
 """
 from .scene import (Scene, Accumulation, FrayError, lib, render_info, denoise, denoise_params, denoise_signal,  # noqa: F401
-                    temporal_accumulate, temporal_params, view_from_camera, Transform, light_begin_frame, shader_begin_frame)
+                    temporal_accumulate, temporal_params, view_from_camera, Transform, light_begin_frame, shader_begin_frame,
+                    temporal_accumulate_split, split_history_parts, join_history_parts)
 from . import abi  # noqa: F401
 
 __all__ = ["Scene", "Accumulation", "FrayError", "lib", "abi", "render_info", "denoise", "denoise_params", "denoise_signal", "temporal_accumulate",
-           "temporal_params", "view_from_camera", "Transform", "light_begin_frame", "shader_begin_frame"]
+           "temporal_params", "view_from_camera", "Transform", "light_begin_frame", "shader_begin_frame", "temporal_accumulate_split",
+           "split_history_parts", "join_history_parts"]

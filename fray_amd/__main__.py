@@ -18,7 +18,10 @@ src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --he
                                                                                           is started when it does not exist; the picture of all of them)
                          python -m fray_amd scene.fray -o out.bmp --components-out FILE.npz [--denoise --split]   (path-traced mono frames: direct and
                                                                                          indirect light kept apart and saved with their noise estimates;
-                                                                                          --denoise --split: each filtered on its own, then added)"""
+                                                                                          --denoise --split: each filtered on its own, then added)
+                         python -m fray_amd scene.fray -o out.bmp --denoise --split --frames N [--yaw-step DEG] [--move ... [--motion-vectors]]
+                                                                                         (the sequence with one history per light component: direct
+                                                                                          light keeps a short one, where a moved shadow lives)"""
 import argparse
 import json
 import os
@@ -82,7 +85,8 @@ def build_parser():
                          "kept apart and save direct, indirect, noise_direct, noise_indirect, samples and seed; the picture is their sum")
     ap.add_argument("--split", action="store_true",
                     help="with --denoise: filter direct and indirect light apart and add the results (Scene.render_denoised_split); path-traced mono "
-                         "frames only, not with --adaptive")
+                         "frames only, not with --adaptive.  With --frames N: the sequence keeps one history per component "
+                         "(Scene.render_sequence(split=True); direct light's max_history is 8, a choice, indirect light's 32)")
     return ap
 
 
@@ -138,8 +142,10 @@ def check_args(ap, a):
         ap.error("--split cannot be combined with --adaptive")
     if a.split and not a.denoise:
         ap.error("--split needs --denoise")
-    if (a.split or a.components_out) and (a.frames is not None or a.accumulate or a.probe or a.adaptive is not None or a.time_limit is not None):
-        ap.error("--split and --components-out cannot be combined with --frames, --accumulate, --probe, --adaptive or --time-limit")
+    if a.components_out and a.frames is not None:
+        ap.error("--components-out cannot be combined with --frames")
+    if (a.split or a.components_out) and (a.accumulate or a.probe or a.adaptive is not None or a.time_limit is not None):
+        ap.error("--split and --components-out cannot be combined with --accumulate, --probe, --adaptive or --time-limit")
     if a.components_out and a.denoise and not a.split:
         ap.error("--components-out with --denoise needs --split")
 
@@ -243,15 +249,16 @@ def main(argv=None):
         start = abi.Camera.from_buffer_copy(s.camera)
         edit = (lambda _k, scene: move_nodes(scene, a.move)) if a.motion_vectors else None
         for k, (img, _raw, info) in enumerate(s.render_sequence(orbit(start, a.frames, a.yaw_step), seed=a.seed, feature_samples=a.feature_samples,
-                                                                edit=edit)):
+                                                                edit=edit, split=a.split)):
             path = sequence_path(a.output, k)
             img = img.cpu().numpy()
             if lib.frayhip_save_bmp(path.encode(), img.ctypes.data, img.shape[1], img.shape[0]):
                 print(lib.frayhip_last_error().decode(), file=sys.stderr)
                 return 1
+            filter_ms = info["denoise_direct"]["ms_kernels"] + info["denoise_indirect"]["ms_kernels"] if a.split else info["denoise"]["ms_kernels"]
             print("frame %d: yaw %+.2f, frame %.1f ms, features %.1f ms, accumulation %.2f ms, filter %.2f ms (kernels); wrote %s"
                   % (k, k * a.yaw_step, info["render"]["ms_kernels"], info["features"]["ms_kernels"], info["temporal"]["ms_kernels"],
-                     info["denoise"]["ms_kernels"], path), flush=True)
+                     filter_ms, path), flush=True)
             if a.move and not a.motion_vectors and k + 1 < a.frames:
                 move_nodes(s, a.move)           # the generator renders the next frame when it is asked for it: after this edit
         print("Rendered %d frames in %.2fs" % (a.frames, time.time() - t0))

@@ -205,6 +205,7 @@ class Temporal(C.Structure):
 
 
 HISTORY_CHANNELS = 12   # FRAYHIP_HISTORY_CHANNELS: {acc.rgb, N}, {P.xyz, m1}, {n.xyz, m2}
+HISTORY_SPLIT_CHANNELS = 20   # FRAYHIP_HISTORY_SPLIT_CHANNELS: {accD.rgb, N_D}, {P.xyz, m1_D}, {n.xyz, m2_D}, {accI.rgb, N_I}, {m1_I, m2_I, 0, 0}
 
 
 STRUCTS = {"frayhip_transform": Transform, "frayhip_geom_ref": GeomRef, "frayhip_node": Node,
@@ -262,6 +263,9 @@ SYMBOLS = {
     "frayhip_temporal_accumulate_device": (C.c_int, [C.c_int, C.c_int, VP, VP, P(View), VP, P(Temporal), VP, VP, VP, VP, P(Stats)]),
     "frayhip_temporal_accumulate_motion": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(View), VP, P(Temporal), VP, VP, VP, P(Stats)]),
     "frayhip_temporal_accumulate_motion_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(View), VP, P(Temporal), VP, VP, VP, VP, P(Stats)]),
+    "frayhip_temporal_accumulate_split": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, VP, P(View), VP, P(Temporal), P(Temporal), VP, VP, VP, VP, VP, P(Stats)]),
+    "frayhip_temporal_accumulate_split_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, VP, P(View), VP, P(Temporal), P(Temporal), VP, VP, VP, VP, VP, VP,
+                                                           P(Stats)]),
     "frayhip_camera_rays": (C.c_int, [VP, i64, VP, C.c_int, VP, VP]),
     "frayhip_camera_rays_device": (C.c_int, [VP, i64, VP, C.c_int, VP, VP, VP]),
     "frayhip_trace_rays": (C.c_int, [VP, i64, VP, VP, C.c_int, VP, VP, VP, P(Stats)]),

@@ -21,9 +21,7 @@
 #include <string>
 
 #include "entry_support.hpp"
-
-static __device__ __forceinline__ float tp_lum(float r, float g, float b) { return ((r + g) + b) / 3.0f; }
-static __device__ __forceinline__ float tp_dot(float a0, float a1, float a2, float b0, float b1, float b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
+#include "temporal_common.hpp"
 
 struct TemporalCall {
     int W, H;
@@ -186,15 +184,7 @@ static __global__ __launch_bounds__(256) void k_tp_variance(TemporalCall T)
 namespace {
 
 using namespace frayhip_detail;
-
-bool overlaps(const void* a, size_t an, const void* b, size_t bn)
-{
-    if (!a || !b) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bn && y < x + an;
-}
-
-bool finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+using namespace frayhip_temporal_detail;
 
 // Every check of both entries, in this order; none touches the device.
 // WITH_MOTION: the _motion entries, whose motion frame is an input like feat; NO_MOTION: the others (motion is null).
@@ -218,19 +208,8 @@ int check(const char* who, int W, int H, const float* rgb, const float* feat, co
         if (misaligned(histIn, 16) || misaligned(histOut, 16)) return bad(who, "device pointer to a history not 16-byte aligned");
         if (misaligned(motion, 16)) return bad(who, "device pointer to a motion frame not 16-byte aligned");
     }
-    if (view) {
-        if (view->width != W || view->height != H) return bad(who, "prev_view's size is not the frame's");
-        if (!finite3(view->pos) || !finite3(view->right) || !finite3(view->up) || !finite3(view->front) || !std::isfinite(view->tan_x) || !std::isfinite(view->tan_y))
-            return bad(who, "prev_view has a non-finite field");
-        if (!(view->tan_x > 0) || !(view->tan_y > 0)) return bad(who, "prev_view's tan_x and tan_y must be > 0");
-    }
-    if (p->demodulate != 0 && p->demodulate != 1) return bad(who, "demodulate must be 0 or 1");
-    if (p->max_history < 1 || p->max_history > 4096) return bad(who, "max_history must be 1..4096");
-    if (p->variance_history < 1 || p->variance_history > 4096) return bad(who, "variance_history must be 1..4096");
-    if (!(p->alpha_min >= 0 && p->alpha_min <= 1)) return bad(who, "alpha_min must be 0..1");
-    if (!std::isfinite(p->film_offset)) return bad(who, "film_offset must be finite");
-    if (!std::isfinite(p->plane_tolerance) || p->plane_tolerance < 0) return bad(who, "plane_tolerance must be finite and >= 0");
-    if (!(p->normal_min_dot >= -1 && p->normal_min_dot <= 1)) return bad(who, "normal_min_dot must be -1..1");
+    if (const int rc = check_view(who, W, H, view)) return rc;
+    if (const int rc = check_params(who, p)) return rc;
     const size_t n = (size_t)W * H;
     const struct { const void* q; size_t bytes; } ins[4] = {{rgb, 12 * n}, {feat, 4 * FRAYHIP_FEAT_CHANNELS * n}, {histIn, 4 * FRAYHIP_HISTORY_CHANNELS * n},
                                                             {motion, 4 * FRAYHIP_MOTION_CHANNELS * n}};
@@ -244,11 +223,6 @@ int check(const char* who, int W, int H, const float* rgb, const float* feat, co
     }
     return FRAYHIP_OK;
 }
-
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
 
 // The device path of both entries (device pointers, checked)
 // motion: the motion frame of the _motion entries, or null

@@ -304,6 +304,99 @@ def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, st
     return (hist, signal, var, st.as_dict()) if stats else (hist, signal, var)
 
 
+_TEMPORAL_SHARED = ("demodulate", "film_offset", "plane_tolerance", "normal_min_dot")     # the fields that decide which taps count
+
+
+def _split_params(who, direct, indirect, shared):
+    """The two abi.Temporal of a split call: `shared` applied to both, then each component's own dict; the fields of _TEMPORAL_SHARED must come
+    out equal bit for bit (ValueError)."""
+    pd, pi = temporal_params(**dict(shared, **(direct or {}))), temporal_params(**dict(shared, **(indirect or {})))
+    for k in _TEMPORAL_SHARED:
+        a, b = getattr(pd, k), getattr(pi, k)
+        if np.asarray(a).tobytes() != np.asarray(b).tobytes():
+            raise ValueError("%s: direct and indirect must agree on %s (%r and %r): it decides which taps count" % (who, k, a, b))
+    return pd, pi
+
+
+def split_history_parts(hist):
+    """The two ordinary histories inside a split history [H, W, 20] (numpy or torch): (direct [H, W, 12], indirect [H, W, 12]), each what
+    temporal_accumulate takes as hist_in for that component.  Copies."""
+    if hist.ndim != 3 or hist.shape[2] != abi.HISTORY_SPLIT_CHANNELS:
+        raise ValueError("split_history_parts: hist must be shaped [H, W, %d], got %s" % (abi.HISTORY_SPLIT_CHANNELS, tuple(hist.shape)))
+    if _torch_tensor(hist):
+        import torch
+        return hist[..., 0:12].contiguous(), torch.cat([hist[..., 12:16], hist[..., 4:7], hist[..., 16:17], hist[..., 8:11], hist[..., 17:18]], dim=2)
+    return (np.ascontiguousarray(hist[..., 0:12]),
+            np.concatenate([hist[..., 12:16], hist[..., 4:7], hist[..., 16:17], hist[..., 8:11], hist[..., 17:18]], axis=2))
+
+
+def join_history_parts(hist_direct, hist_indirect):
+    """split_history_parts' inverse: the split history [H, W, 20] of two ordinary histories of one frame.  ValueError when their position or
+    normal columns differ in any bit (they are not histories of the same surface points)."""
+    who = "join_history_parts"
+    tensors = _torch_tensor(hist_direct)
+    if tensors != _torch_tensor(hist_indirect):
+        raise TypeError("%s: pass numpy arrays or torch tensors, not a mix" % who)
+    for name, h in (("hist_direct", hist_direct), ("hist_indirect", hist_indirect)):
+        if h.ndim != 3 or h.shape[2] != abi.HISTORY_CHANNELS:
+            raise ValueError("%s: %s must be shaped [H, W, %d], got %s" % (who, name, abi.HISTORY_CHANNELS, tuple(h.shape)))
+    if tuple(hist_direct.shape) != tuple(hist_indirect.shape):
+        raise ValueError("%s: the parts' sizes differ: %s and %s" % (who, tuple(hist_direct.shape), tuple(hist_indirect.shape)))
+    if tensors:
+        import torch
+        bits = lambda a: a.contiguous().view(torch.int32)
+        cat = lambda parts: torch.cat(parts, dim=2)
+        zeros = torch.zeros_like(hist_indirect[..., 0:2])
+    else:
+        if hist_direct.dtype != np.float32 or hist_indirect.dtype != np.float32:
+            raise TypeError("%s: the parts must be float32" % who)
+        bits = lambda a: np.ascontiguousarray(a).view(np.int32)
+        cat = lambda parts: np.concatenate(parts, axis=2)
+        zeros = np.zeros_like(hist_indirect[..., 0:2])
+    for lo in (4, 8):
+        if not bool((bits(hist_direct[..., lo:lo + 3]) == bits(hist_indirect[..., lo:lo + 3])).all()):
+            raise ValueError("%s: the parts' %s columns differ" % (who, "position" if lo == 4 else "normal"))
+    return cat([hist_direct, hist_indirect[..., 0:4], hist_indirect[..., 7:8], hist_indirect[..., 11:12], zeros])
+
+
+def temporal_accumulate_split(rgb_direct, rgb_indirect, feat, prev_view=None, hist_in=None, motion=None, direct=None, indirect=None, stats=False,
+                              stream=None, **shared):
+    """temporal_accumulate for a frame's direct and indirect light in one call (frayhip_temporal_accumulate_split): rgb_direct and rgb_indirect
+    [H, W, 3] (Scene.render_components), feat [H, W, 10], prev_view and hist_in [H, W, 20] (the previous call's split history) both None for the
+    first frame, motion [H, W, 8] or None as temporal_accumulate takes it; float32, numpy arrays (host entry) or GPU torch tensors (device
+    entry, on `stream`).  direct, indirect: dicts of temporal_params fields for that component; **shared is applied to both.  The components may
+    differ in max_history, variance_history and alpha_min; demodulate, film_offset, plane_tolerance and normal_min_dot must agree (ValueError).
+    Returns (hist_out [H, W, 20], signal_direct, signal_indirect, variance_direct, variance_indirect[, stats]); each component's outputs are
+    temporal_accumulate's for that component and its part of the history (split_history_parts), bit for bit."""
+    who = "temporal_accumulate_split"
+    pd, pi = _split_params(who, direct, indirect, shared)
+    if (prev_view is None) != (hist_in is None):
+        raise ValueError("%s: prev_view and hist_in must both be given or both be None" % who)
+    if prev_view is not None and not isinstance(prev_view, abi.View):
+        raise TypeError("%s: prev_view must be an abi.View (view_from_camera), got %s" % (who, type(prev_view).__name__))
+    named = [("rgb_direct", rgb_direct, 3), ("rgb_indirect", rgb_indirect, 3), ("feat", feat, abi.FEAT_CHANNELS)]
+    if hist_in is not None:
+        named.append(("hist_in", hist_in, abi.HISTORY_SPLIT_CHANNELS))
+    if motion is not None:
+        named.append(("motion", motion, abi.MOTION_CHANNELS))
+    ins, (H, W), tensors = _frame_inputs(who, named)
+    hin = ins[3] if hist_in is not None else None
+    mot = ins[-1] if motion is not None else None
+    view = C.byref(prev_view) if prev_view is not None else None
+    st = abi.Stats()
+    shapes = ((H, W, abi.HISTORY_SPLIT_CHANNELS), (H, W, 3), (H, W, 3), (H, W), (H, W))
+    if not tensors:
+        outs = tuple(np.empty(shape, np.float32) for shape in shapes)
+        _check(lib.frayhip_temporal_accumulate_split(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(mot), view, _ptr(hin), C.byref(pd), C.byref(pi),
+                                                     *[_ptr(o) for o in outs], C.byref(st)))
+    else:
+        with _DeviceCall(ins[0].device, stream) as call:
+            outs = tuple(call.torch.empty(shape, dtype=call.torch.float32, device=ins[0].device) for shape in shapes)
+            _check(lib.frayhip_temporal_accumulate_split_device(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(mot), view, _ptr(hin), C.byref(pd),
+                                                                C.byref(pi), *[_ptr(o) for o in outs], call.handle, C.byref(st)))
+    return outs + ((st.as_dict(),) if stats else ())
+
+
 class Transform:
     """The reference's Transform (matrix.h:72-98) over the C helpers frayhip_transform_*: the parser's own arithmetic, so that
     Transform().scale(...).rotate(...).translate(...) in the order of a block's lines gives the bytes parseScene stores.  Starts as the identity,
@@ -961,7 +1054,8 @@ class Scene:
                                               "indirect": i_out, "direct_rgb": d_rgb, "indirect_rgb": i_rgb, "noise_direct": d_noise,
                                               "noise_indirect": i_noise, "features_frame": feat}
 
-    def render_sequence(self, cameras, seed=42, feature_samples=4, temporal=None, edit=None, **denoise_params):
+    def render_sequence(self, cameras, seed=42, feature_samples=4, temporal=None, edit=None, split=False, temporal_direct=None, temporal_indirect=None,
+                        **denoise_params):
         """A generator over a fly-through of a static scene with temporal accumulation (include/frayhip.h "temporal accumulation"): for the k-th
         abi.Camera of `cameras` it sets the view, renders the feature frame and the frame with seed + k (equal seeds would accumulate the same
         noise every frame), accumulates onto the previous frame's history reprojected into this view, runs the a-trous levels on the accumulated
@@ -975,11 +1069,31 @@ class Scene:
         edit: None (a static scene: exactly the launches above), or a callable edit(k, scene) that is called before frame k >= 1, after the
         snapshot of node_transforms(); it may edit the description's tables and must call scene.update() itself if it does.  With edit given,
         every frame renders the features and the motion frame in one pass (frayhip_render_features_motion; frame 0 against its own transforms),
-        accumulates through the motion frame, and info also holds "motion" [H, W, 8].  What was edited stays edited when the generator ends."""
+        accumulates through the motion frame, and info also holds "motion" [H, W, 8].  What was edited stays edited when the generator ends.
+        split: False runs exactly the launches above.  True (mono path-traced frames; a Whitted or a stereo frame is refused with FrayError before
+        anything is rendered) keeps one history per light component (include/frayhip.h "split temporal accumulation"): after the feature pass the
+        frame's samples are rendered as components (render_components into two fresh device states, seed + k), one temporal_accumulate_split
+        accumulates both, denoise_signal runs on each component with the sequence's `demodulate` (1 is fine here: the variance comes from the
+        moments of the demodulated signal), and the yielded picture is the FP32 sum of the two results.  raw is direct_rgb + indirect_rgb, which
+        is NOT render(seed + k) bit for bit: two sums of samples are added.  info then holds "direct", "indirect" (the filtered components),
+        "direct_rgb", "indirect_rgb", "signal_direct", "signal_indirect", "variance_direct", "variance_indirect", "history" [H, W, 20],
+        "params_direct" and "params_indirect" (the temporal_params fields in force), and "denoise_direct", "denoise_indirect" in place of
+        "denoise".  temporal= still sets both components; temporal_direct / temporal_indirect (dicts of temporal_params fields; split only)
+        override it per component, and demodulate, film_offset, plane_tolerance and normal_min_dot must stay equal.  Where the caller names no
+        max_history the direct component's is 8 and the indirect one's the default 32: a shadow that moves over a static surface lives in the
+        direct component, and its residue after j frames is (1 - 1/8)^j of the step instead of (1 - 1/32)^j, while direct light at one
+        next-event sample per path sample is the less noisy component.  The 8 is a choice, not a measurement."""
         self._need_dev()
         import torch
         W, H = self.frame_size
         spp = self.samples_per_pixel()
+        if not split and (temporal_direct is not None or temporal_indirect is not None):
+            raise ValueError("render_sequence: temporal_direct and temporal_indirect need split=True")
+        if split:
+            if not self.settings.gi:
+                raise FrayError(abi.E_UNSUPPORTED, "render_sequence: component frames need a path-traced frame (settings.gi)")
+            if self.camera.stereoSeparation > 0:
+                raise FrayError(abi.E_UNSUPPORTED, "render_sequence: component frames are not offered for stereo frames")
         tparams = dict(temporal or {})
         if "film_offset" not in tparams:
             tparams["film_offset"] = 0.5 if (self.settings.gi or self.camera.dof) else 0.3 if self.settings.wantAA else 0.0
@@ -987,6 +1101,14 @@ class Scene:
         if tparams.setdefault("demodulate", dparams.demodulate) != dparams.demodulate:
             raise ValueError("render_sequence: the accumulation and the filter must agree on demodulate")
         temporal_params(**tparams)                      # unknown fields are refused before anything is rendered
+        if split:
+            tdirect, tindirect = dict(tparams, **(temporal_direct or {})), dict(tparams, **(temporal_indirect or {}))
+            tdirect.setdefault("max_history", 8)
+            for t in (tdirect, tindirect):
+                if t["demodulate"] != dparams.demodulate:
+                    raise ValueError("render_sequence: the accumulation and the filter must agree on demodulate")
+            pd, pi = _split_params("render_sequence", tdirect, tindirect, {})
+            fields = lambda p: {k: getattr(p, k) for k in _TEMPORAL_FIELDS}
         n_feat = min(int(feature_samples), spp)
         saved = abi.Camera.from_buffer_copy(self.desc.camera)
         stream = torch.cuda.current_stream()
@@ -1004,7 +1126,6 @@ class Scene:
                     if k:
                         edit(k, self)
                 feat = torch.empty((H, W, abi.FEAT_CHANNELS), dtype=torch.float32, device="cuda")
-                raw = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
                 fst, rst = abi.Stats(), abi.Stats()
                 fr = self._frame(abi.MODE_RENDER, (seed + k) & 0xFFFFFFFF, 0, 1, 0, False)
                 if edit is not None:
@@ -1013,6 +1134,23 @@ class Scene:
                                                                      motion.data_ptr(), handle, C.byref(fst)))
                 else:
                     _check(lib.frayhip_render_features_device(self._dev, C.byref(fr), n_feat, feat.data_ptr(), handle, C.byref(fst)))
+                if split:
+                    state = tuple(Accumulation.empty((W, H), fr.seed, device="cuda") for _ in range(2))
+                    d_rgb, i_rgb, _state, rst = self.render_components(spp, state, seed=fr.seed, stats=True, stream=stream)
+                    hist, sig_d, sig_i, var_d, var_i, tst = temporal_accumulate_split(d_rgb, i_rgb, feat, view, hist, motion=motion, direct=tdirect,
+                                                                                      indirect=tindirect, stats=True, stream=stream)
+                    d_out, dst = denoise_signal(sig_d, var_d, feat, stats=True, stream=stream, **denoise_params)
+                    i_out, ist = denoise_signal(sig_i, var_i, feat, stats=True, stream=stream, **denoise_params)
+                    view = view_from_camera(self.desc.camera, W, H)
+                    info = {"features_frame": feat, "history": hist, "direct": d_out, "indirect": i_out, "direct_rgb": d_rgb, "indirect_rgb": i_rgb,
+                            "signal_direct": sig_d, "signal_indirect": sig_i, "variance_direct": var_d, "variance_indirect": var_i, "view": view,
+                            "film_offset": tdirect["film_offset"], "params_direct": fields(pd), "params_indirect": fields(pi), "render": rst,
+                            "features": fst.as_dict(), "temporal": tst, "denoise_direct": dst, "denoise_indirect": ist}
+                    if edit is not None:
+                        info["motion"] = motion
+                    yield d_out + i_out, d_rgb + i_rgb, info
+                    continue
+                raw = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
                 _check(lib.frayhip_render_device(self._dev, C.byref(fr), raw.data_ptr(), None, None, handle, C.byref(rst)))
                 hist, signal, var, tst = temporal_accumulate(raw, feat, view, hist, stats=True, stream=stream, motion=motion, **tparams)
                 out, dst = denoise_signal(signal, var, feat, stats=True, stream=stream, **denoise_params)

@@ -869,6 +869,50 @@ int  frayhip_temporal_accumulate_motion(int width, int height, const float* rgb,
 int  frayhip_temporal_accumulate_motion_device(int width, int height, const float* d_rgb, const float* d_feat, const float* d_motion,
                                                const frayhip_view* prev_view, const float* d_hist_in, const struct frayhip_temporal* p,
                                                float* d_hist_out, float* d_signal, float* d_variance, void* hip_stream, frayhip_stats* st);
+
+/* ---- split temporal accumulation (one history per light component) --------------------------------------------------------------------------
+ * The stage above for two signals of one frame in one call: a frame's direct and indirect light (frayhip_render_components), each with a
+ * history length of its own.  A shadow that moves across a static floor passes every surface test (the floor's first hit did not move) and so
+ * stays in a single history for max_history frames; it lives in the direct component, which can take a short history while the indirect
+ * component, the noisier one, keeps a long one.
+ *
+ * Split history: FRAYHIP_HISTORY_SPLIT_CHANNELS = 20 floats per pixel, five 16-byte rows:
+ *     0 {accD.rgb, N_D}   1 {P.xyz, m1_D}   2 {n.xyz, m2_D}   3 {accI.rgb, N_I}   4 {m1_I, m2_I, +0.0f, +0.0f}
+ * Rows 0-2 are, as they stand, the direct component's 12-channel history; the indirect component's is {row 3}, {P, m1_I}, {n, m2_I}.
+ *
+ * p_direct and p_indirect may differ in max_history, variance_history and alpha_min.  The fields that decide which taps count -- demodulate,
+ * film_offset, plane_tolerance, normal_min_dot -- must agree bit for bit.  motion NULL: the arithmetic of frayhip_temporal_accumulate;
+ * otherwise (a motion frame, as that entry takes it) the arithmetic of frayhip_temporal_accumulate_motion.  The library sets no default of
+ * its own for the two lengths (frayhip_temporal_defaults fills either struct); the Python sequence and the CLI give the direct component a
+ * max_history of 8 and leave the indirect one's at 32 where the caller names none.  The 8 is a maintainer's choice, not a measurement: a moved
+ * shadow's residue after j frames is (1 - 1/8)^j of the step instead of (1 - 1/32)^j, and direct light at one next-event sample per path
+ * sample is the less noisy component.
+ *
+ * The contract.  For every pixel the call produces two groups of outputs, each equal BIT FOR BIT to a call of the entry above:
+ *   direct    rows 0-2 of hist_out, signal_direct and variance_direct are what frayhip_temporal_accumulate[_motion] returns for rgb_direct,
+ *             p_direct and rows 0-2 of hist_in;
+ *   indirect  {row 3}, {P, m1_I}, {n, m2_I} of hist_out, signal_indirect and variance_indirect are what it returns for rgb_indirect,
+ *             p_indirect and the same three rows of hist_in.
+ * It holds because the tap tests and the bilinear weights depend only on P, n, the view and the shared fields; everything per component is the
+ * same expression, with every sum in the order written above, on the other component's inputs.
+ * Kernels: k_tp_accumulate_split (the projection, the footprint and the surface tests once, each counted tap's five rows read once), then
+ *   k_tp_variance_split when max(variance_history_D, variance_history_I) > 1 (the window's surface tests once; a component whose
+ *   variance_history is 1 never takes the window).  No work buffers.  Device pointers, the stream contract and *st as above (the histories and
+ *   the motion frame 16-byte aligned).
+ * FRAYHIP_E_ARG, before the device is touched: the list above, per struct and per output (NULL rgb_direct, rgb_indirect, feat, p_direct,
+ *   p_indirect or any of the five outputs; any output overlapping any input or another output), and a shared field that differs between
+ *   p_direct and p_indirect. */
+#define FRAYHIP_HISTORY_SPLIT_CHANNELS 20
+int  frayhip_temporal_accumulate_split(int width, int height, const float* rgb_direct, const float* rgb_indirect, const float* feat,
+                                       const float* motion, const frayhip_view* prev_view, const float* hist_in,
+                                       const struct frayhip_temporal* p_direct, const struct frayhip_temporal* p_indirect, float* hist_out,
+                                       float* signal_direct, float* signal_indirect, float* variance_direct, float* variance_indirect,
+                                       frayhip_stats* st);
+int  frayhip_temporal_accumulate_split_device(int width, int height, const float* d_rgb_direct, const float* d_rgb_indirect, const float* d_feat,
+                                              const float* d_motion, const frayhip_view* prev_view, const float* d_hist_in,
+                                              const struct frayhip_temporal* p_direct, const struct frayhip_temporal* p_indirect,
+                                              float* d_hist_out, float* d_signal_direct, float* d_signal_indirect, float* d_variance_direct,
+                                              float* d_variance_indirect, void* hip_stream, frayhip_stats* st);
 /* Not covered: SVGF's wider 3 x 3 retry when no bilinear tap counts, feeding a filtered level back into the history, moved lights and the
  * shadows and reflections of moved objects (only a pixel's own first hit is carried back: frayhip_render_features_motion), motion blur,
  * specular motion vectors (what a mirror shows moves with the camera while its first hit does not), learned
