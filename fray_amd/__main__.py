@@ -21,7 +21,11 @@ src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --he
                                                                                           --denoise --split: each filtered on its own, then added)
                          python -m fray_amd scene.fray -o out.bmp --denoise --split --frames N [--yaw-step DEG] [--move ... [--motion-vectors]]
                                                                                          (the sequence with one history per light component: direct
-                                                                                          light keeps a short one, where a moved shadow lives)"""
+                                                                                          light keeps a short one, where a moved shadow lives)
+                         python -m fray_amd scene.fray -o out.bmp --denoise --frames N --move NODE DX DY DZ --motion-vectors --change-samples K
+                                                                                         (the sequence with a probe of K samples per frame that finds
+                                                                                          what the move changed in the light -- the node's shadow -- and
+                                                                                          shortens the history there; with or without --split)"""
 import argparse
 import json
 import os
@@ -74,6 +78,11 @@ def build_parser():
     ap.add_argument("--motion-vectors", action="store_true",
                     help="with --denoise --frames N --move ...: render the motion frame with the features (Scene.render_sequence(edit=...)) and "
                          "accumulate through it, so that a moved node's pixels keep their history")
+    ap.add_argument("--change-samples", type=int, default=0, metavar="K",
+                    help="with --denoise --frames N --move ... --motion-vectors: before each move render K samples per pixel of the coming frame "
+                         "(its first K, of the same seed) and compare them with the frame's own after the move: where they differ the light changed -- "
+                         "a moved node's shadow or reflection -- and the history is shortened (Scene.render_sequence(change_samples=K); K / spp more "
+                         "rays per frame; default 0: off)")
     ap.add_argument("--accumulate", metavar="FILE.npz",
                     help="resumable frame (Scene.render_samples): continue the state saved in FILE.npz by --spp more samples per pixel (default: the "
                          "scene's own count), or start it when the file does not exist; writes FILE.npz and the picture of all samples so far.  A "
@@ -123,6 +132,10 @@ def check_args(ap, a):
         ap.error("--move needs --frames")
     if a.motion_vectors and not (a.denoise and a.frames is not None and a.move):
         ap.error("--motion-vectors needs --denoise --frames N --move ...")
+    if a.change_samples < 0:
+        ap.error("--change-samples must be >= 0")
+    if a.change_samples and not a.motion_vectors:
+        ap.error("--change-samples needs --denoise --frames N --move ... --motion-vectors")
     if a.move and (a.adaptive is not None or a.accumulate or a.probe or a.time_limit is not None):
         ap.error("--move cannot be combined with --adaptive, --accumulate, --probe or --time-limit")
     for m in a.move or []:
@@ -249,7 +262,7 @@ def main(argv=None):
         start = abi.Camera.from_buffer_copy(s.camera)
         edit = (lambda _k, scene: move_nodes(scene, a.move)) if a.motion_vectors else None
         for k, (img, _raw, info) in enumerate(s.render_sequence(orbit(start, a.frames, a.yaw_step), seed=a.seed, feature_samples=a.feature_samples,
-                                                                edit=edit, split=a.split)):
+                                                                edit=edit, split=a.split, change_samples=a.change_samples)):
             path = sequence_path(a.output, k)
             img = img.cpu().numpy()
             if lib.frayhip_save_bmp(path.encode(), img.ctypes.data, img.shape[1], img.shape[0]):

@@ -204,6 +204,11 @@ class Temporal(C.Structure):
                 ("plane_tolerance", C.c_float), ("normal_min_dot", C.c_float)]
 
 
+# struct frayhip_change (a struct tag without a typedef, as frayhip_denoise)
+class Change(C.Structure):
+    _fields_ = [("radius", i32), ("gain", C.c_float)]
+
+
 HISTORY_CHANNELS = 12   # FRAYHIP_HISTORY_CHANNELS: {acc.rgb, N}, {P.xyz, m1}, {n.xyz, m2}
 HISTORY_SPLIT_CHANNELS = 20   # FRAYHIP_HISTORY_SPLIT_CHANNELS: {accD.rgb, N_D}, {P.xyz, m1_D}, {n.xyz, m2_D}, {accI.rgb, N_I}, {m1_I, m2_I, 0, 0}
 
@@ -266,6 +271,11 @@ SYMBOLS = {
     "frayhip_temporal_accumulate_split": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, VP, P(View), VP, P(Temporal), P(Temporal), VP, VP, VP, VP, VP, P(Stats)]),
     "frayhip_temporal_accumulate_split_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, VP, P(View), VP, P(Temporal), P(Temporal), VP, VP, VP, VP, VP, VP,
                                                            P(Stats)]),
+    "frayhip_change_defaults": (C.c_int, [P(Change)]),
+    "frayhip_change_frame": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(Change), VP, P(Stats)]),
+    "frayhip_change_frame_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(Change), VP, VP, P(Stats)]),
+    "frayhip_temporal_accumulate_adaptive": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, VP, P(View), VP, P(Temporal), VP, VP, VP, P(Stats)]),
+    "frayhip_temporal_accumulate_adaptive_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, VP, P(View), VP, P(Temporal), VP, VP, VP, VP, P(Stats)]),
     "frayhip_camera_rays": (C.c_int, [VP, i64, VP, C.c_int, VP, VP]),
     "frayhip_camera_rays_device": (C.c_int, [VP, i64, VP, C.c_int, VP, VP, VP]),
     "frayhip_trace_rays": (C.c_int, [VP, i64, VP, VP, C.c_int, VP, VP, VP, P(Stats)]),

@@ -119,6 +119,7 @@ int frayhip_sizeof(const char* n)
     FRAYHIP_SZ(frayhip_view)
     if (!strcmp(n, "frayhip_denoise")) return (int)sizeof(struct frayhip_denoise);   // a struct tag: the name is also a function's
     if (!strcmp(n, "frayhip_temporal")) return (int)sizeof(struct frayhip_temporal);
+    if (!strcmp(n, "frayhip_change")) return (int)sizeof(struct frayhip_change);
 #undef FRAYHIP_SZ
     return -1;
 }

@@ -1,5 +1,5 @@
 // C ABI, temporal accumulation (include/frayhip.h "temporal accumulation"): frayhip_view_from_camera, frayhip_temporal_defaults,
-// frayhip_temporal_accumulate, frayhip_temporal_accumulate_motion and their _device entries.  The temporal stage of SVGF: the previous frame's accumulated signal and
+// frayhip_temporal_accumulate, frayhip_temporal_accumulate_motion, frayhip_temporal_accumulate_adaptive and their _device entries.  The temporal stage of SVGF: the previous frame's accumulated signal and
 // luminance moments reprojected through the feature frame's world positions, surface tests on the four bilinear taps, the exponential blend,
 // and the variance the a-trous levels take (frayhip_denoise_signal).  Scene-free, FP32 throughout; the Makefile builds this object as it builds
 // denoise.o (-ffp-contract=off, correctly rounded divide and sqrt), so every product and sum below is rounded where it is written
@@ -8,7 +8,9 @@
 //   k_tp_accumulate  per pixel: the signal, the projection into the previous view, four taps of three float4 rows each, the blend; writes the
 //                    three history rows, the signal, and the temporal variance where N >= variance_history.  <MOTION>: the point projected and
 //                    the surface the taps are tested against are the motion frame's P' and n' (two float4 rows) instead of the feature frame's
-//                    position and normal; <false> is the kernel as it was
+//                    position and normal; <false> is the kernel as it was.  <MOTION, ADAPTIVE>: a change frame (change.hip) shortens the history per
+//                    pixel -- none where change >= 1, a blend factor raised towards 1 where it is > 0, the arithmetic as it was where it is 0;
+//                    <MOTION, false> are the two kernels as they were
 //   k_tp_variance    per pixel with N < variance_history: the 7x7 window of the finished history (rows 1 and 2: position, normal, m1, m2),
 //                    taken from an LDS tile that the 16x16 block stages first; a block without such a pixel stages nothing
 // k_tp_accumulate's taps are read through L1 / L2, as the filter's.  k_tp_variance with the same direct reads took 0.214 ms at 1080p where
@@ -35,9 +37,10 @@ struct TemporalCall {
     frayhip_view view;          // read only with histIn
     int demodulate, varianceHistory;
     float maxHistory, alphaMin, filmOffset, planeTolerance, normalMinDot;
+    const float* change;        // k_tp_accumulate<MOTION, true> only: one float a pixel
 };
 
-template <bool MOTION>
+template <bool MOTION, bool ADAPTIVE>
 static __global__ __launch_bounds__(256) void k_tp_accumulate(TemporalCall T)
 {
     const int W = T.W, H = T.H;
@@ -109,7 +112,22 @@ static __global__ __launch_bounds__(256) void k_tp_accumulate(TemporalCall T)
         }
     }
     float ar = cr, ag = cg, ab = cb, m1 = l, m2 = l2, N = 1.0f;
-    if (sb > 0.0f) {
+    float g = 0.0f;                        // the pixel's change, read only where a history was fetched
+    if constexpr (ADAPTIVE) {
+        if (sb > 0.0f) g = T.change[p];
+    }
+    if (ADAPTIVE && !(g < 1.0f)) {
+        // changed through and through (1, above 1, NaN): no history, the first-frame values above
+    } else if (ADAPTIVE && g > 0.0f) {
+        hr = hr / sb; hg = hg / sb; hb = hb / sb; hn = hn / sb; h1 = h1 / sb; h2 = h2 / sb;
+        const float N0 = fminf(hn + 1.0f, T.maxHistory);
+        const float a0 = fmaxf(T.alphaMin, 1.0f / N0);
+        const float alpha = a0 + g * (1.0f - a0);
+        N = fminf(N0, 1.0f / alpha);
+        ar = hr + alpha * (cr - hr); ag = hg + alpha * (cg - hg); ab = hb + alpha * (cb - hb);
+        m1 = h1 + alpha * (l - h1);
+        m2 = h2 + alpha * (l2 - h2);
+    } else if (sb > 0.0f) {
         hr = hr / sb; hg = hg / sb; hb = hb / sb; hn = hn / sb; h1 = h1 / sb; h2 = h2 / sb;
         N = fminf(hn + 1.0f, T.maxHistory);
         const float alpha = fmaxf(T.alphaMin, 1.0f / N);
@@ -186,24 +204,27 @@ namespace {
 using namespace frayhip_detail;
 using namespace frayhip_temporal_detail;
 
-// Every check of both entries, in this order; none touches the device.
-// WITH_MOTION: the _motion entries, whose motion frame is an input like feat; NO_MOTION: the others (motion is null).
-enum MotionInput { NO_MOTION, WITH_MOTION };
+// Every check of the entries, in this order; none touches the device.
+// WITH_MOTION: the _motion entries, whose motion frame is an input like feat; NO_MOTION: the others (motion is null); MAY_MOTION: the _adaptive
+// entries, which take either.  adaptive: the _adaptive entries, whose change frame is an input like feat.
+enum MotionInput { NO_MOTION, WITH_MOTION, MAY_MOTION };
 int check(const char* who, int W, int H, const float* rgb, const float* feat, const frayhip_view* view, const float* histIn, const struct frayhip_temporal* p,
-          const float* histOut, const float* signal, const float* variance, bool device, MotionInput mi, const float* motion)
+          const float* histOut, const float* signal, const float* variance, bool device, MotionInput mi, const float* motion, bool adaptive = false,
+          const float* change = nullptr)
 {
     if (W < 1 || H < 1) return bad(who, "width and height must be >= 1");
     if ((long long)W * H > (1ll << 30)) return bad(who, "more than 2^30 pixels");
     if (!rgb) return bad(who, "null rgb");
     if (!feat) return bad(who, "null feat");
     if (mi == WITH_MOTION && !motion) return bad(who, "null motion");
+    if (adaptive && !change) return bad(who, "null change");
     if (!p) return bad(who, "null parameters");
     if (!histOut) return bad(who, "null hist_out");
     if (!signal) return bad(who, "null signal");
     if (!variance) return bad(who, "null variance");
     if (!histIn != !view) return bad(who, "hist_in and prev_view must both be given or both be null");
     if (device) {
-        for (const void* q : {(const void*)rgb, (const void*)feat, (const void*)signal, (const void*)variance})
+        for (const void* q : {(const void*)rgb, (const void*)feat, (const void*)signal, (const void*)variance, (const void*)change})
             if (misaligned(q, 4)) return bad(who, "device pointer to floats not 4-byte aligned");
         if (misaligned(histIn, 16) || misaligned(histOut, 16)) return bad(who, "device pointer to a history not 16-byte aligned");
         if (misaligned(motion, 16)) return bad(who, "device pointer to a motion frame not 16-byte aligned");
@@ -211,8 +232,8 @@ int check(const char* who, int W, int H, const float* rgb, const float* feat, co
     if (const int rc = check_view(who, W, H, view)) return rc;
     if (const int rc = check_params(who, p)) return rc;
     const size_t n = (size_t)W * H;
-    const struct { const void* q; size_t bytes; } ins[4] = {{rgb, 12 * n}, {feat, 4 * FRAYHIP_FEAT_CHANNELS * n}, {histIn, 4 * FRAYHIP_HISTORY_CHANNELS * n},
-                                                            {motion, 4 * FRAYHIP_MOTION_CHANNELS * n}};
+    const struct { const void* q; size_t bytes; } ins[5] = {{rgb, 12 * n}, {feat, 4 * FRAYHIP_FEAT_CHANNELS * n}, {histIn, 4 * FRAYHIP_HISTORY_CHANNELS * n},
+                                                            {motion, 4 * FRAYHIP_MOTION_CHANNELS * n}, {change, 4 * n}};
     const struct { const void* q; size_t bytes; const char* name; } outs[3] = {{histOut, 4 * FRAYHIP_HISTORY_CHANNELS * n, "hist_out"}, {signal, 12 * n, "signal"},
                                                                                  {variance, 4 * n, "variance"}};
     for (int o = 0; o < 3; o++) {
@@ -224,17 +245,18 @@ int check(const char* who, int W, int H, const float* rgb, const float* feat, co
     return FRAYHIP_OK;
 }
 
-// The device path of both entries (device pointers, checked)
-// motion: the motion frame of the _motion entries, or null
+// The device path of the entries (device pointers, checked)
+// motion: the motion frame of the _motion and _adaptive entries, or null; change: the change frame of the _adaptive entries, or null
 int run(int W, int H, const float* rgb, const float* feat, const frayhip_view* view, const float* histIn, const struct frayhip_temporal* prm, float* histOut,
-        float* signal, float* variance, hipStream_t stream, frayhip_stats* st, std::chrono::steady_clock::time_point t0, const float* motion = nullptr)
+        float* signal, float* variance, hipStream_t stream, frayhip_stats* st, std::chrono::steady_clock::time_point t0, const float* motion = nullptr,
+        const float* change = nullptr)
 {
     const size_t n = (size_t)W * H;
     TemporalCall T{};
     T.W = W; T.H = H;
     T.rgb = rgb; T.feat = feat; T.motion = (const float4*)motion;
     T.histIn = (const float4*)histIn; T.histOut = (float4*)histOut;
-    T.signal = signal; T.variance = variance;
+    T.signal = signal; T.variance = variance; T.change = change;
     if (view) T.view = *view;
     T.demodulate = prm->demodulate; T.varianceHistory = prm->variance_history;
     T.maxHistory = (float)prm->max_history; T.alphaMin = prm->alpha_min; T.filmOffset = prm->film_offset;
@@ -245,8 +267,10 @@ int run(int W, int H, const float* rgb, const float* feat, const frayhip_view* v
     struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{stream};
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     HIP_TRY(hipEventRecord(E.a, stream));
-    if (motion) hipLaunchKernelGGL(k_tp_accumulate<true>, grid, block, 0, stream, T);
-    else hipLaunchKernelGGL(k_tp_accumulate<false>, grid, block, 0, stream, T);
+    if (change && motion) hipLaunchKernelGGL((k_tp_accumulate<true, true>), grid, block, 0, stream, T);
+    else if (change) hipLaunchKernelGGL((k_tp_accumulate<false, true>), grid, block, 0, stream, T);
+    else if (motion) hipLaunchKernelGGL((k_tp_accumulate<true, false>), grid, block, 0, stream, T);
+    else hipLaunchKernelGGL((k_tp_accumulate<false, false>), grid, block, 0, stream, T);
     HIP_TRY(hipGetLastError());
     if (prm->variance_history > 1) {         // N >= 1 always: with variance_history 1 no pixel takes the spatial estimate
         hipLaunchKernelGGL(k_tp_variance, dim3((unsigned)((W + 15) / 16) * (unsigned)((H + 15) / 16)), block, 0, stream, T);
@@ -385,6 +409,53 @@ int frayhip_temporal_accumulate_motion(int width, int height, const float* rgb, 
     HIP_TRY(hipMemcpy(d_motion, motion, n * 4 * MC, hipMemcpyHostToDevice));
     if (d_hin) HIP_TRY(hipMemcpy(d_hin, hist_in, n * 4 * HC, hipMemcpyHostToDevice));
     if (const int rc = run(width, height, d_rgb, d_feat, prev_view, d_hin, p, d_hout, d_signal, d_var, nullptr, st, t0, d_motion)) return rc;
+    HIP_TRY(hipMemcpy(hist_out, d_hout, n * 4 * HC, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(signal, d_signal, n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(variance, d_var, n * 4, hipMemcpyDeviceToHost));
+    if (st) st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return FRAYHIP_OK;
+}
+
+int frayhip_temporal_accumulate_adaptive_device(int width, int height, const float* d_rgb, const float* d_feat, const float* d_motion, const float* d_change,
+                                                const frayhip_view* prev_view, const float* d_hist_in, const struct frayhip_temporal* p, float* d_hist_out,
+                                                float* d_signal, float* d_variance, void* hip_stream, frayhip_stats* st)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (const int rc = check("frayhip_temporal_accumulate_adaptive_device", width, height, d_rgb, d_feat, prev_view, d_hist_in, p, d_hist_out, d_signal, d_variance,
+                             true, MAY_MOTION, d_motion, true, d_change))
+        return rc;
+    return run(width, height, d_rgb, d_feat, prev_view, d_hist_in, p, d_hist_out, d_signal, d_variance, (hipStream_t)hip_stream, st, t0, d_motion, d_change);
+}
+
+int frayhip_temporal_accumulate_adaptive(int width, int height, const float* rgb, const float* feat, const float* motion, const float* change,
+                                         const frayhip_view* prev_view, const float* hist_in, const struct frayhip_temporal* p, float* hist_out, float* signal,
+                                         float* variance, frayhip_stats* st)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const char* who = "frayhip_temporal_accumulate_adaptive";
+    if (const int rc = check(who, width, height, rgb, feat, prev_view, hist_in, p, hist_out, signal, variance, false, MAY_MOTION, motion, true, change)) return rc;
+    const size_t n = (size_t)width * height;
+    const size_t HC = FRAYHIP_HISTORY_CHANNELS, MC = FRAYHIP_MOTION_CHANNELS;
+    // one allocation, the 16-byte rows first: hist_out, hist_in and motion when given, then rgb, feat, change, signal, variance
+    DeviceArrays B(std::string(who) + ": out of device memory");
+    float* d_hout;
+    if (const int rc = B.alloc(d_hout, n * (HC + (hist_in ? HC : 0) + (motion ? MC : 0) + 3 + FRAYHIP_FEAT_CHANNELS + 1 + 3 + 1))) return rc;
+    float* q = d_hout + HC * n;
+    float* d_hin = nullptr;
+    float* d_motion = nullptr;
+    if (hist_in) { d_hin = q; q += HC * n; }
+    if (motion) { d_motion = q; q += MC * n; }
+    float* d_rgb = q;
+    float* d_feat = d_rgb + 3 * n;
+    float* d_change = d_feat + FRAYHIP_FEAT_CHANNELS * n;
+    float* d_signal = d_change + n;
+    float* d_var = d_signal + 3 * n;
+    HIP_TRY(hipMemcpy(d_rgb, rgb, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_feat, feat, n * 4 * FRAYHIP_FEAT_CHANNELS, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_change, change, n * 4, hipMemcpyHostToDevice));
+    if (d_motion) HIP_TRY(hipMemcpy(d_motion, motion, n * 4 * MC, hipMemcpyHostToDevice));
+    if (d_hin) HIP_TRY(hipMemcpy(d_hin, hist_in, n * 4 * HC, hipMemcpyHostToDevice));
+    if (const int rc = run(width, height, d_rgb, d_feat, prev_view, d_hin, p, d_hout, d_signal, d_var, nullptr, st, t0, d_motion, d_change)) return rc;
     HIP_TRY(hipMemcpy(hist_out, d_hout, n * 4 * HC, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(signal, d_signal, n * 12, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(variance, d_var, n * 4, hipMemcpyDeviceToHost));

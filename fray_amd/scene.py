@@ -236,6 +236,11 @@ def denoise_signal(signal, variance, feat, stats=False, stream=None, **params):
 
 
 _denoise_params = denoise_params         # Scene.render_sequence takes **denoise_params
+
+
+def _sum_stats(a, b):
+    """The stats dict of two calls that together are one step of a sequence: every figure is the sum of the two."""
+    return {k: a[k] + b[k] for k in a}
 _TEMPORAL_FIELDS = ("demodulate", "max_history", "variance_history", "alpha_min", "film_offset", "plane_tolerance", "normal_min_dot")
 
 
@@ -261,7 +266,43 @@ def view_from_camera(camera, width, height):
     return v
 
 
-def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, stream=None, motion=None, **params):
+def change_params(radius=3, gain=1.0):
+    """A frayhip_change with the given fields (the defaults are frayhip_change_defaults')."""
+    p = abi.Change()
+    _check(lib.frayhip_change_defaults(C.byref(p)))
+    p.radius, p.gain = int(radius), float(gain)
+    return p
+
+
+def change_frame(before, after, motion=None, stats=False, stream=None, radius=3, gain=1.0):
+    """The change frame of include/frayhip.h (frayhip_change_frame): before and after are two states [H, W, 4] float32 -- or the Accumulations
+    that hold them (Scene.render_samples, or one component of Scene.render_components) -- of the SAME samples of one seed and view, rendered
+    before and after an edit of the scene; motion [H, W, 8] or None masks the pixels of moved nodes.  numpy arrays go through the host entry;
+    torch tensors on the GPU (storage 16-byte aligned) through the device entry, on `stream` (None: the current stream).  radius 0..3: the
+    window is (2 radius + 1)^2 pixels; gain > 0.  Returns change [H, W] float32 of the inputs' kind, in [0, 1] and exactly 0 where no state in
+    the window differs -- temporal_accumulate's change= -- and with stats=True also the stats dict (ms_total, ms_kernels)."""
+    who = "change_frame"
+    if isinstance(before, Accumulation) and isinstance(after, Accumulation) and before.samples_done != after.samples_done:
+        raise ValueError("%s: before holds %d samples per pixel and after %d" % (who, before.samples_done, after.samples_done))
+    before, after = (a.state if isinstance(a, Accumulation) else a for a in (before, after))
+    p = change_params(radius, gain)
+    named = [("before", before, abi.ACCUM_CHANNELS), ("after", after, abi.ACCUM_CHANNELS)]
+    if motion is not None:
+        named.append(("motion", motion, abi.MOTION_CHANNELS))
+    ins, (H, W), tensors = _frame_inputs(who, named)
+    mot = ins[2] if motion is not None else None
+    st = abi.Stats()
+    if not tensors:
+        out = np.empty((H, W), np.float32)
+        _check(lib.frayhip_change_frame(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(mot), C.byref(p), out.ctypes.data, C.byref(st)))
+    else:
+        with _DeviceCall(ins[0].device, stream) as call:
+            out = call.torch.empty((H, W), dtype=call.torch.float32, device=ins[0].device)
+            _check(lib.frayhip_change_frame_device(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(mot), C.byref(p), out.data_ptr(), call.handle, C.byref(st)))
+    return (out, st.as_dict()) if stats else out
+
+
+def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, stream=None, motion=None, change=None, **params):
     """The temporal stage of include/frayhip.h (frayhip_temporal_accumulate): rgb [H, W, 3] and feat [H, W, 10] of the current frame, prev_view
     (view_from_camera of the previous frame's camera) and hist_in [H, W, 12] (the previous call's history), both None for the first frame;
     float32.  numpy arrays go through the host entry; torch tensors on the GPU through the device entry, on `stream` (None: the current
@@ -269,7 +310,10 @@ def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, st
     variance are denoise_signal's inputs -- and with stats=True also the stats dict (ms_total, ms_kernels).
     motion: the motion frame [H, W, 8] of Scene.render_features_motion, of the inputs' kind (a tensor's storage 16-byte aligned): the history is
     fetched where the pixel's surface point was before the scene's nodes moved (frayhip_temporal_accumulate_motion).  None: exactly the call
-    above."""
+    above.
+    change: a change frame [H, W] of the inputs' kind (change_frame): the history is shortened per pixel -- dropped where change >= 1, blended
+    with a larger factor where it is > 0, taken as it is where it is 0 (frayhip_temporal_accumulate_adaptive, with or without motion).  None:
+    exactly the calls above."""
     p = temporal_params(**params)
     if (prev_view is None) != (hist_in is None):
         raise ValueError("temporal_accumulate: prev_view and hist_in must both be given or both be None")
@@ -278,14 +322,20 @@ def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, st
     named = [("rgb", rgb, 3), ("feat", feat, abi.FEAT_CHANNELS)] + ([("hist_in", hist_in, abi.HISTORY_CHANNELS)] if hist_in is not None else [])
     if motion is not None:
         named.append(("motion", motion, abi.MOTION_CHANNELS))
+    if change is not None:
+        named.append(("change", change, 0))
     ins, (H, W), tensors = _frame_inputs("temporal_accumulate", named)
     hin = ins[2] if hist_in is not None else None
+    chg = ins.pop() if change is not None else None
     mot = ins[-1] if motion is not None else None
     view = C.byref(prev_view) if prev_view is not None else None
     st = abi.Stats()
     if not tensors:
         hist, signal, var = (np.empty((H, W, abi.HISTORY_CHANNELS), np.float32), np.empty((H, W, 3), np.float32), np.empty((H, W), np.float32))
-        if mot is not None:
+        if chg is not None:
+            _check(lib.frayhip_temporal_accumulate_adaptive(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(mot), _ptr(chg), view, _ptr(hin), C.byref(p),
+                                                            hist.ctypes.data, signal.ctypes.data, var.ctypes.data, C.byref(st)))
+        elif mot is not None:
             _check(lib.frayhip_temporal_accumulate_motion(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(mot), view, _ptr(hin), C.byref(p), hist.ctypes.data,
                                                           signal.ctypes.data, var.ctypes.data, C.byref(st)))
         else:
@@ -295,7 +345,10 @@ def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, st
         with _DeviceCall(ins[0].device, stream) as call:
             new = lambda *shape: call.torch.empty(shape, dtype=call.torch.float32, device=ins[0].device)
             hist, signal, var = new(H, W, abi.HISTORY_CHANNELS), new(H, W, 3), new(H, W)
-            if mot is not None:
+            if chg is not None:
+                _check(lib.frayhip_temporal_accumulate_adaptive_device(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(mot), _ptr(chg), view, _ptr(hin), C.byref(p),
+                                                                       hist.data_ptr(), signal.data_ptr(), var.data_ptr(), call.handle, C.byref(st)))
+            elif mot is not None:
                 _check(lib.frayhip_temporal_accumulate_motion_device(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(mot), view, _ptr(hin), C.byref(p),
                                                                      hist.data_ptr(), signal.data_ptr(), var.data_ptr(), call.handle, C.byref(st)))
             else:
@@ -1054,8 +1107,31 @@ class Scene:
                                               "indirect": i_out, "direct_rgb": d_rgb, "indirect_rgb": i_rgb, "noise_direct": d_noise,
                                               "noise_indirect": i_noise, "features_frame": feat}
 
+    def _sequence_samples(self, fr, count, state, stream):
+        """render_sequence's own call of frayhip_render_samples_device (state: an Accumulation) or frayhip_render_components_device (a pair of
+        them) for `count` more samples of frame record `fr`, without the counting kernels that stats=True asks for: (rgb or (direct_rgb,
+        indirect_rgb), stats dict).  The states are fresh device states of the record's seed."""
+        import torch
+        W, H = self.frame_size
+        pair = isinstance(state, tuple)
+        first = state[0] if pair else state
+        st = abi.Stats()
+        req = abi.Samples(sample_first=first.samples_done, sample_count=int(count))
+        with torch.cuda.stream(stream):
+            rgb = [torch.zeros((H, W, 3), dtype=torch.float32, device="cuda") for _ in range(2 if pair else 1)]
+        handle = C.c_void_p(stream.cuda_stream)
+        if pair:
+            _check(lib.frayhip_render_components_device(self._dev, C.byref(fr), C.byref(req), None, _ptr(state[0].state), _ptr(state[1].state),
+                                                        _ptr(rgb[0]), _ptr(rgb[1]), None, None, handle, C.byref(st)))
+        else:
+            _check(lib.frayhip_render_samples_device(self._dev, C.byref(fr), C.byref(req), None, _ptr(state.state), _ptr(rgb[0]), None, handle,
+                                                     C.byref(st)))
+        for a in (state if pair else (state,)):
+            a.samples_done = req.samples_done
+        return (tuple(rgb) if pair else rgb[0]), st.as_dict()
+
     def render_sequence(self, cameras, seed=42, feature_samples=4, temporal=None, edit=None, split=False, temporal_direct=None, temporal_indirect=None,
-                        **denoise_params):
+                        change_samples=0, change=None, **denoise_params):
         """A generator over a fly-through of a static scene with temporal accumulation (include/frayhip.h "temporal accumulation"): for the k-th
         abi.Camera of `cameras` it sets the view, renders the feature frame and the frame with seed + k (equal seeds would accumulate the same
         noise every frame), accumulates onto the previous frame's history reprojected into this view, runs the a-trous levels on the accumulated
@@ -1082,11 +1158,41 @@ class Scene:
         override it per component, and demodulate, film_offset, plane_tolerance and normal_min_dot must stay equal.  Where the caller names no
         max_history the direct component's is 8 and the indirect one's the default 32: a shadow that moves over a static surface lives in the
         direct component, and its residue after j frames is (1 - 1/8)^j of the step instead of (1 - 1/32)^j, while direct light at one
-        next-event sample per path sample is the less noisy component.  The 8 is a choice, not a measurement."""
+        next-event sample per path sample is the less noisy component.  The 8 is a choice, not a measurement.
+        change_samples: 0 runs exactly the launches above.  n > 0 (needs edit=, ValueError otherwise; n = min(change_samples, spp)) detects what
+        the edit changed in the light a pixel receives -- moved lights, the shadows and reflections of moved objects -- and shortens the history
+        there (include/frayhip.h "change frames").  Frame 0 is as above.  Frame k >= 1: after the snapshot of node_transforms() and BEFORE
+        edit(k, scene), samples [0, n) of this frame's view and seed are rendered into a fresh device state (the probe: render_samples, or
+        render_components with split) while the scene is still in frame k - 1's state; after the edit and the feature / motion pass the frame
+        itself is rendered as those n samples into a fresh state, the state is cloned, and the remaining spp - n samples follow, so raw is still
+        render(seed + k) bit for bit (resumable frames) and the frame costs n / spp more rays (info["render"] and, with split, info["temporal"] then
+        hold the sums of their two calls' figures).  change_frame(probe, clone, motion) then gives the
+        change frame, and the accumulation takes it (temporal_accumulate(change=)).  A pixel none of whose n paths met anything the edit changed
+        has change 0 where its whole window has, and is accumulated exactly as without change_samples.  With split there is one change frame
+        per component, from that component's pair of states, and the accumulation of frames k >= 1 is UNFUSED: two temporal_accumulate(change=)
+        calls on split_history_parts(history), joined by join_history_parts (there is no adaptive form of the split kernel).  info then also
+        holds "change" (or "change_direct" and "change_indirect") and the "probe" stats dict; they are None in frame 0.
+        change: a dict of change_frame's radius and gain (needs change_samples > 0).  radius 3 and gain 1 are a choice, not a measurement."""
         self._need_dev()
         import torch
         W, H = self.frame_size
         spp = self.samples_per_pixel()
+        change_samples = int(change_samples)
+        if change_samples < 0:
+            raise ValueError("render_sequence: change_samples must be >= 0, got %d" % change_samples)
+        if change_samples > 0 and edit is None:
+            raise ValueError("render_sequence: change_samples needs edit=: without an edit nothing changes between the probe and the frame")
+        if change is not None and change_samples == 0:
+            raise ValueError("render_sequence: change= needs change_samples > 0")
+        cparams = dict(change or {})
+        if set(cparams) - {"radius", "gain"}:
+            raise TypeError("render_sequence: change= takes radius and gain, got %s" % ", ".join(sorted(set(cparams) - {"radius", "gain"})))
+        cp = change_params(**cparams)
+        if not 0 <= cp.radius <= 3:
+            raise ValueError("render_sequence: change=: radius must be 0..3, got %d" % cp.radius)
+        if not (np.isfinite(cp.gain) and cp.gain > 0):
+            raise ValueError("render_sequence: change=: gain must be finite and > 0, got %r" % cp.gain)
+        n_probe = min(change_samples, spp)
         if not split and (temporal_direct is not None or temporal_indirect is not None):
             raise ValueError("render_sequence: temporal_direct and temporal_indirect need split=True")
         if split:
@@ -1121,13 +1227,19 @@ class Scene:
                 C.memmove(C.byref(self.desc.camera), C.byref(cam), C.sizeof(abi.Camera))
                 self.beginFrame()
                 motion = None
+                fr = self._frame(abi.MODE_RENDER, (seed + k) & 0xFFFFFFFF, 0, 1, 0, False)
+                fresh = lambda: Accumulation.empty((W, H), fr.seed, device="cuda")
+                probing = n_probe > 0 and k > 0
+                probe, pst = None, None
                 if edit is not None:
                     prev = self.node_transforms()
+                    if probing:                 # samples [0, n) of this frame, in the scene as the previous frame saw it
+                        probe = (fresh(), fresh()) if split else fresh()
+                        _, pst = self._sequence_samples(fr, n_probe, probe, stream)
                     if k:
                         edit(k, self)
                 feat = torch.empty((H, W, abi.FEAT_CHANNELS), dtype=torch.float32, device="cuda")
                 fst, rst = abi.Stats(), abi.Stats()
-                fr = self._frame(abi.MODE_RENDER, (seed + k) & 0xFFFFFFFF, 0, 1, 0, False)
                 if edit is not None:
                     motion = torch.empty((H, W, abi.MOTION_CHANNELS), dtype=torch.float32, device="cuda")
                     _check(lib.frayhip_render_features_motion_device(self._dev, C.byref(fr), n_feat, prev, len(prev), feat.data_ptr(),
@@ -1135,10 +1247,25 @@ class Scene:
                 else:
                     _check(lib.frayhip_render_features_device(self._dev, C.byref(fr), n_feat, feat.data_ptr(), handle, C.byref(fst)))
                 if split:
-                    state = tuple(Accumulation.empty((W, H), fr.seed, device="cuda") for _ in range(2))
-                    d_rgb, i_rgb, _state, rst = self.render_components(spp, state, seed=fr.seed, stats=True, stream=stream)
-                    hist, sig_d, sig_i, var_d, var_i, tst = temporal_accumulate_split(d_rgb, i_rgb, feat, view, hist, motion=motion, direct=tdirect,
-                                                                                      indirect=tindirect, stats=True, stream=stream)
+                    state = (fresh(), fresh())
+                    chg_d = chg_i = None
+                    if probing:
+                        (d_rgb, i_rgb), rst = self._sequence_samples(fr, n_probe, state, stream)
+                        first = [a.state.clone() for a in state]
+                        if spp > n_probe:
+                            (d_rgb, i_rgb), rst2 = self._sequence_samples(fr, spp - n_probe, state, stream)
+                            rst = _sum_stats(rst, rst2)
+                        chg_d = change_frame(probe[0], first[0], motion, stream=stream, **cparams)
+                        chg_i = change_frame(probe[1], first[1], motion, stream=stream, **cparams)
+                        hd, hi = split_history_parts(hist)
+                        hd, sig_d, var_d, tst_d = temporal_accumulate(d_rgb, feat, view, hd, stats=True, stream=stream, motion=motion, change=chg_d, **tdirect)
+                        hi, sig_i, var_i, tst_i = temporal_accumulate(i_rgb, feat, view, hi, stats=True, stream=stream, motion=motion, change=chg_i, **tindirect)
+                        hist = join_history_parts(hd, hi)
+                        tst = _sum_stats(tst_d, tst_i)
+                    else:
+                        d_rgb, i_rgb, _state, rst = self.render_components(spp, state, seed=fr.seed, stats=True, stream=stream)
+                        hist, sig_d, sig_i, var_d, var_i, tst = temporal_accumulate_split(d_rgb, i_rgb, feat, view, hist, motion=motion, direct=tdirect,
+                                                                                          indirect=tindirect, stats=True, stream=stream)
                     d_out, dst = denoise_signal(sig_d, var_d, feat, stats=True, stream=stream, **denoise_params)
                     i_out, ist = denoise_signal(sig_i, var_i, feat, stats=True, stream=stream, **denoise_params)
                     view = view_from_camera(self.desc.camera, W, H)
@@ -1148,18 +1275,33 @@ class Scene:
                             "features": fst.as_dict(), "temporal": tst, "denoise_direct": dst, "denoise_indirect": ist}
                     if edit is not None:
                         info["motion"] = motion
+                    if n_probe > 0:
+                        info.update(change_direct=chg_d, change_indirect=chg_i, probe=pst)
                     yield d_out + i_out, d_rgb + i_rgb, info
                     continue
-                raw = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
-                _check(lib.frayhip_render_device(self._dev, C.byref(fr), raw.data_ptr(), None, None, handle, C.byref(rst)))
-                hist, signal, var, tst = temporal_accumulate(raw, feat, view, hist, stats=True, stream=stream, motion=motion, **tparams)
+                chg = None
+                if probing:
+                    state = fresh()
+                    raw, rdict = self._sequence_samples(fr, n_probe, state, stream)
+                    first = state.state.clone()
+                    if spp > n_probe:
+                        raw, rdict2 = self._sequence_samples(fr, spp - n_probe, state, stream)
+                        rdict = _sum_stats(rdict, rdict2)
+                    chg = change_frame(probe, first, motion, stream=stream, **cparams)
+                else:
+                    raw = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+                    _check(lib.frayhip_render_device(self._dev, C.byref(fr), raw.data_ptr(), None, None, handle, C.byref(rst)))
+                    rdict = rst.as_dict()
+                hist, signal, var, tst = temporal_accumulate(raw, feat, view, hist, stats=True, stream=stream, motion=motion, change=chg, **tparams)
                 out, dst = denoise_signal(signal, var, feat, stats=True, stream=stream, **denoise_params)
                 view = view_from_camera(self.desc.camera, W, H)
                 info = {"features_frame": feat, "history": hist, "signal": signal, "variance": var, "view": view,
-                        "film_offset": tparams["film_offset"], "render": rst.as_dict(), "features": fst.as_dict(), "temporal": tst,
+                        "film_offset": tparams["film_offset"], "render": rdict, "features": fst.as_dict(), "temporal": tst,
                         "denoise": dst}
                 if edit is not None:
                     info["motion"] = motion
+                if n_probe > 0:
+                    info.update(change=chg, probe=pst)
                 yield out, raw, info
         finally:
             if self.desc is not None:

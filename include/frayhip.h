@@ -734,7 +734,9 @@ int  frayhip_render_features_device(frayhip_scene* s, const frayhip_frame* f, in
  * FRAYHIP_E_ARG, before the device is touched: what frayhip_render_features refuses, a NULL prev_T or motion, n_prev != the node count, a
  *   non-finite double in prev_T, feat and motion overlapping.  FRAYHIP_E_UNSUPPORTED: as there.
  * Not covered: moved lights; shadows and reflections of moved objects (their pixels' first hits did not move, so they ghost as in a static
- *   sequence); motion blur; vertex edits (frayhip_scene_update does not take them). */
+ *   sequence); motion blur; vertex edits (frayhip_scene_update does not take them).  Moved lights and those shadows and reflections are what
+ *   a change frame detects (frayhip_change_frame, frayhip_temporal_accumulate_adaptive below): the motion frame itself still follows a node's
+ *   own pixels only. */
 #define FRAYHIP_MOTION_CHANNELS 8   /* per pixel, two 16-byte rows: {P'.xyz, moved}, {n'.xyz, 0} */
 int  frayhip_render_features_motion(frayhip_scene* s, const frayhip_frame* f, int n_samples, const frayhip_transform* prev_T, int n_prev,
                                     float* feat, float* motion, frayhip_stats* st);
@@ -913,11 +915,63 @@ int  frayhip_temporal_accumulate_split_device(int width, int height, const float
                                               const struct frayhip_temporal* p_direct, const struct frayhip_temporal* p_indirect,
                                               float* d_hist_out, float* d_signal_direct, float* d_signal_indirect, float* d_variance_direct,
                                               float* d_variance_indirect, void* hip_stream, frayhip_stats* st);
+
+/* ---- change frames (where the light a pixel receives changed between two states of the scene, scene-free) ------------------------------------
+ * A frame is a function of (scene, view, seed) bit for bit, so what an edit changed can be detected exactly: render samples [0, n) of a view
+ * and seed before the edit and the same samples after it (two frayhip_render_samples or frayhip_render_components states); a pixel none of
+ * whose paths met anything that changed holds the same bits in both, and its difference is exactly zero.  frayhip_change_frame turns such a
+ * pair into a per-pixel change in [0, 1], and frayhip_temporal_accumulate_adaptive shortens the history where it is not zero -- which covers
+ * moved lights and the shadows and reflections of moved objects, whose pixels pass every surface test.
+ *
+ * accum_before, accum_after: two FRAYHIP_ACCUM_CHANNELS states (W*H*4 floats) that hold the same samples of the same seed and view; the
+ * caller's word is trusted.  The sample count cancels, so the states' sums are used as they stand.  motion: a motion frame or NULL.  FP32
+ * throughout, no contraction (tests/change_ref.py restates it in numpy).
+ * Per texel q:  la = ((sum.r + sum.g) + sum.b) / 3.0f of accum_before, lb likewise of accum_after; m_q = fmaxf(la, lb), d_q = fabsf(lb - la);
+ *   d_q = m_q = 0 when la or lb is not finite, when m_q <= 0, and, with a motion frame, when the texel's `moved` channel is not 0 (a moved
+ *   node's own pixels are the motion frame's business).
+ * Per pixel p:  sd = sum(d_q), sm = sum(m_q) over the (2 radius + 1)^2 window around p, j outer, i inner, skipping taps outside the image;
+ *   change_p = sm > 0 ? fminf(1.0f, gain * (sd / sm)) : 0.0f.  No surface tests in the window: a shadow crosses object edges.
+ * radius 3 and gain 1 are a maintainer's choice, not a measurement.
+ * Kernel: k_ch_frame, one launch; a 16x16 block stages the (d, m) pairs of the 22x22 texels its windows can reach in LDS (each state row read
+ *   once, as a float4), then each thread sums its window from the tile.  No work buffers.  Device pointers: both states and the motion frame
+ *   16-byte aligned, change 4-byte; the stream contract and *st as frayhip_temporal_accumulate_device.
+ * FRAYHIP_E_ARG, before the device is touched: width or height < 1 or W*H > 2^30; a NULL pointer other than motion; radius outside 0..3; a
+ *   gain that is NaN, infinite or <= 0; change overlapping an input; a misaligned device pointer. */
+/* A struct tag without a typedef, as frayhip_denoise. */
+struct frayhip_change {
+    int32_t radius;            /* the window is (2 radius + 1)^2 texels; 0..3, default 3                                     */
+    float   gain;              /* change = min(1, gain * sum|difference| / sum(max)); finite and > 0, default 1             */
+};
+int  frayhip_change_defaults(struct frayhip_change* p);
+int  frayhip_change_frame(int width, int height, const float* accum_before, const float* accum_after, const float* motion,
+                          const struct frayhip_change* p, float* change, frayhip_stats* st);
+int  frayhip_change_frame_device(int width, int height, const float* d_accum_before, const float* d_accum_after, const float* d_motion,
+                                 const struct frayhip_change* p, float* d_change, void* hip_stream, frayhip_stats* st);
+/* Gradient-adaptive accumulation: frayhip_temporal_accumulate when motion is NULL and frayhip_temporal_accumulate_motion otherwise, with a
+ * change frame (W*H floats) that shortens the history per pixel.  Step 3 becomes, with g = change_p, read only where a history was fetched
+ * (sum(b) > 0):
+ *   !(g < 1.0f)   (1, above 1, NaN) the pixel takes no history: acc = c, m1 = l, m2 = l * l, N = 1
+ *   g > 0         N0 = fminf(N_hist + 1, max_history); a0 = fmaxf(alpha_min, 1 / N0); alpha = a0 + g * (1.0f - a0);
+ *                 N = fminf(N0, 1.0f / alpha); the blend of step 3 with this alpha
+ *   otherwise     (+0, -0, negative) step 3 as it stands, so a change frame of zeros gives every output bit of the plain (or motion) entry
+ * k_tp_variance runs unchanged on the finished hist_out: a pixel whose N dropped below variance_history takes the spatial estimate again.
+ * Kernel: k_tp_accumulate<MOTION, true>; the plain and the motion entries keep their instantiations.  FRAYHIP_E_ARG: the plain entry's list,
+ *   and a NULL, misaligned or overlapping (with an output) change. */
+int  frayhip_temporal_accumulate_adaptive(int width, int height, const float* rgb, const float* feat, const float* motion, const float* change,
+                                          const frayhip_view* prev_view, const float* hist_in, const struct frayhip_temporal* p, float* hist_out,
+                                          float* signal, float* variance, frayhip_stats* st);
+int  frayhip_temporal_accumulate_adaptive_device(int width, int height, const float* d_rgb, const float* d_feat, const float* d_motion,
+                                                 const float* d_change, const frayhip_view* prev_view, const float* d_hist_in,
+                                                 const struct frayhip_temporal* p, float* d_hist_out, float* d_signal, float* d_variance,
+                                                 void* hip_stream, frayhip_stats* st);
 /* Not covered: SVGF's wider 3 x 3 retry when no bilinear tap counts, feeding a filtered level back into the history, moved lights and the
  * shadows and reflections of moved objects (only a pixel's own first hit is carried back: frayhip_render_features_motion), motion blur,
  * specular motion vectors (what a mirror shows moves with the camera while its first hit does not), learned
  * denoisers, adaptive and stereo frames, and denoising across ranks (gather the frame and its features first: frayhip_gather_buckets takes a
- * channel count). */
+ * channel count).  With a change frame the accumulation does shorten the history under a moved light and under the shadows and reflections of
+ * moved objects (the history is dropped or faded there, not carried to where the shadow went).  Still not covered with it: a fused adaptive
+ * form of the split entry, a moved node's own pixels entering changed light (their difference is masked: they are the motion frame's
+ * business), view-dependent change under camera motion, and any tuning beyond gain. */
 
 /* Multi-GPU tile exchange helpers.  pack: gathers this rank's buckets from a
  * full-frame device buffer into a compact bucket-major buffer of
