@@ -8,6 +8,11 @@ library with the scene resident in HBM.
 N > 1 is strong scaling of the same frame: the reference's 48x48 buckets are dealt round-robin to
 the ranks (no data-path collective while rendering), then one RCCL gather of the packed buckets to
 rank 0, inside the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline figure needs and no more: set-up, one instrumented frame that counts the rays,
+the warm-up, the timed steps, --dump-outputs, the line.  --full adds every measurement that takes a run of its
+own -- the serialised pass behind the per-kernel roofline, the same frame in contracted arithmetic, the CPU
+baseline with its parity check against the oracle and the reference's object code -- to the same line.
 """
 import argparse
 import json
@@ -218,8 +223,11 @@ def main():
     ap.add_argument("--workload", default="cornell_pt64", choices=sorted(WORKLOADS))
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--spp-chunk", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-serial-pass", action="store_true", help="skip the serialised pass that times every launch alone (path tracing): durations then come from the timed region")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run what takes runs of its own: the serialised pass (per-kernel durations of the roofline), "
+                    "the same frame with option fp_contract = 1 (`contracted`), the CPU baseline with its parity figures (`cpu_baseline`).  Off by default: a plain run "
+                    "reports the headline figure, with the roofline's durations taken from the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-serial-pass", action="store_true", help="with --full: skip the serialised pass that times every launch alone (path tracing): durations then come from the timed region")
     ap.add_argument("--check", action="store_true", help="N > 1: also render the whole frame on rank 0 and require the gathered frame to equal it")
     ap.add_argument("--torch-gather", action="store_true", help="N > 1: exchange through torch.distributed.gather instead of frayhip_gather_buckets")
     ap.add_argument("--shard-of", type=int, default=0, help="diagnosis on one GPU: render only ONE rank's share of an N-rank run (buckets r mod N, r = --shard-rank), no exchange")
@@ -227,9 +235,9 @@ def main():
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL; the real multi-GPU run) or gloo (rehearsal: N ranks sharing GPU 0)")
     ap.add_argument("--arith", default="exact", choices=["exact", "contracted"],
                     help="exact (default): the reference's arithmetic everywhere, every pixel the oracle's bit for bit.  contracted: option fp_contract = 1 for the timed region "
-                    "(path tracing past a sample's first closest hit on kernels built with fused multiply-adds; colour within 1e-4 RMS).  The default run reports the "
+                    "(path tracing past a sample's first closest hit on kernels built with fused multiply-adds; colour within 1e-4 RMS).  A --full run reports the "
                     "contracted figures too, in a `contracted` object beside the exact line")
-    ap.add_argument("--no-contracted", action="store_true", help="skip the second timed region that renders the same frame with option fp_contract = 1 (profiling passes: one arithmetic per run)")
+    ap.add_argument("--no-contracted", action="store_true", help="with --full: skip the second timed region that renders the same frame with option fp_contract = 1 (profiling passes: one arithmetic per run)")
     ap.add_argument("--library-gather", action="store_true", help="with --backend gloo: still exchange through frayhip_gather_buckets (the library binds whatever RCCL "
                     "FRAYHIP_RCCL_LIBRARY names -- on a one-GPU box the test suite's loopback stand-in, since RCCL itself refuses two ranks on one device)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed (the frame; hit ids and distances "
@@ -407,7 +415,7 @@ def main():
     # stream it runs on) -- the same mode the kept rocprofv3 kernel trace under profiles/ is collected in.
     serial = None
     serial_note = None
-    if rank == 0 and world == 1 and scene.settings.gi and not args.no_serial_pass:
+    if rank == 0 and world == 1 and scene.settings.gi and args.full and not args.no_serial_pass:
         lanes_before = int(os.environ.get("FRAYHIP_PT_LANES", "4") or 4)       # the library's own default (render_state.hpp) unless the environment presets it
         # A frame that takes seconds (4096 x 4096 x 1024 spp: 13 s) is not rendered twice more: its serialised pass renders the SAME frame with fewer
         # samples per pixel -- the batches, hence the launches, keep their size (a batch's samples per pixel follow from the queue budget and the frame's
@@ -446,7 +454,7 @@ def main():
     # counted by its own instrumented pass, and kept for the parity figures of cpu_baseline below.  The default line stays the exact one.
     contracted = None
     exact_frame = frame
-    if rank == 0 and world == 1 and scene.settings.gi and mode == abi.MODE_RENDER and args.arith == "exact" and args.shard_of <= 1 and not args.no_contracted:
+    if rank == 0 and world == 1 and scene.settings.gi and mode == abi.MODE_RENDER and args.arith == "exact" and args.shard_of <= 1 and args.full and not args.no_contracted:
         exact_frame = frame.clone()
         scene.set_option("fp_contract", 1)
         st_c = step(stats=True)
@@ -602,7 +610,7 @@ def main():
                                             "bit_identical_pixels": float((cframe == exact_frame).all(dim=2).float().mean())}
             out["contracted"] = contracted
             out["value_contracted"] = contracted["value"]
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(fray_amd, abi, wl, args.seed, gpu_frame=exact_frame.cpu().numpy(),
                                                other_frames={"contracted": cframe.cpu().numpy()} if cframe is not None else None) if mode == abi.MODE_RENDER else None
             if contracted and out["cpu_baseline"] and "other_frames_vs_oracle_on_the_sample" in out["cpu_baseline"]:

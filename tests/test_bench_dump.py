@@ -40,7 +40,7 @@ def test_dump_of_a_large_output_is_the_same_seeded_sample_under_the_limit(tmp_pa
 def test_bench_dumps_the_last_timed_step(fray, gpu, tmp_path, workload):
     """The files hold the timed path's own result: the hit records / the exact-arithmetic frame, not the contracted frame bench.py renders
     into the same buffer afterwards."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0", "--no-cpu-baseline", "--no-serial-pass",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-serial-pass",
            "--workload", workload, "--dump-outputs", str(tmp_path / "out")]
     out = run_in_clean_child(cmd, str(tmp_path / "bench.log"), timeout=600)
     lines = [l for l in out.splitlines() if l.startswith("{")]

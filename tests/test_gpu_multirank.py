@@ -164,13 +164,14 @@ def test_union_of_eight_shards_equals_the_full_frame_at_full_size(fray, gpu, wor
 
 
 def test_bench_line_contract_single_gpu(tmp_path):
-    """`python bench.py` (N = 1, a short run) prints ONE JSON line with the fields the driver reads, the roofline of the dominant
-    kernel with non-overlapped launch durations, and the CPU baseline with its in-run parity check."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"]
+    """`python bench.py --full` (N = 1, a short run) prints ONE JSON line with the fields the driver reads, the roofline of the dominant
+    kernel with non-overlapped launch durations, the contracted frame's figures and the CPU baseline with its in-run parity check."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full"]
     out = run_in_clean_child(cmd, str(tmp_path / "bench.log"), timeout=600)
     lines = [l for l in out.splitlines() if l.startswith("{")]
-    assert len(lines) == 1, out[-3000:]
+    assert len(lines) == 1 and "[exit code 0]" in out, out[-3000:]
     r = json.loads(lines[0])
+    assert r["value_contracted"] == r["contracted"]["value"] > 0 and max(r["contracted"]["rms_per_channel"]) <= 1e-4
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline"):
         assert k in r, k
@@ -188,3 +189,25 @@ def test_bench_line_contract_single_gpu(tmp_path):
         assert k in cb, k
     par = cb["gpu_frame_vs_oracle_on_the_sample"]
     assert max(par["rms_per_channel"]) <= 1e-4 and par["bit_identical_pixels"] >= 0.99
+
+
+def test_bench_plain_run_is_lean(tmp_path):
+    """`python bench.py --gpus 1 --steps N --warmup W` without --full: the same headline fields, none of the legs that take runs of their own
+    (serialised pass, contracted frame, CPU baseline), and at most 30 s of the whole run, start to exit, outside its N + W steps."""
+    import time
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"]
+    t0 = time.perf_counter()
+    out = run_in_clean_child(cmd, str(tmp_path / "bench.log"), timeout=600)
+    wall = time.perf_counter() - t0
+    lines = [l for l in out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and "[exit code 0]" in out, out[-3000:]
+    r = json.loads(lines[0])
+    assert r["n_gpus"] == 1 and r["steps"] == 2 and r["warmup"] == 1 and r["unit"] == "Mrays/s" and r["dtype"] == "f64" and r["higher_is_better"] is True
+    assert "cornell_box.fray 1920x1080 64spp" in r["config"]["workload"] and r["metric"].endswith("at 1920x1080, 64spp path trace")
+    assert abs(r["value"] - r["config"]["rays_per_frame"] / (r["ms_per_step"] * 1e-3) / 1e6) < 1e-6 * r["value"]
+    for k in ("cpu_baseline", "contracted", "value_contracted"):
+        assert k not in r, k
+    assert r["roofline"]["durations_from"] == "the timed region"
+    outside = wall - 3 * r["ms_per_step"] * 1e-3
+    print("plain run: %.1f s in all, %.1f s outside its steps" % (wall, outside))
+    assert outside <= 30.0, outside

@@ -7,7 +7,7 @@ mkdir -p $OUT
 for w in $WLS; do
   for l in $LIBS; do
     if [ "$l" = "default" ]; then unset FRAYHIP_LIB; else export FRAYHIP_LIB=$PWD/build/ab/$l/libfrayhip.so; fi
-    timeout -k 10 300 python bench.py --steps $STEPS --warmup 2 --no-cpu-baseline --workload $w > $OUT/${l}_$w.json 2> $OUT/${l}_$w.err || { echo "$l $w FAILED" >> $OUT/summary.txt; continue; }
+    timeout -k 10 300 python bench.py --full --steps $STEPS --warmup 2 --no-cpu-baseline --workload $w > $OUT/${l}_$w.json 2> $OUT/${l}_$w.err || { echo "$l $w FAILED" >> $OUT/summary.txt; continue; }
     python - "$OUT/${l}_$w.json" "$l" "$w" >> $OUT/summary.txt <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
