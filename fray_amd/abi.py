@@ -276,6 +276,10 @@ SYMBOLS = {
     "frayhip_change_frame_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(Change), VP, VP, P(Stats)]),
     "frayhip_temporal_accumulate_adaptive": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, VP, P(View), VP, P(Temporal), VP, VP, VP, P(Stats)]),
     "frayhip_temporal_accumulate_adaptive_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, VP, P(View), VP, P(Temporal), VP, VP, VP, VP, P(Stats)]),
+    "frayhip_temporal_accumulate_split_adaptive": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, VP, VP, VP, P(View), VP, P(Temporal), P(Temporal), VP, VP, VP, VP,
+                                                             VP, P(Stats)]),
+    "frayhip_temporal_accumulate_split_adaptive_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, VP, VP, VP, P(View), VP, P(Temporal), P(Temporal), VP, VP,
+                                                                    VP, VP, VP, VP, P(Stats)]),
     "frayhip_camera_rays": (C.c_int, [VP, i64, VP, C.c_int, VP, VP]),
     "frayhip_camera_rays_device": (C.c_int, [VP, i64, VP, C.c_int, VP, VP, VP]),
     "frayhip_trace_rays": (C.c_int, [VP, i64, VP, VP, C.c_int, VP, VP, VP, P(Stats)]),

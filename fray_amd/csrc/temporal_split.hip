@@ -1,4 +1,5 @@
-// C ABI, split temporal accumulation (include/frayhip.h "split temporal accumulation"): frayhip_temporal_accumulate_split and its _device entry.
+// C ABI, split temporal accumulation (include/frayhip.h "split temporal accumulation"): frayhip_temporal_accumulate_split,
+// frayhip_temporal_accumulate_split_adaptive and their _device entries.
 // temporal.hip's stage for two signals of one frame -- a frame's direct and indirect light (frayhip_render_components) -- with one history of
 // five float4 rows a pixel: the projection, the footprint and the surface tests run once, each counted tap is read once, and everything per
 // component is temporal.hip's expression on the other component's inputs, so each group of outputs equals frayhip_temporal_accumulate[_motion]'s
@@ -7,7 +8,9 @@
 //   k_tp_accumulate_split  per pixel: both signals, one projection into the previous view, four taps of five float4 rows each, the seven history
 //                          sums once per component, the blend with each component's max_history and alpha_min; writes the five history rows,
 //                          both signals, and each component's temporal variance where its N >= its variance_history.  <MOTION> as
-//                          k_tp_accumulate's
+//                          k_tp_accumulate's.  <MOTION, ADAPTIVE>: one change frame per component (change.hip) shortens that component's
+//                          history per pixel, by k_tp_accumulate<MOTION, true>'s three cases; the two components may take different cases
+//                          in one pixel.  <MOTION, false> are the two kernels as they were
 //   k_tp_variance_split    per pixel with N_D < variance_history_D or N_I < variance_history_I: the 7x7 window of the finished history, its
 //                          surface tests once, the moments' sums per component; the 16x16 block stages rows 1, 2 and 4 of the 22x22 texels as
 //                          three planes of float4; a block without such a pixel stages nothing
@@ -36,6 +39,7 @@ struct TemporalSplitCall {
     frayhip_view view;          // read only with histIn
     int demodulate, varianceHistory[2];
     float maxHistory[2], alphaMin[2], filmOffset, planeTolerance, normalMinDot;
+    const float* change[2];     // k_tp_accumulate_split<MOTION, true> only: one float a pixel per component
 };
 
 // One component's history sums over the counted taps, and k_tp_accumulate's steps on them
@@ -66,7 +70,36 @@ static __device__ __forceinline__ TpBlend tp_blend(TpSums h, float sb, float cr,
     return o;
 }
 
-template <bool MOTION>
+// tp_blend with a component's change g (0 where no history was fetched): k_tp_accumulate<MOTION, true>'s three cases, each sum and division
+// in that kernel's order
+static __device__ __forceinline__ TpBlend tp_blend_adaptive(TpSums h, float sb, float cr, float cg, float cb, float g, float maxHistory, float alphaMin)
+{
+    const float l = tp_lum(cr, cg, cb);
+    const float l2 = l * l;
+    TpBlend o{cr, cg, cb, 1.0f, l, l2};
+    if (!(g < 1.0f)) {
+        // changed through and through (1, above 1, NaN): no history, the first-frame values above
+    } else if (g > 0.0f) {
+        h.r = h.r / sb; h.g = h.g / sb; h.b = h.b / sb; h.n = h.n / sb; h.m1 = h.m1 / sb; h.m2 = h.m2 / sb;
+        const float N0 = fminf(h.n + 1.0f, maxHistory);
+        const float a0 = fmaxf(alphaMin, 1.0f / N0);
+        const float alpha = a0 + g * (1.0f - a0);
+        o.N = fminf(N0, 1.0f / alpha);
+        o.r = h.r + alpha * (cr - h.r); o.g = h.g + alpha * (cg - h.g); o.b = h.b + alpha * (cb - h.b);
+        o.m1 = h.m1 + alpha * (l - h.m1);
+        o.m2 = h.m2 + alpha * (l2 - h.m2);
+    } else if (sb > 0.0f) {
+        h.r = h.r / sb; h.g = h.g / sb; h.b = h.b / sb; h.n = h.n / sb; h.m1 = h.m1 / sb; h.m2 = h.m2 / sb;
+        o.N = fminf(h.n + 1.0f, maxHistory);
+        const float alpha = fmaxf(alphaMin, 1.0f / o.N);
+        o.r = h.r + alpha * (cr - h.r); o.g = h.g + alpha * (cg - h.g); o.b = h.b + alpha * (cb - h.b);
+        o.m1 = h.m1 + alpha * (l - h.m1);
+        o.m2 = h.m2 + alpha * (l2 - h.m2);
+    }
+    return o;
+}
+
+template <bool MOTION, bool ADAPTIVE>
 static __global__ __launch_bounds__(256) void k_tp_accumulate_split(TemporalSplitCall T)
 {
     const int W = T.W, H = T.H;
@@ -141,8 +174,16 @@ static __global__ __launch_bounds__(256) void k_tp_accumulate_split(TemporalSpli
             }
         }
     }
-    const TpBlend D = tp_blend(hd, sb, dr, dg, db, T.maxHistory[0], T.alphaMin[0]);
-    const TpBlend I = tp_blend(hi, sb, ir, ig, ib, T.maxHistory[1], T.alphaMin[1]);
+    TpBlend D, I;
+    if constexpr (ADAPTIVE) {
+        float gd = 0.0f, gi = 0.0f;        // each component's change, read only where a history was fetched
+        if (sb > 0.0f) { gd = T.change[0][p]; gi = T.change[1][p]; }
+        D = tp_blend_adaptive(hd, sb, dr, dg, db, gd, T.maxHistory[0], T.alphaMin[0]);
+        I = tp_blend_adaptive(hi, sb, ir, ig, ib, gi, T.maxHistory[1], T.alphaMin[1]);
+    } else {
+        D = tp_blend(hd, sb, dr, dg, db, T.maxHistory[0], T.alphaMin[0]);
+        I = tp_blend(hi, sb, ir, ig, ib, T.maxHistory[1], T.alphaMin[1]);
+    }
     float4* ho = T.histOut + p * FRAY_TPS_ROWS;
     ho[0] = make_float4(D.r, D.g, D.b, D.N);
     ho[1] = make_float4(Px, Py, Pz, D.m1);
@@ -232,18 +273,22 @@ struct SplitArgs {
     const frayhip_view* view;
     const struct frayhip_temporal *pD, *pI;
     float *histOut, *signalD, *signalI, *varD, *varI;
+    const float *chgD = nullptr, *chgI = nullptr;       // the _adaptive entries' change frames
 };
 
 bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof a) == 0; }
 
-// Every check of both entries, in frayhip_temporal_accumulate's order; none touches the device.
-int check(const char* who, int W, int H, const SplitArgs& A, bool device)
+// Every check of the entries, in frayhip_temporal_accumulate's order; none touches the device.  adaptive: the _adaptive entries, whose change
+// frames are inputs like feat.
+int check(const char* who, int W, int H, const SplitArgs& A, bool device, bool adaptive = false)
 {
     if (W < 1 || H < 1) return bad(who, "width and height must be >= 1");
     if ((long long)W * H > (1ll << 30)) return bad(who, "more than 2^30 pixels");
     if (!A.rgbD) return bad(who, "null rgb_direct");
     if (!A.rgbI) return bad(who, "null rgb_indirect");
     if (!A.feat) return bad(who, "null feat");
+    if (adaptive && !A.chgD) return bad(who, "null change_direct");
+    if (adaptive && !A.chgI) return bad(who, "null change_indirect");
     if (!A.pD) return bad(who, "null p_direct");
     if (!A.pI) return bad(who, "null p_indirect");
     if (!A.histOut) return bad(who, "null hist_out");
@@ -254,7 +299,7 @@ int check(const char* who, int W, int H, const SplitArgs& A, bool device)
     if (!A.histIn != !A.view) return bad(who, "hist_in and prev_view must both be given or both be null");
     if (device) {
         for (const void* q : {(const void*)A.rgbD, (const void*)A.rgbI, (const void*)A.feat, (const void*)A.signalD, (const void*)A.signalI, (const void*)A.varD,
-                              (const void*)A.varI})
+                              (const void*)A.varI, (const void*)A.chgD, (const void*)A.chgI})
             if (misaligned(q, 4)) return bad(who, "device pointer to floats not 4-byte aligned");
         if (misaligned(A.histIn, 16) || misaligned(A.histOut, 16)) return bad(who, "device pointer to a history not 16-byte aligned");
         if (misaligned(A.motion, 16)) return bad(who, "device pointer to a motion frame not 16-byte aligned");
@@ -268,8 +313,9 @@ int check(const char* who, int W, int H, const SplitArgs& A, bool device)
     if (!same_bits(A.pD->plane_tolerance, A.pI->plane_tolerance)) return bad(who, "p_direct and p_indirect differ in plane_tolerance");
     if (!same_bits(A.pD->normal_min_dot, A.pI->normal_min_dot)) return bad(who, "p_direct and p_indirect differ in normal_min_dot");
     const size_t n = (size_t)W * H;
-    const struct { const void* q; size_t bytes; } ins[5] = {{A.rgbD, 12 * n}, {A.rgbI, 12 * n}, {A.feat, 4 * FRAYHIP_FEAT_CHANNELS * n},
-                                                            {A.histIn, 4 * FRAYHIP_HISTORY_SPLIT_CHANNELS * n}, {A.motion, 4 * FRAYHIP_MOTION_CHANNELS * n}};
+    const struct { const void* q; size_t bytes; } ins[7] = {{A.rgbD, 12 * n}, {A.rgbI, 12 * n}, {A.feat, 4 * FRAYHIP_FEAT_CHANNELS * n},
+                                                            {A.histIn, 4 * FRAYHIP_HISTORY_SPLIT_CHANNELS * n}, {A.motion, 4 * FRAYHIP_MOTION_CHANNELS * n},
+                                                            {A.chgD, 4 * n}, {A.chgI, 4 * n}};
     const struct { const void* q; size_t bytes; const char* name; } outs[5] = {{A.histOut, 4 * FRAYHIP_HISTORY_SPLIT_CHANNELS * n, "hist_out"},
                                                                                  {A.signalD, 12 * n, "signal_direct"}, {A.signalI, 12 * n, "signal_indirect"},
                                                                                  {A.varD, 4 * n, "variance_direct"}, {A.varI, 4 * n, "variance_indirect"}};
@@ -282,7 +328,7 @@ int check(const char* who, int W, int H, const SplitArgs& A, bool device)
     return FRAYHIP_OK;
 }
 
-// The device path of both entries (device pointers, checked)
+// The device path of the entries (device pointers, checked); with change frames the <MOTION, true> kernels
 int run(int W, int H, const SplitArgs& A, hipStream_t stream, frayhip_stats* st, std::chrono::steady_clock::time_point t0)
 {
     const size_t n = (size_t)W * H;
@@ -291,6 +337,7 @@ int run(int W, int H, const SplitArgs& A, hipStream_t stream, frayhip_stats* st,
     T.rgb[0] = A.rgbD; T.rgb[1] = A.rgbI; T.feat = A.feat; T.motion = (const float4*)A.motion;
     T.histIn = (const float4*)A.histIn; T.histOut = (float4*)A.histOut;
     T.signal[0] = A.signalD; T.signal[1] = A.signalI; T.variance[0] = A.varD; T.variance[1] = A.varI;
+    T.change[0] = A.chgD; T.change[1] = A.chgI;
     if (A.view) T.view = *A.view;
     T.demodulate = A.pD->demodulate;
     T.varianceHistory[0] = A.pD->variance_history; T.varianceHistory[1] = A.pI->variance_history;
@@ -303,8 +350,10 @@ int run(int W, int H, const SplitArgs& A, hipStream_t stream, frayhip_stats* st,
     struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{stream};
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     HIP_TRY(hipEventRecord(E.a, stream));
-    if (A.motion) hipLaunchKernelGGL(k_tp_accumulate_split<true>, grid, block, 0, stream, T);
-    else hipLaunchKernelGGL(k_tp_accumulate_split<false>, grid, block, 0, stream, T);
+    if (A.chgD && A.motion) hipLaunchKernelGGL((k_tp_accumulate_split<true, true>), grid, block, 0, stream, T);
+    else if (A.chgD) hipLaunchKernelGGL((k_tp_accumulate_split<false, true>), grid, block, 0, stream, T);
+    else if (A.motion) hipLaunchKernelGGL((k_tp_accumulate_split<true, false>), grid, block, 0, stream, T);
+    else hipLaunchKernelGGL((k_tp_accumulate_split<false, false>), grid, block, 0, stream, T);
     HIP_TRY(hipGetLastError());
     if (A.pD->variance_history > 1 || A.pI->variance_history > 1) {     // N >= 1 always: a component with variance_history 1 never takes the window
         hipLaunchKernelGGL(k_tp_variance_split, dim3((unsigned)((W + 15) / 16) * (unsigned)((H + 15) / 16)), block, 0, stream, T);
@@ -321,6 +370,53 @@ int run(int W, int H, const SplitArgs& A, hipStream_t stream, frayhip_stats* st,
         o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         *st = o;
     }
+    return FRAYHIP_OK;
+}
+
+// The host path of the entries (host pointers): checked, staged in one allocation, run on the null stream, copied back
+int run_host(const char* who, int width, int height, const SplitArgs& A, bool adaptive, frayhip_stats* st, std::chrono::steady_clock::time_point t0)
+{
+    if (const int rc = check(who, width, height, A, false, adaptive)) return rc;
+    const size_t n = (size_t)width * height;
+    const size_t HC = FRAYHIP_HISTORY_SPLIT_CHANNELS, MC = FRAYHIP_MOTION_CHANNELS, FC = FRAYHIP_FEAT_CHANNELS;
+    // one allocation, the 16-byte rows first: hist_out, hist_in and motion when given, then both rgb, feat, both change frames when given, both
+    // signals, both variances
+    DeviceArrays B(std::string(who) + ": out of device memory");
+    float* d_hout;
+    if (const int rc = B.alloc(d_hout, n * (HC + (A.histIn ? HC : 0) + (A.motion ? MC : 0) + 6 + FC + (adaptive ? 2 : 0) + 6 + 2))) return rc;
+    float* q = d_hout + HC * n;
+    float* d_hin = nullptr;
+    float* d_motion = nullptr;
+    if (A.histIn) { d_hin = q; q += HC * n; }
+    if (A.motion) { d_motion = q; q += MC * n; }
+    float* d_rgbD = q;
+    float* d_rgbI = d_rgbD + 3 * n;
+    float* d_feat = d_rgbI + 3 * n;
+    q = d_feat + FC * n;
+    float* d_chgD = nullptr;
+    float* d_chgI = nullptr;
+    if (adaptive) { d_chgD = q; d_chgI = q + n; q += 2 * n; }
+    float* d_sigD = q;
+    float* d_sigI = d_sigD + 3 * n;
+    float* d_varD = d_sigI + 3 * n;
+    float* d_varI = d_varD + n;
+    HIP_TRY(hipMemcpy(d_rgbD, A.rgbD, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_rgbI, A.rgbI, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_feat, A.feat, n * 4 * FC, hipMemcpyHostToDevice));
+    if (adaptive) {
+        HIP_TRY(hipMemcpy(d_chgD, A.chgD, n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_chgI, A.chgI, n * 4, hipMemcpyHostToDevice));
+    }
+    if (d_motion) HIP_TRY(hipMemcpy(d_motion, A.motion, n * 4 * MC, hipMemcpyHostToDevice));
+    if (d_hin) HIP_TRY(hipMemcpy(d_hin, A.histIn, n * 4 * HC, hipMemcpyHostToDevice));
+    const SplitArgs D{d_rgbD, d_rgbI, d_feat, d_motion, d_hin, A.view, A.pD, A.pI, d_hout, d_sigD, d_sigI, d_varD, d_varI, d_chgD, d_chgI};
+    if (const int rc = run(width, height, D, nullptr, st, t0)) return rc;
+    HIP_TRY(hipMemcpy(A.histOut, d_hout, n * 4 * HC, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(A.signalD, d_sigD, n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(A.signalI, d_sigI, n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(A.varD, d_varD, n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(A.varI, d_varI, n * 4, hipMemcpyDeviceToHost));
+    if (st) st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return FRAYHIP_OK;
 }
 
@@ -346,42 +442,35 @@ int frayhip_temporal_accumulate_split(int width, int height, const float* rgb_di
                                       float* variance_direct, float* variance_indirect, frayhip_stats* st)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    const char* who = "frayhip_temporal_accumulate_split";
     const SplitArgs A{rgb_direct, rgb_indirect, feat, motion, hist_in, prev_view, p_direct, p_indirect,
                       hist_out, signal_direct, signal_indirect, variance_direct, variance_indirect};
-    if (const int rc = check(who, width, height, A, false)) return rc;
-    const size_t n = (size_t)width * height;
-    const size_t HC = FRAYHIP_HISTORY_SPLIT_CHANNELS, MC = FRAYHIP_MOTION_CHANNELS, FC = FRAYHIP_FEAT_CHANNELS;
-    // one allocation, the 16-byte rows first: hist_out, hist_in and motion when given, then both rgb, feat, both signals, both variances
-    DeviceArrays B(std::string(who) + ": out of device memory");
-    float* d_hout;
-    if (const int rc = B.alloc(d_hout, n * (HC + (hist_in ? HC : 0) + (motion ? MC : 0) + 6 + FC + 6 + 2))) return rc;
-    float* q = d_hout + HC * n;
-    float* d_hin = nullptr;
-    float* d_motion = nullptr;
-    if (hist_in) { d_hin = q; q += HC * n; }
-    if (motion) { d_motion = q; q += MC * n; }
-    float* d_rgbD = q;
-    float* d_rgbI = d_rgbD + 3 * n;
-    float* d_feat = d_rgbI + 3 * n;
-    float* d_sigD = d_feat + FC * n;
-    float* d_sigI = d_sigD + 3 * n;
-    float* d_varD = d_sigI + 3 * n;
-    float* d_varI = d_varD + n;
-    HIP_TRY(hipMemcpy(d_rgbD, rgb_direct, n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_rgbI, rgb_indirect, n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_feat, feat, n * 4 * FC, hipMemcpyHostToDevice));
-    if (d_motion) HIP_TRY(hipMemcpy(d_motion, motion, n * 4 * MC, hipMemcpyHostToDevice));
-    if (d_hin) HIP_TRY(hipMemcpy(d_hin, hist_in, n * 4 * HC, hipMemcpyHostToDevice));
-    const SplitArgs D{d_rgbD, d_rgbI, d_feat, d_motion, d_hin, prev_view, p_direct, p_indirect, d_hout, d_sigD, d_sigI, d_varD, d_varI};
-    if (const int rc = run(width, height, D, nullptr, st, t0)) return rc;
-    HIP_TRY(hipMemcpy(hist_out, d_hout, n * 4 * HC, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(signal_direct, d_sigD, n * 12, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(signal_indirect, d_sigI, n * 12, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(variance_direct, d_varD, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(variance_indirect, d_varI, n * 4, hipMemcpyDeviceToHost));
-    if (st) st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return FRAYHIP_OK;
+    return run_host("frayhip_temporal_accumulate_split", width, height, A, false, st, t0);
+}
+
+int frayhip_temporal_accumulate_split_adaptive_device(int width, int height, const float* d_rgb_direct, const float* d_rgb_indirect, const float* d_feat,
+                                                      const float* d_motion, const float* d_change_direct, const float* d_change_indirect,
+                                                      const frayhip_view* prev_view, const float* d_hist_in, const struct frayhip_temporal* p_direct,
+                                                      const struct frayhip_temporal* p_indirect, float* d_hist_out, float* d_signal_direct,
+                                                      float* d_signal_indirect, float* d_variance_direct, float* d_variance_indirect, void* hip_stream,
+                                                      frayhip_stats* st)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const SplitArgs A{d_rgb_direct, d_rgb_indirect, d_feat, d_motion, d_hist_in, prev_view, p_direct, p_indirect,
+                      d_hist_out, d_signal_direct, d_signal_indirect, d_variance_direct, d_variance_indirect, d_change_direct, d_change_indirect};
+    if (const int rc = check("frayhip_temporal_accumulate_split_adaptive_device", width, height, A, true, true)) return rc;
+    return run(width, height, A, (hipStream_t)hip_stream, st, t0);
+}
+
+int frayhip_temporal_accumulate_split_adaptive(int width, int height, const float* rgb_direct, const float* rgb_indirect, const float* feat, const float* motion,
+                                               const float* change_direct, const float* change_indirect, const frayhip_view* prev_view, const float* hist_in,
+                                               const struct frayhip_temporal* p_direct, const struct frayhip_temporal* p_indirect, float* hist_out,
+                                               float* signal_direct, float* signal_indirect, float* variance_direct, float* variance_indirect,
+                                               frayhip_stats* st)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const SplitArgs A{rgb_direct, rgb_indirect, feat, motion, hist_in, prev_view, p_direct, p_indirect,
+                      hist_out, signal_direct, signal_indirect, variance_direct, variance_indirect, change_direct, change_indirect};
+    return run_host("frayhip_temporal_accumulate_split_adaptive", width, height, A, true, st, t0);
 }
 
 }  // extern "C"

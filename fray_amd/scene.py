@@ -413,16 +413,22 @@ def join_history_parts(hist_direct, hist_indirect):
 
 
 def temporal_accumulate_split(rgb_direct, rgb_indirect, feat, prev_view=None, hist_in=None, motion=None, direct=None, indirect=None, stats=False,
-                              stream=None, **shared):
+                              stream=None, change_direct=None, change_indirect=None, **shared):
     """temporal_accumulate for a frame's direct and indirect light in one call (frayhip_temporal_accumulate_split): rgb_direct and rgb_indirect
     [H, W, 3] (Scene.render_components), feat [H, W, 10], prev_view and hist_in [H, W, 20] (the previous call's split history) both None for the
     first frame, motion [H, W, 8] or None as temporal_accumulate takes it; float32, numpy arrays (host entry) or GPU torch tensors (device
     entry, on `stream`).  direct, indirect: dicts of temporal_params fields for that component; **shared is applied to both.  The components may
     differ in max_history, variance_history and alpha_min; demodulate, film_offset, plane_tolerance and normal_min_dot must agree (ValueError).
     Returns (hist_out [H, W, 20], signal_direct, signal_indirect, variance_direct, variance_indirect[, stats]); each component's outputs are
-    temporal_accumulate's for that component and its part of the history (split_history_parts), bit for bit."""
+    temporal_accumulate's for that component and its part of the history (split_history_parts), bit for bit.
+    change_direct, change_indirect: both None (exactly the call above), or one change frame [H, W] per component, of the inputs' kind
+    (change_frame; the same array may be passed for both): each component's history is shortened per pixel as temporal_accumulate(change=)
+    shortens it, in one call on the split history (frayhip_temporal_accumulate_split_adaptive), and each component's outputs are
+    temporal_accumulate(change=)'s for that component, bit for bit.  One of the two alone is a ValueError."""
     who = "temporal_accumulate_split"
     pd, pi = _split_params(who, direct, indirect, shared)
+    if (change_direct is None) != (change_indirect is None):
+        raise ValueError("%s: change_direct and change_indirect must both be given or both be None" % who)
     if (prev_view is None) != (hist_in is None):
         raise ValueError("%s: prev_view and hist_in must both be given or both be None" % who)
     if prev_view is not None and not isinstance(prev_view, abi.View):
@@ -432,21 +438,33 @@ def temporal_accumulate_split(rgb_direct, rgb_indirect, feat, prev_view=None, hi
         named.append(("hist_in", hist_in, abi.HISTORY_SPLIT_CHANNELS))
     if motion is not None:
         named.append(("motion", motion, abi.MOTION_CHANNELS))
+    if change_direct is not None:
+        named += [("change_direct", change_direct, 0), ("change_indirect", change_indirect, 0)]
     ins, (H, W), tensors = _frame_inputs(who, named)
     hin = ins[3] if hist_in is not None else None
+    chg_i, chg_d = (ins.pop(), ins.pop()) if change_direct is not None else (None, None)
     mot = ins[-1] if motion is not None else None
     view = C.byref(prev_view) if prev_view is not None else None
     st = abi.Stats()
     shapes = ((H, W, abi.HISTORY_SPLIT_CHANNELS), (H, W, 3), (H, W, 3), (H, W), (H, W))
     if not tensors:
         outs = tuple(np.empty(shape, np.float32) for shape in shapes)
-        _check(lib.frayhip_temporal_accumulate_split(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(mot), view, _ptr(hin), C.byref(pd), C.byref(pi),
-                                                     *[_ptr(o) for o in outs], C.byref(st)))
+        if chg_d is not None:
+            _check(lib.frayhip_temporal_accumulate_split_adaptive(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(mot), _ptr(chg_d), _ptr(chg_i), view,
+                                                                  _ptr(hin), C.byref(pd), C.byref(pi), *[_ptr(o) for o in outs], C.byref(st)))
+        else:
+            _check(lib.frayhip_temporal_accumulate_split(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(mot), view, _ptr(hin), C.byref(pd),
+                                                         C.byref(pi), *[_ptr(o) for o in outs], C.byref(st)))
     else:
         with _DeviceCall(ins[0].device, stream) as call:
             outs = tuple(call.torch.empty(shape, dtype=call.torch.float32, device=ins[0].device) for shape in shapes)
-            _check(lib.frayhip_temporal_accumulate_split_device(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(mot), view, _ptr(hin), C.byref(pd),
-                                                                C.byref(pi), *[_ptr(o) for o in outs], call.handle, C.byref(st)))
+            if chg_d is not None:
+                _check(lib.frayhip_temporal_accumulate_split_adaptive_device(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(mot), _ptr(chg_d), _ptr(chg_i),
+                                                                             view, _ptr(hin), C.byref(pd), C.byref(pi), *[_ptr(o) for o in outs], call.handle,
+                                                                             C.byref(st)))
+            else:
+                _check(lib.frayhip_temporal_accumulate_split_device(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(mot), view, _ptr(hin), C.byref(pd),
+                                                                    C.byref(pi), *[_ptr(o) for o in outs], call.handle, C.byref(st)))
     return outs + ((st.as_dict(),) if stats else ())
 
 
@@ -1165,12 +1183,12 @@ class Scene:
         edit(k, scene), samples [0, n) of this frame's view and seed are rendered into a fresh device state (the probe: render_samples, or
         render_components with split) while the scene is still in frame k - 1's state; after the edit and the feature / motion pass the frame
         itself is rendered as those n samples into a fresh state, the state is cloned, and the remaining spp - n samples follow, so raw is still
-        render(seed + k) bit for bit (resumable frames) and the frame costs n / spp more rays (info["render"] and, with split, info["temporal"] then
-        hold the sums of their two calls' figures).  change_frame(probe, clone, motion) then gives the
+        render(seed + k) bit for bit (resumable frames) and the frame costs n / spp more rays (info["render"] then holds the sum of its two
+        calls' figures).  change_frame(probe, clone, motion) then gives the
         change frame, and the accumulation takes it (temporal_accumulate(change=)).  A pixel none of whose n paths met anything the edit changed
         has change 0 where its whole window has, and is accumulated exactly as without change_samples.  With split there is one change frame
-        per component, from that component's pair of states, and the accumulation of frames k >= 1 is UNFUSED: two temporal_accumulate(change=)
-        calls on split_history_parts(history), joined by join_history_parts (there is no adaptive form of the split kernel).  info then also
+        per component, from that component's pair of states, and frames k >= 1 make one temporal_accumulate_split(change_direct=,
+        change_indirect=) on the 20-channel history, whose outputs are those two temporal_accumulate(change=) calls' bit for bit.  info then also
         holds "change" (or "change_direct" and "change_indirect") and the "probe" stats dict; they are None in frame 0.
         change: a dict of change_frame's radius and gain (needs change_samples > 0).  radius 3 and gain 1 are a choice, not a measurement."""
         self._need_dev()
@@ -1257,15 +1275,11 @@ class Scene:
                             rst = _sum_stats(rst, rst2)
                         chg_d = change_frame(probe[0], first[0], motion, stream=stream, **cparams)
                         chg_i = change_frame(probe[1], first[1], motion, stream=stream, **cparams)
-                        hd, hi = split_history_parts(hist)
-                        hd, sig_d, var_d, tst_d = temporal_accumulate(d_rgb, feat, view, hd, stats=True, stream=stream, motion=motion, change=chg_d, **tdirect)
-                        hi, sig_i, var_i, tst_i = temporal_accumulate(i_rgb, feat, view, hi, stats=True, stream=stream, motion=motion, change=chg_i, **tindirect)
-                        hist = join_history_parts(hd, hi)
-                        tst = _sum_stats(tst_d, tst_i)
                     else:
                         d_rgb, i_rgb, _state, rst = self.render_components(spp, state, seed=fr.seed, stats=True, stream=stream)
-                        hist, sig_d, sig_i, var_d, var_i, tst = temporal_accumulate_split(d_rgb, i_rgb, feat, view, hist, motion=motion, direct=tdirect,
-                                                                                          indirect=tindirect, stats=True, stream=stream)
+                    hist, sig_d, sig_i, var_d, var_i, tst = temporal_accumulate_split(d_rgb, i_rgb, feat, view, hist, motion=motion, direct=tdirect,
+                                                                                      indirect=tindirect, stats=True, stream=stream, change_direct=chg_d,
+                                                                                      change_indirect=chg_i)
                     d_out, dst = denoise_signal(sig_d, var_d, feat, stats=True, stream=stream, **denoise_params)
                     i_out, ist = denoise_signal(sig_i, var_i, feat, stats=True, stream=stream, **denoise_params)
                     view = view_from_camera(self.desc.camera, W, H)

@@ -964,13 +964,42 @@ int  frayhip_temporal_accumulate_adaptive_device(int width, int height, const fl
                                                  const float* d_change, const frayhip_view* prev_view, const float* d_hist_in,
                                                  const struct frayhip_temporal* p, float* d_hist_out, float* d_signal, float* d_variance,
                                                  void* hip_stream, frayhip_stats* st);
+/* The same for a split history: frayhip_temporal_accumulate_split with one change frame per component (W*H floats each; 0 direct, 1 indirect),
+ * in one call on the 20-channel history.  motion may be NULL; both change frames are required.  Inputs may alias each other: one change frame
+ * passed for both components is legal.
+ *
+ * The contract.  For every pixel the call produces two groups of outputs, each equal BIT FOR BIT to a call of
+ * frayhip_temporal_accumulate_adaptive (whose motion rule is this entry's):
+ *   direct    rows 0-2 of hist_out, signal_direct and variance_direct are what it returns for rgb_direct, p_direct, change_direct and rows 0-2
+ *             of hist_in;
+ *   indirect  {row 3}, {P, m1_I}, {n, m2_I} of hist_out, signal_indirect and variance_indirect are what it returns for rgb_indirect,
+ *             p_indirect, change_indirect and the same three rows of hist_in.
+ * Each component takes one of the three cases above by its own change, so the two may take different cases in one pixel; a change is read only
+ * where a history was fetched (sum(b) > 0, which the components share).  Two consequences: two change frames of +0 give every output bit of
+ * frayhip_temporal_accumulate_split, and two change frames of 1 give the hist_in = NULL call.
+ * Kernels: k_tp_accumulate_split<MOTION, true> (the projection, the footprint, the surface tests and the tap reads once, as in the split
+ *   entry; only the blend is per-component adaptive), then k_tp_variance_split unchanged and under the same condition: a pixel whose N the
+ *   change dropped below its component's variance_history takes the window again.  The split entry keeps its instantiations.  No work
+ *   buffers.  Device pointers, the stream contract and *st as the split entry's (the change frames 4-byte aligned).
+ * FRAYHIP_E_ARG, before the device is touched: the split entry's list, and a NULL or misaligned change frame or one that an output overlaps. */
+int  frayhip_temporal_accumulate_split_adaptive(int width, int height, const float* rgb_direct, const float* rgb_indirect, const float* feat,
+                                                const float* motion, const float* change_direct, const float* change_indirect,
+                                                const frayhip_view* prev_view, const float* hist_in, const struct frayhip_temporal* p_direct,
+                                                const struct frayhip_temporal* p_indirect, float* hist_out, float* signal_direct,
+                                                float* signal_indirect, float* variance_direct, float* variance_indirect, frayhip_stats* st);
+int  frayhip_temporal_accumulate_split_adaptive_device(int width, int height, const float* d_rgb_direct, const float* d_rgb_indirect,
+                                                       const float* d_feat, const float* d_motion, const float* d_change_direct,
+                                                       const float* d_change_indirect, const frayhip_view* prev_view, const float* d_hist_in,
+                                                       const struct frayhip_temporal* p_direct, const struct frayhip_temporal* p_indirect,
+                                                       float* d_hist_out, float* d_signal_direct, float* d_signal_indirect,
+                                                       float* d_variance_direct, float* d_variance_indirect, void* hip_stream,
+                                                       frayhip_stats* st);
 /* Not covered: SVGF's wider 3 x 3 retry when no bilinear tap counts, feeding a filtered level back into the history, moved lights and the
  * shadows and reflections of moved objects (only a pixel's own first hit is carried back: frayhip_render_features_motion), motion blur,
  * specular motion vectors (what a mirror shows moves with the camera while its first hit does not), learned
  * denoisers, adaptive and stereo frames, and denoising across ranks (gather the frame and its features first: frayhip_gather_buckets takes a
  * channel count).  With a change frame the accumulation does shorten the history under a moved light and under the shadows and reflections of
- * moved objects (the history is dropped or faded there, not carried to where the shadow went).  Still not covered with it: a fused adaptive
- * form of the split entry, a moved node's own pixels entering changed light (their difference is masked: they are the motion frame's
+ * moved objects (the history is dropped or faded there, not carried to where the shadow went).  Still not covered with it: a moved node's own pixels entering changed light (their difference is masked: they are the motion frame's
  * business), view-dependent change under camera motion, and any tuning beyond gain. */
 
 /* Multi-GPU tile exchange helpers.  pack: gathers this rank's buckets from a

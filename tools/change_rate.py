@@ -19,8 +19,17 @@
    pixels.  mae_changed is the same error over a mask that has no noise in it: the static pixels whose DIRECT state of samples [0, 2) differs
    in any bit between the scene before and after some frame's move (the union over the frames of a split run's change_direct > 0 at radius 0)
    -- the pixels the block's shadow left or reached.
+3. --split: frayhip_temporal_accumulate_split_adaptive_device against what it replaces, 1920x1080, cornell_box at 4 spp as components, the
+   tall block moved by tests/scene_edits.py's cornell-block edit between frame 0 and frame 1, through the motion frame, onto a split history
+   four frames deep, with the sequence's parameters (direct max_history 8).  Two rows: "sparse" passes the direct component's change frame
+   for both components (zero on most pixels), "block" each component's own.  Per row, ALTERNATING in one loop of one process: (a) ms_kernels
+   of the fused device call and of the two adaptive device calls on the history's parts (their sum); (b) the wall time, device synchronised
+   before and after, of the step Scene.render_sequence(split=True, change_samples=n) runs per frame -- one
+   temporal_accumulate_split(change_direct=, change_indirect=) -- and of the step it ran before: split_history_parts, two
+   temporal_accumulate(change=), join_history_parts.  bit_equal: the two steps' five outputs hold the same bits.
 
     python tools/change_rate.py [--rounds 21] [--warmup 3] [--plain-only] [--out FILE]
+    python tools/change_rate.py --split [--rounds 21] [--warmup 3] [--out FILE]
     python tools/change_rate.py --sequence [--frames 6] [--repeats 5] [--size W H] [--spp N] [--out FILE]"""
 import argparse
 import json
@@ -33,6 +42,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = 1920, 1080
 NODE, STEP = 5, (8.0, 0.0, -4.0)
 PROBE = 2
+BLOCK_NODE, BLOCK_STEP = 6, (30.0, 0.0, 5.0)          # tests/scene_edits.py's cornell-block: the tall block, reset and translated
 
 
 def timing(a, fray_amd, abi, open_scene):
@@ -138,6 +148,117 @@ def timing(a, fray_amd, abi, open_scene):
     return res
 
 
+def split_timing(a, fray_amd, abi, open_scene):
+    import ctypes as C
+    import torch
+    L = fray_amd.lib
+    stream = torch.cuda.Stream()
+    h = stream.cuda_stream
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device="cuda")
+    s = open_scene(fray_amd, "cornell_box.fray", W, H, wantAA=0, numPaths=4)
+    s.beginRender()
+    view = fray_amd.view_from_camera(s.camera, W, H)
+    pair_of = lambda seed: tuple(fray_amd.Accumulation.empty((W, H), seed, device="cuda") for _ in range(2))
+    with torch.cuda.stream(stream):
+        # frame 0, then frame 1 as render_sequence(split=True, change_samples=PROBE) renders it around the cornell-block edit
+        prev = s.node_transforms()
+        feat0, motion0 = new(H, W, 10), new(H, W, 8)
+        fr = abi.Frame(mode=abi.MODE_RENDER, seed=42)
+        assert L.frayhip_render_features_motion_device(s._dev, C.byref(fr), 4, prev, len(prev), feat0.data_ptr(), motion0.data_ptr(), h, None) == 0
+        d0, i0, _ = s.render_components(4, pair_of(42), seed=42, stream=stream)
+        probe = pair_of(43)
+        s.render_components(PROBE, probe, seed=43, stream=stream)
+        fray_amd.Transform().translate(*BLOCK_STEP).store(s.nodes[BLOCK_NODE])
+        s.update()
+        feat, motion = new(H, W, 10), new(H, W, 8)
+        fr = abi.Frame(mode=abi.MODE_RENDER, seed=43)
+        assert L.frayhip_render_features_motion_device(s._dev, C.byref(fr), 4, prev, len(prev), feat.data_ptr(), motion.data_ptr(), h, None) == 0
+        state = pair_of(43)
+        s.render_components(PROBE, state, seed=43, stream=stream)
+        first = [x.state.clone() for x in state]
+        d1, i1, _ = s.render_components(4 - PROBE, state, seed=43, stream=stream)
+        chg_d = fray_amd.change_frame(probe[0], first[0], motion, stream=stream)
+        chg_i = fray_amd.change_frame(probe[1], first[1], motion, stream=stream)
+    s.close()
+    tdirect, tindirect = dict(max_history=8), dict()                      # render_sequence's defaults
+    pd, pi = fray_amd.temporal_params(**tdirect), fray_amd.temporal_params(**tindirect)
+    with torch.cuda.stream(stream):
+        out = dict(hs=new(H, W, 20), hd=new(H, W, 12), hi=new(H, W, 12), sd=new(H, W, 3), si=new(H, W, 3), vd=new(H, W), vi=new(H, W))
+        # the steady-state history: frame 0 accumulated onto itself under the still camera, four frames deep
+        hs = [new(H, W, 20), new(H, W, 20)]
+        for k in range(4):
+            rc = L.frayhip_temporal_accumulate_split_device(W, H, d0.data_ptr(), i0.data_ptr(), feat0.data_ptr(), motion0.data_ptr(),
+                                                            C.byref(view) if k else None, hs[(k + 1) % 2].data_ptr() if k else None, C.byref(pd), C.byref(pi),
+                                                            hs[k % 2].data_ptr(), out["sd"].data_ptr(), out["si"].data_ptr(), out["vd"].data_ptr(),
+                                                            out["vi"].data_ptr(), h, None)
+            assert rc == 0, L.frayhip_last_error()
+        steady = hs[1]
+        parts = fray_amd.split_history_parts(steady)
+
+    def fused_kernels(cd, ci):
+        st = abi.Stats()
+        rc = L.frayhip_temporal_accumulate_split_adaptive_device(W, H, d1.data_ptr(), i1.data_ptr(), feat.data_ptr(), motion.data_ptr(), cd.data_ptr(),
+                                                                 ci.data_ptr(), C.byref(view), steady.data_ptr(), C.byref(pd), C.byref(pi), out["hs"].data_ptr(),
+                                                                 out["sd"].data_ptr(), out["si"].data_ptr(), out["vd"].data_ptr(), out["vi"].data_ptr(), h,
+                                                                 C.byref(st))
+        assert rc == 0, L.frayhip_last_error()
+        return st.ms_kernels
+
+    def pair_kernels(cd, ci):
+        ms = 0.0
+        for rgb, c, hin, hout, sig, var, p in ((d1, cd, parts[0], out["hd"], out["sd"], out["vd"], pd), (i1, ci, parts[1], out["hi"], out["si"], out["vi"], pi)):
+            st = abi.Stats()
+            rc = L.frayhip_temporal_accumulate_adaptive_device(W, H, rgb.data_ptr(), feat.data_ptr(), motion.data_ptr(), c.data_ptr(), C.byref(view),
+                                                               hin.data_ptr(), C.byref(p), hout.data_ptr(), sig.data_ptr(), var.data_ptr(), h, C.byref(st))
+            assert rc == 0, L.frayhip_last_error()
+            ms += st.ms_kernels
+        return ms
+
+    def fused_step(cd, ci):                                               # what render_sequence runs per frame with a probe
+        return fray_amd.temporal_accumulate_split(d1, i1, feat, view, steady, motion=motion, direct=tdirect, indirect=tindirect, stats=True, stream=stream,
+                                                  change_direct=cd, change_indirect=ci)[:5]
+
+    def unfused_step(cd, ci):                                             # what it ran before: take-apart, two adaptive calls, join
+        hd, hi = fray_amd.split_history_parts(steady)
+        hd, sd, vd, _ = fray_amd.temporal_accumulate(d1, feat, view, hd, stats=True, stream=stream, motion=motion, change=cd, **tdirect)
+        hi, si, vi, _ = fray_amd.temporal_accumulate(i1, feat, view, hi, stats=True, stream=stream, motion=motion, change=ci, **tindirect)
+        return fray_amd.join_history_parts(hd, hi), sd, si, vd, vi
+
+    def wall(f, *args):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with torch.cuda.stream(stream):
+            r = f(*args)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, r
+
+    res = {"library": os.path.relpath(fray_amd.render_info()["library"], ROOT), "size": [W, H], "rounds": a.rounds, "warmup": a.warmup,
+           "node": BLOCK_NODE, "step": BLOCK_STEP, "change_samples": PROBE,
+           "changed_share_direct": float((chg_d > 0).float().mean()), "changed_share_indirect": float((chg_i > 0).float().mean()),
+           "steady_young_share_direct": float((steady[..., 3] < 4).float().mean()), "steady_young_share_indirect": float((steady[..., 15] < 4).float().mean())}
+    med = statistics.median
+    # "sparse": the direct component's change frame for both components (inputs may alias), zero on most pixels; "block": each component's own
+    for name, cd, ci in (("sparse", chg_d, chg_d), ("block", chg_d, chg_i)):
+        fk, pk, fw, uw = [], [], [], []
+        row = {"changed_share": [float((cd > 0).float().mean()), float((ci > 0).float().mean())]}
+        for r in range(a.warmup + a.rounds):
+            x = fused_kernels(cd, ci)
+            y = pair_kernels(cd, ci)
+            tf, got = wall(fused_step, cd, ci)
+            tu, want = wall(unfused_step, cd, ci)
+            if r == 0:
+                row["bit_equal"] = all(torch.equal(g.view(torch.int32), w.view(torch.int32)) for g, w in zip(got, want))
+                row["young_share"] = [float((got[0][..., 3] < 4).float().mean()), float((got[0][..., 15] < 4).float().mean())]
+            if r >= a.warmup:
+                fk.append(x); pk.append(y); fw.append(tf); uw.append(tu)
+        row.update(fused_kernels_ms=med(fk), fused_kernels_min_max=[min(fk), max(fk)], pair_kernels_ms=med(pk), pair_kernels_min_max=[min(pk), max(pk)],
+                   kernels_ratio=med(fk) / med(pk), fused_step_ms=med(fw), fused_step_min_max=[min(fw), max(fw)], unfused_step_ms=med(uw),
+                   unfused_step_min_max=[min(uw), max(uw)], step_ratio=med(fw) / med(uw))
+        res[name] = row
+        print(name, json.dumps(row), flush=True)
+    return res
+
+
 def sequence(a, fray_amd, abi, open_scene):
     import numpy as np
     import torch
@@ -220,6 +341,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--plain-only", action="store_true", help="timing: only the two existing entries (runs in a checkout without change frames)")
     ap.add_argument("--sequence", action="store_true")
+    ap.add_argument("--split", action="store_true", help="timing of the fused adaptive split entry against the unfused step it replaces")
     ap.add_argument("--frames", type=int, default=6)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--size", type=int, nargs=2, default=[320, 240], metavar=("W", "H"), help="--sequence: the frame's size")
@@ -237,7 +359,7 @@ def main():
     from fray_amd import abi
     from conftest import open_scene
     fray_amd.lib.frayhip_init(0)
-    res = (sequence if a.sequence else timing)(a, fray_amd, abi, open_scene)
+    res = (sequence if a.sequence else split_timing if a.split else timing)(a, fray_amd, abi, open_scene)
     line = json.dumps(res)
     print(line)
     if a.out:
