@@ -348,7 +348,7 @@ frayhip_stats finish_stats(frayhip_scene* sc, const DStats* blocks, int nBlocks,
 
 // What frayhip_scene_update needs of a scene after its description is gone (include/frayhip.h "scene edits").  Of the arena as built: the table
 // list, the facts, and a host copy of the tables arena_update writes or reads -- the editable tables, the DMesh table and the triangle records of the
-// meshes whose planes the segment-plane tables are made from (detail::arena_keeps_tris: tree-less, fewer than FRAY_GATE_MIN_TRIS triangles) -- packed back
+// meshes whose triangles the segment-plane tables and the tight gate records are made from (detail::arena_keeps_tris: tree-less, a few dozen triangles at most) -- packed back
 // to back: nothing whose size grows with a large mesh or with the texel pool.  Of the description: its fixed part, to compare an update's with.
 struct SceneEdit {
     frayhip_arena::ArenaFacts F;
@@ -637,6 +637,7 @@ int frayhip_scene_create(const frayhip_scene_desc* desc, frayhip_scene** out)
     if (const char* e = getenv("FRAYHIP_SKIP_NULL_SEGMENTS")) sc->skipNullSegments = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_SEGMENT_PLANES")) sc->segmentPlanes = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_CERTIFIED_SEGMENTS")) sc->certifiedSegments = atol(e) != 0;
+    if (const char* e = getenv("FRAYHIP_TIGHT_GATES")) sc->tightGates = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_FUSED_WHITTED_MAX")) { long v = atol(e); if (v >= 0 && v <= 1024) sc->fusedWhittedMax = (int)v; }
     if (const char* e = getenv("FRAYHIP_CSG_LANES")) { long v = atol(e); if (v >= 1 && v <= FRAY_PT_LANES) sc->csgLanes = (int)v; }
     if (const char* e = getenv("FRAYHIP_SEED_TABLE_MIB")) { long v = atol(e); if (v >= 0 && v <= (1 << 20)) sc->seedTableCapBytes = (size_t)v << 20; }
@@ -719,6 +720,17 @@ int frayhip_scene_set_option(frayhip_scene* s, const char* name, int64_t value)
         set_error("frayhip_scene_set_option: unknown option " + n);
         return FRAYHIP_E_ARG;
     }
+    return FRAYHIP_OK;
+}
+
+int frayhip_scene_tight_gates(frayhip_scene* s, int enable, int64_t* enabled, int64_t* eligible)
+{
+    if (!s) { set_error("frayhip_scene_tight_gates: null scene"); return FRAYHIP_E_ARG; }
+    if (enable < -1 || enable > 1) { set_error("frayhip_scene_tight_gates: enable must be -1, 0 or 1"); return FRAYHIP_E_ARG; }
+    if (enable >= 0 && s->rendering) { set_error("frayhip_scene_tight_gates: the scene is rendering a frame"); return FRAYHIP_E_ARG; }
+    if (enable >= 0) s->tightGates = enable != 0;
+    if (enabled) *enabled = s->tightGates ? 1 : 0;
+    if (eligible) *eligible = s->edit->F.nTightGates;
     return FRAYHIP_OK;
 }
 

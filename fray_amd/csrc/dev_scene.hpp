@@ -17,6 +17,7 @@
 #include "frayhip.h"      // FRAYHIP_BUCKET_SKEW: the bucket numbering is part of the C ABI
 #include "dev_tricert.hpp"  // DTri32
 #include "dev_segcert.hpp"  // DSegPlane
+#include "dev_gatecert.hpp" // DGateTight
 
 // Scene tables are read-only for the whole frame.  On the device their pointers are typed into the
 // constant address space (4): loads through them are known not to alias the kernels' stores, so a
@@ -174,7 +175,11 @@ struct DCamera {
 // exact: the gate's box is the geometry's own box in the space the reference tests it in (an untransformed node), and cf / hf / Mf are what
 // ray_surely_misses_box_f32 (dev_misscert.hpp) needs: FP32 centre, half extents widened by 1e-5 and by the centre's rounding, rounded up, and max (|cf| + hf).
 // When EVERY gate of a scene is exact (DScene::gatesExact) "gate-free" is a proof, not a hint, and the consumers skip the gated nodes for such rays.
-struct DGate { double lo[3], hi[3]; float cf[3], hf[3]; float Mf; int32_t exact; };
+// The table holds every gate TWICE, FRAY_MAX_GATES entries apart: first as above, then in its TIGHT form -- for an exact gate that stands for an eligible mesh
+// (dev_gatecert.hpp) cf / hf / Mf describe the box of the mesh's own triangles (an OBJ mesh's bounding box also holds the loader's dummy vertex (0, 0, 0)) and
+// guard / nDirs / nf the guard against rays nearly parallel to a face; for every other gate the second entry equals the first, where nDirs = 0.  The switch of
+// frayhip_scene_tight_gates chooses the half DScene::gates points to (render_impl.hpp), so the producers run one code on either.
+struct DGate { double lo[3], hi[3]; float cf[3], hf[3]; float Mf; int32_t exact; float guard; int32_t nDirs; float nf[FRAY_GATE_MAX_DIRS][3]; };      // 160 B
 
 struct DScene {
     const FRAY_RO DNode* nodes;

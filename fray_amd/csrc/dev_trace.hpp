@@ -45,6 +45,11 @@ constexpr bool kd_variant(int st) { return (st & 6) != 0; }
 constexpr bool tex_variant(int st) { return (st & 14) != 0; }
 // the variants whose node_intersect takes the shortcut for untransformed nodes (flag words 0 and 1)
 constexpr bool identity_variant(int st) { return FRAY_IDENTITY_SKIP && (st & 14) == 0; }
+// The variant whose producers evaluate the guards of tight gates (ray_gate_class<true>), and whose frames get the gate table's tight half (render_impl.hpp):
+// flag word 0 in the exact arithmetic.  Not the counting variant, which asks every node anyway and whose waves lose the wave-uniform exit of the root box test
+// when rays that pass a mesh's bounding box are filed gate-free (+14 % of its vector instructions); not the fp_contract copy, whose bounce kernel spills
+// nine more registers with the guards (the contracted frame: +3.7 ms of 64; profiles/tight_gates/README.md).  Every other variant's code is what it was.
+constexpr bool tight_variant(int st) { return FRAY_ARITH == 0 && (st & 15) == 0; }
 
 // Closest-hit record.  Shading attributes (ip, normal, uv, dNdx/dNdy) are re-derived from it for
 // the winning node only (finalize_hit in dev_shade.hpp) -- same arithmetic, so same bits.
@@ -1111,16 +1116,46 @@ FD uint32_t segment_skip_nodes(const DScene& S, V3 a, V3 b, bool live)
 // of the meshes with long brute-force triangle loops).  A slab test in FP32 on the world-space box -- a scheduling hint, nothing else.
 // Round 5: when every gate of the scene is EXACT (DGate::exact: untransformed nodes) the test is dev_misscert.hpp's FP32 certificate instead, "gate-free" is
 // then proven, and the consumers skip the gated nodes for the rays filed at the front (closest_hit / visible, `gateFree`).
+// With tight gates switched on (frayhip_scene_tight_gates) DScene::gates is the table's tight half: a gate that stands for an eligible mesh is tested by dev_gatecert.hpp's certificate -- no
+// triangle of the mesh accepts the ray -- on the box of the mesh's triangles instead: the same proof for the consumers, a smaller gate.
 // Returns 0 for a gate-free ray, else 1 + the index of the first gate it may enter.
 #ifdef __HIP__
 #define FRAY_RCPF(x) __builtin_amdgcn_rcpf(x)
 #else
 #define FRAY_RCPF(x) (1.0f / (x))          // the host harnesses (tests/native) compile this header as plain C++; the hint decides nothing there
 #endif
+// TIGHT: compiled with the guards of tight entries -- the leanest timed variant only (tight_variant: an eligible mesh is untransformed and has no KD-tree, and
+// render_impl hands the table's tight half to no other variant), so that every other variant's code is what it was.
+template <bool TIGHT = false>
 FD uint32_t ray_gate_class(const DScene& S, V3 o, V3 d)
 {
     const int ng = S.nGates;
     if (ng == 0) return 0u;
+    if constexpr (TIGHT) {
+        if (S.gatesExact) {
+            const float dx = (float)d.x, dy = (float)d.y, dz = (float)d.z;
+            const float dsum = fabsf(dx) + fabsf(dy) + fabsf(dz);
+            // A tight entry (frayhip_scene_tight_gates, dev_gatecert.hpp: the box of a mesh's own triangles) needs its guard besides the box part: the guards of all
+            // gates first, in a loop of their own over the direction alone -- ray_surely_misses_mesh_f32 in three steps.  A ray that fails some gate's guard,
+            // or the certificate's bounds on the ray, counts as one that may enter the first gate.
+            bool guarded = true, tight = false;
+            for (int g = 0; g < ng; g++) {
+                const FRAY_RO DGate& G = S.gates[g];
+                if (G.nDirs) { guarded = guarded & gate_guard_f32(G, dx, dy, dz, dsum); tight = true; }
+            }
+            FRAY_CERT_SEQ();          // (the guards before the start is converted: scheduled among the box tests they cost k_pt_bounce<0> ten more spilled registers)
+            const float ox = (float)o.x, oy = (float)o.y, oz = (float)o.z;
+            const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
+            uint32_t first = 0;
+            for (int g = ng - 1; g >= 0; g--) {
+                const FRAY_RO DGate& G = S.gates[g];
+                if (!ray_surely_misses_box_f32(G.cf[0], G.cf[1], G.cf[2], G.hf[0], G.hf[1], G.hf[2], G.Mf, ox, oy, oz, dx, dy, dz, omax, dsum)) first = (uint32_t)g + 1u;
+            }
+            if (tight) guarded = guarded & gate_ray_range(dsum, omax, ox + oy + oz);
+            if (!guarded && !first) first = 1u;
+            return !(omax < 1e9f) && !first ? 1u : first;
+        }
+    }
     const float ox = (float)o.x, oy = (float)o.y, oz = (float)o.z;
     if (S.gatesExact) {
         const float dx = (float)d.x, dy = (float)d.y, dz = (float)d.z;

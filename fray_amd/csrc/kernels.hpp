@@ -1148,7 +1148,7 @@ FD void path_shade(const DScene& S, PathStateT<G>& ps, const HitT<ST>& h, const 
                 // register allocator's choice, not the source's -- the other order spills two more VGPRs here and eight more there (profiles/certified_segments/README.md).
                 bool planesPass = false;
                 if constexpr (ST == 0 && FRAY_ARITH == 0) { if (S.certifiedSegments) planesPass = segment_certified(S, sa, sb); }
-                shadowBack = ray_gate_class(S, sa, sb - sa);
+                shadowBack = ray_gate_class<tight_variant(ST)>(S, sa, sb - sa);
                 if constexpr (ST == 0) {
                     if (FRAY_ARITH == 0 ? planesPass && shadowBack == 0 : segment_surely_visible(S, sa, sb, shadowBack)) {
                         own = sc;
@@ -1316,7 +1316,7 @@ static __global__ __launch_bounds__(256, waves_for(ST, kd_variant(ST) ? FRAY_BOU
         }
         // survivors and next-event segments of this batch of 64 paths go to the wave's own segments of the output queues: gate-free rays to
         // the front, the others to the back (ballot ranks, no global counter)
-        const uint32_t gate = cont ? ray_gate_class(S, ps.o, ps.d) : 0u;
+        const uint32_t gate = cont ? ray_gate_class<tight_variant(ST)>(S, ps.o, ps.d) : 0u;
         const bool back = gate != 0;
         const uint32_t slotOut = seg_slot(outEnds, cont, back);
 #ifdef FRAY_SORT_BY_MATERIAL

@@ -221,7 +221,10 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
     const int first = acc ? acc->first : 0;
     if (acc) F.spp = 0;
     const int spp = acc ? acc->count : F.spp, nItems = F.nBuckets * 2304;
-    const DScene S = frame_scene(sc);
+    DScene S0 = frame_scene(sc);
+    // tight gates (frayhip_scene_tight_gates): the tight half of the gate table (dev_scene.hpp DGate), for the variant compiled with its guards (dev_trace.hpp tight_variant)
+    if constexpr (tight_variant(ST)) { if (sc->tightGates) S0.gates += FRAY_MAX_GATES; }
+    const DScene S = S0;
     DCamera C = camera_begin_frame(sc->camera, W, H);
     Batches B;
     B.sc = sc; B.prog = prog; B.t0 = t0; B.F = F; B.nItems = nItems; B.d_rgb = d_rgb;
@@ -606,7 +609,11 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                         // measured slower with it)
                         bool contractedLaunch = false;
                         if constexpr (!(ST & 2)) {
-                            if (sc->fpContract && !longRng && b > 0) { launch_bounce_contracted<ST>(grid, ls, BA); contractedLaunch = true; nContracted++; }
+                            if (sc->fpContract && !longRng && b > 0) {
+                                BounceArgs BC = BA;
+                                BC.S.gates = sc->S.gates;          // the gate table's plain half: the contracted kernels are compiled without the guards of tight gates (dev_trace.hpp tight_variant)
+                                launch_bounce_contracted<ST>(grid, ls, BC); contractedLaunch = true; nContracted++;
+                            }
                         }
                         if (contractedLaunch) {}
                         else if (longRng) hipLaunchKernelGGL((k_pt_bounce<ST, true>), dim3(grid), dim3(256), 0, ls, BA);

@@ -81,6 +81,7 @@ struct frayhip_scene {
     bool skipNullSegments = true;     // option "skip_null_segments": the timed path-tracing kernels queue no next-event segment whose contribution is +0 in every channel (dev_shade.hpp nee_prepare)
     bool segmentPlanes = true;        // option "segment_planes": k_pt_shadow skips, per wave, the eligible nodes whose triangles' planes no live segment crosses (dev_segcert.hpp)
     bool certifiedSegments = true;    // option "certified_segments": path_shade stores the term of a next-event segment proven unoccluded itself instead of queueing it (dev_trace.hpp segment_certified; needs segmentPlanes and DScene::segCertAll)
+    bool tightGates = true;           // frayhip_scene_tight_gates: the producers test an eligible mesh's gate by its own triangles' box and a guard (dev_gatecert.hpp) instead of its reference box
     long long lastShadowCertified = 0;   // the last frame's next-event segments decided that way (frayhip_scene_get_option "shadow_segments_certified"); they are part of lastShadowSegments
     long long lastShadowNodesSkipped = 0;   // the last frame's sum over k_pt_shadow's wave iterations of the nodes skipped that way (frayhip_scene_get_option "shadow_nodes_skipped")
     long long lastShadowSegments = 0; // the last frame's next-event segments the timed kernels decided, shadow-queue entries over all its launches plus the certified ones (frayhip_scene_get_option "shadow_segments"; render_impl frames)

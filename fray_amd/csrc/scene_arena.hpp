@@ -32,6 +32,7 @@ struct ArenaMeshTables { int32_t tris, attrs, kd, kdBox, refs, ltris, ltris32; }
 struct ArenaFacts {
     int32_t extGeometry, kdMeshes, textured, whittedNeedsRecursion, lightDraws, lightSampleCount, specFanMax;
     int32_t nGates, gatesExact, nSegPlanes, nSegNodes, segCertAll;
+    int32_t nTightGates;                      // gates whose entry in the table's tight half differs: eligible meshes (dev_gatecert.hpp)
     int32_t nNodes, nLights, nMeshes, nTextures;
     int32_t envPresent, envLoaded, envWidth[6], envHeight[6];
     int64_t envTexelOffset[6];
@@ -97,9 +98,10 @@ inline bool shader_uses_uv(const frayhip_scene_desc& d, int s, int depth = 0)
 // segment planes, the primitives, shaders, layers, lights and texture records, and the scene facts that follow from them.  arena_build runs it on the
 // freshly laid out arena and arena_update on an arena built earlier, so an updated arena equals a fresh one byte for byte.  tab[t] is where table t
 // can be written.  Read besides `d`: the DMesh table (the header scalars of every mesh) and the DTri table of every mesh without a KD-tree and with
-// fewer than FRAY_GATE_MIN_TRIS triangles (arena_keeps_tris) -- never a mesh array or the texel pool of `d`.  Every inner pointer is written null
+// at most FRAY_GATECERT_MAX_TRIS triangles (arena_keeps_tris: the segment planes of the small ones, the tight gate records of the others) -- never a
+// mesh array or the texel pool of `d`.  Every inner pointer is written null
 // (arena_place); the unused tails of the gate and segment-plane tables are zeroed.  F: the t* indices and the counts are read, the editable facts written.
-inline bool arena_keeps_tris(const DMesh& M) { return !M.hasKd && M.nTris > 0 && M.nTris < FRAY_GATE_MIN_TRIS; }
+inline bool arena_keeps_tris(const DMesh& M) { return !M.hasKd && M.nTris > 0 && M.nTris <= FRAY_GATECERT_MAX_TRIS; }
 inline void fill_editable(const frayhip_scene_desc& d, const ArenaMeshTables* meshTables, ArenaFacts& F, unsigned char* const* tab)
 {
     const DMesh* const meshes = (const DMesh*)tab[F.tMeshes];
@@ -302,10 +304,10 @@ inline void fill_editable(const frayhip_scene_desc& d, const ArenaMeshTables* me
     if (!nodesX.empty()) memcpy(tab[F.tNodesX], nodesX.data(), nodesX.size() * sizeof(DNodeX));
     // gates: world-space boxes of the meshes whose brute-force triangle loops are worth skipping for a whole wave (dev_scene.hpp DGate):
     // the eight corners of the mesh's box through the node's transform (Transform::transformPoint, matrix.cpp:137-146), a hair wider
-    int nGates = 0;
+    int nGates = 0, nTight = 0;
     bool gatesExact = false;
     {
-        DGate gates[FRAY_MAX_GATES];
+        DGate gates[FRAY_MAX_GATES], tight[FRAY_MAX_GATES];
         int gateNode[FRAY_MAX_GATES];
         // ... and of the CsgOp nodes whose tree is bounded (their machine is the most expensive thing a ray can enter), unless the box is so large
         // against the others that nearly every ray enters it anyway (a floor slab): larger than 30 times the smallest such box in some extent
@@ -340,7 +342,25 @@ inline void fill_editable(const frayhip_scene_desc& d, const ArenaMeshTables* me
                 g.Mf = std::max(g.Mf, std::nextafterf(std::fabs(g.cf[k]) + g.hf[k], INFINITY));
             }
             if (!(g.Mf < 1e9f)) g.exact = 0;
+            g.guard = 0; g.nDirs = 0;
+            for (int j = 0; j < FRAY_GATE_MAX_DIRS; j++) g.nf[j][0] = g.nf[j][1] = g.nf[j][2] = 0;
             for (int k = 0; k < 3; k++) { const double e = 1e-6 * (1.0 + std::fabs(g.lo[k]) + std::fabs(g.hi[k])); g.lo[k] -= e; g.hi[k] += e; }
+            // ... and its entry in the table's tight half: for an exact gate that stands for a mesh whose every triangle is admissible (dev_gatecert.hpp) the box of
+            // the triangles themselves -- the reference's box above also holds the OBJ loader's dummy vertex (0, 0, 0) -- and the guard; else the same entry again
+            tight[nGates] = g;
+            if (g.exact && N.tlTris >= FRAY_GATE_MIN_TRIS && N.tlTris <= FRAY_GATECERT_MAX_TRIS) {
+                const DTri* const tris = (const DTri*)tab[meshTables[N.geomIndex].tris];
+                GateTri gt[FRAY_GATECERT_MAX_TRIS];
+                for (int t = 0; t < N.tlTris; t++) gt[t] = GateTri{tris[t].A, tris[t].AB, tris[t].AC, tris[t].N};
+                DGateTight T;
+                if (gatecert_make(T, gt, N.tlTris)) {
+                    DGate& o = tight[nGates];
+                    for (int k = 0; k < 3; k++) { o.cf[k] = T.cf[k]; o.hf[k] = T.hf[k]; }
+                    o.Mf = T.Mf; o.guard = T.guard; o.nDirs = T.nDirs;
+                    memcpy(o.nf, T.nf, sizeof o.nf);
+                    nTight++;
+                }
+            }
             gateNode[nGates] = i;
             gates[nGates++] = g;
         }
@@ -348,13 +368,14 @@ inline void fill_editable(const frayhip_scene_desc& d, const ArenaMeshTables* me
         for (int q = 0; q < nGates; q++) gatesExact = gatesExact && gates[q].exact;
         if (gatesExact)
             for (int q = 0; q < nGates; q++) nodes[gateNode[q]].gated = 1;
-        memset(tab[F.tGates], 0, FRAY_MAX_GATES * sizeof(DGate));
+        memset(tab[F.tGates], 0, 2 * FRAY_MAX_GATES * sizeof(DGate));
         if (nGates) memcpy(tab[F.tGates], gates, (size_t)nGates * sizeof(DGate));
+        if (nGates) memcpy(tab[F.tGates] + FRAY_MAX_GATES * sizeof(DGate), tight, (size_t)nGates * sizeof(DGate));
     }
     if (!nodes.empty()) memcpy(tab[F.tNodes], nodes.data(), nodes.size() * sizeof(DNode));
     if (!tex.empty()) memcpy(tab[F.tTex], tex.data(), tex.size() * sizeof(DTexture));
 
-    F.nGates = nGates; F.gatesExact = gatesExact ? 1 : 0;
+    F.nGates = nGates; F.gatesExact = gatesExact ? 1 : 0; F.nTightGates = nTight;
     F.nSegPlanes = nSegPlanes; F.nSegNodes = nSegNodes;
     // Certified segments (kernels.hpp path_shade, dev_trace.hpp segment_certified): EVERY node is one a next-event segment can be proven to pass -- by the planes
     // of its triangles (segNode) or by its exact gate (gated, which implies gatesExact).  Any other node (a sphere, a plane, a Cube / CSG node without a gate, a
@@ -416,7 +437,7 @@ inline void arena_build(const frayhip_scene_desc& d, ArenaBuilt& B)
     F.tNodes = A.last();
     A.reserve((size_t)d.n_nodes * sizeof(DNodeX));
     F.tNodesX = A.last();
-    A.reserve(FRAY_MAX_GATES * sizeof(DGate));                                // the path tracer's scheduling hint (DGate)
+    A.reserve(2 * FRAY_MAX_GATES * sizeof(DGate));                            // the path tracer's gates (DGate), as they are and in their tight form
     F.tGates = A.last();
     A.reserve(FRAY_SEG_MAX_PLANES * sizeof(DSegPlane));                       // the planes shadow segments are certified against (dev_segcert.hpp)
     F.tSegPlanes = A.last();

@@ -676,6 +676,14 @@ class Scene:
         _check(lib.frayhip_scene_set_option(self._dev, name.encode(), int(value)))
         return self
 
+    def tight_gates(self, enable=None):
+        """frayhip_scene_tight_gates: switches tight gates on or off (None leaves the switch alone) and returns (enabled, eligible gates): the path tracer
+        tests a gated mesh that is eligible by the box of its own triangles and a guard against rays nearly parallel to a face, not by its bounding box."""
+        self._need_dev()
+        on, n = C.c_int64(0), C.c_int64(0)
+        _check(lib.frayhip_scene_tight_gates(self._dev, -1 if enable is None else int(bool(enable)), C.byref(on), C.byref(n)))
+        return int(on.value), int(n.value)
+
     def get_option(self, name):
         """frayhip_scene_get_option: an option's value, or a figure of the last frame ("fans_filed", "fan_children", "fan_children_looked_up", "fans_given_up", "contracted_launches", "shadow_segments",
         "shadow_segments_certified", "certified_segments_eligible", "segment_plane_nodes", "shadow_nodes_skipped", "seed_table_bytes", "seed_launches", "seed_planes_reused", "batch_lanes")."""

@@ -387,6 +387,19 @@ int  frayhip_scene_set_option(frayhip_scene* s, const char* name, int64_t value)
  * device), "seed_launches" (k_seed launches of the last frame) and "seed_planes_reused" (sample planes the last frame took from the table).
  * "batch_lanes": the streams the last frame's batches ran on, as planned (1 unless path-traced). */
 int  frayhip_scene_get_option(frayhip_scene* s, const char* name, int64_t* value);
+/* Tight gates.  Path tracing, scenes with exact gates: a gate that stands for an ELIGIBLE mesh -- untransformed, no KD-tree, six to 32 triangles with
+ * finite coordinates below 2^24, stored normals that are their edges' cross products, no sliver, at most six normal directions (a box has three) --
+ * is tested by the producers against the box of the mesh's own triangles, with a guard against rays nearly parallel to a face, instead of the
+ * mesh's bounding box.  The bounding box of a mesh loaded from an OBJ file also holds the loader's dummy vertex (0, 0, 0): cornell_box's two blocks
+ * fill a fraction of theirs.  Under the certificate (fray_amd/csrc/dev_gatecert.hpp: statement, proof; tests/test_gatecert_host.py) no triangle of
+ * the mesh accepts the ray as the reference's own arithmetic computes it, so the picture is the same bit for bit, in both arithmetics
+ * (tests/test_gpu_tight_gates.py); more rays are filed gate-free and more next-event segments are certified.  On by default; the environment
+ * variable FRAYHIP_TIGHT_GATES=0 presets it off at frayhip_scene_create.  Takes effect in frayhip_render* frames of scenes whose kernels are the
+ * leanest variants (no KD mesh, no Cube / CSG, no texture), in the timed kernels of the exact arithmetic: the counting kernels and the fp_contract
+ * copies keep the bounding boxes (they measured slower with it), as do the query, adaptive and feature entries.
+ * enable: 1 / 0 switches it on / off (not while the scene renders), -1 leaves it.  enabled, eligible (either may be null): the switch, and the number
+ * of gates of the scene, as last uploaded or updated, that are eligible. */
+int  frayhip_scene_tight_gates(frayhip_scene* s, int enable, int64_t* enabled, int64_t* eligible);
 
 /* Threads: a frayhip_scene renders one frame at a time (it owns one workspace and one set of
  * counters), as the reference calls render() from one thread at a time (main.cpp:407-412,448);
