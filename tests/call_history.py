@@ -1,7 +1,8 @@
 """Operations on a scene handle and the orders to run them in (DESIGN.md "What the call histories show").  Not a test module.
 
 An OPERATION is a complete configuration plus one call: before its call it writes the frame size, every settings and camera field, every settable
-option and -- through Scene.update, when they differ from what the handle holds -- the editable tables.  So the only thing one operation hands to the
+option, the tight-gates switch (frayhip_scene_tight_gates, which is no option name) and -- through Scene.update, when they differ from what the handle
+holds -- the editable tables.  So the only thing one operation hands to the
 next is what the library keeps behind the handle (render_state.hpp: the workspace, the statistics block and its tile cursors, the queue tables, the seed
 table, the warm mask, the effective budget, the motion table, the event pools, the lane streams), and that is what the sequences below vary.  An
 operation's answer is a dict of arrays and integers; answers are compared byte for byte.
@@ -22,6 +23,7 @@ SCENES = [n for n, _ in SCENES_BY_WORD]
 # to the library's, so that a new option fails there until the operations set it
 OPTION_DEFAULTS = dict(pt_lanes=4, pt_budget_mib=24576, speculate_fans=1, fused_whitted_max=4, fp_contract=0, seed_table_mib=4096,
                        skip_null_segments=1, segment_planes=1, certified_segments=1)
+TIGHT_GATES_DEFAULT = 1         # frayhip_scene_tight_gates: the switch a handle is created with (render_state.hpp tightGates), written like an option
 # the settings and camera fields an operation may set; every other field is written from the scene file's record before every call
 SETTINGS_SET = ("frameWidth", "frameHeight", "wantAA", "gi", "maxTraceDepth", "numPaths")
 CAMERA_SET = ("dof", "stereoSeparation")
@@ -60,20 +62,21 @@ SCENE_FACTS = {
 
 
 class Op:
-    """name; settings / camera / options: what differs from the defaults above; tables: "original", "edit_node" or "edit_other"; call(handle) -> answer;
+    """name; settings / camera / options: what differs from the defaults above; tight_gates: the switch of frayhip_scene_tight_gates, 1 or 0;
+    tables: "original", "edit_node" or "edit_other"; call(handle) -> answer;
     kind: which of the last frame's figures the call writes (OWNED);
     work: the workspace the call left on a fresh handle, in bytes (filled in by whoever measured it; big_then_small reads it)."""
 
-    def __init__(self, name, call, settings=None, camera=None, options=None, tables="original", kind="frame"):
-        self.name, self.call, self.tables, self.work, self.kind = name, call, tables, None, kind
-        assert kind in OWNED, kind
+    def __init__(self, name, call, settings=None, camera=None, options=None, tables="original", kind="frame", tight_gates=TIGHT_GATES_DEFAULT):
+        self.name, self.call, self.tables, self.work, self.kind, self.tight_gates = name, call, tables, None, kind, tight_gates
+        assert kind in OWNED and tight_gates in (0, 1), (kind, tight_gates)
         self.settings, self.camera, self.options = dict(settings or {}), dict(camera or {}), dict(options or {})
         assert set(self.settings) <= set(SETTINGS_SET) and set(self.camera) <= set(CAMERA_SET) and set(self.options) <= set(OPTION_DEFAULTS), name
 
     def config(self):
-        """the complete configuration: every option, every settable settings and camera field, and the tables"""
+        """the complete configuration: every option, the tight-gates switch, every settable settings and camera field, and the tables"""
         return dict(settings=dict(SETTINGS_DEFAULTS, **self.settings), camera=dict(CAMERA_DEFAULTS, **self.camera),
-                    options=dict(OPTION_DEFAULTS, **self.options), tables=self.tables)
+                    options=dict(OPTION_DEFAULTS, **self.options), tight_gates=self.tight_gates, tables=self.tables)
 
     def __repr__(self):
         return "Op(%s)" % self.name
@@ -121,6 +124,7 @@ class Handle:
         s.beginFrame()
         for k, v in cfg["options"].items():
             s.set_option(k, v)
+        s.tight_gates(cfg["tight_gates"])
         if cfg["tables"] != self.tables:
             self._write_tables(cfg["tables"])
             s.update()
@@ -333,7 +337,7 @@ def raising_callback(h):
 
 
 WHITTED = dict(gi=0, wantAA=0)
-# scene -> the operations it refuses, which operations() leaves out.  None: run once each on a fresh handle, all four scenes accept all forty
+# scene -> the operations it refuses, which operations() leaves out.  None: run once each on a fresh handle, all four scenes accept all of theirs
 # (cornell_box and csg_nested render Whitted frames with k_whitted, boxed with the wavefront launches, textured_plain fused and, at
 # fused_whitted_max = 0, with the wavefront launches: the three values of whitted_path)
 REFUSED = {}
@@ -386,6 +390,9 @@ def operations(name):
         Op("refused-argument", refused_argument, kind="none"),
         Op("raising-callback", raising_callback),
     ]
+    if name == "cornell_box":
+        # the scene with eligible gates (its two blocks): the switch off hands render_impl the table's plain half; after every other operation, which sets it on
+        ops.append(Op("pt-no-tight-gates", frame(), tight_gates=0))
     dropped = REFUSED.get(name, ())
     assert set(dropped) <= {o.name for o in ops}
     return [o for o in ops if o.name not in dropped]

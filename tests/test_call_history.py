@@ -89,6 +89,8 @@ def test_every_operation_sets_every_option_the_library_accepts(fray, abi):
                                       speculate_fans=int(member("bool speculateFans") == "true"), fused_whitted_max=int(member("int fusedWhittedMax")),
                                       fp_contract=int(member("bool fpContract") == "true"), skip_null_segments=int(member("bool skipNullSegments") == "true"),
                                       segment_planes=int(member("bool segmentPlanes") == "true"), certified_segments=int(member("bool certifiedSegments") == "true"))
+    # the tight-gates switch is no option name (frayhip_scene_tight_gates): the operations write it all the same, from the default a handle is created with
+    assert "tight_gates" not in accepted and ch.TIGHT_GATES_DEFAULT == int(member("bool tightGates") == "true") == 1
     fields = {n for n, _ in abi.Settings._fields_}
     cam = {n for n, _ in abi.Camera._fields_}
     assert set(ch.SETTINGS_SET) <= fields and set(ch.SETTINGS_DEFAULTS) == set(ch.SETTINGS_SET)
@@ -100,6 +102,7 @@ def test_every_operation_sets_every_option_the_library_accepts(fray, abi):
         for o in ops:
             cfg = o.config()
             assert set(cfg["options"]) == accepted, (name, o.name)
+            assert cfg["tight_gates"] in (0, 1), (name, o.name)
             assert set(cfg["settings"]) == set(ch.SETTINGS_SET) and set(cfg["camera"]) == set(ch.CAMERA_SET), (name, o.name)
             assert cfg["tables"] in ("original", "edit_node", "edit_other"), (name, o.name)
             assert set(ch.OWNED[o.kind]) <= set(ch.FIGURES), o.name
@@ -117,6 +120,58 @@ def test_the_operations_reach_what_the_issue_lists():
         assert any(c["camera"]["stereoSeparation"] for c in ops.values())
         assert {c["tables"] for c in ops.values()} == {"original", "edit_node", "edit_other"}
         assert all(ch.SCENE_FACTS[name][e] for e in ("edit_node", "edit_other"))
+    # the tight-gates switch off: one path-traced frame of the scene whose blocks are eligible gates; every other operation writes the default
+    for name in ch.SCENES:
+        off = [o for o in ch.operations(name) if o.config()["tight_gates"] != ch.TIGHT_GATES_DEFAULT]
+        assert [o.name for o in off] == (["pt-no-tight-gates"] if name == "cornell_box" else []), name
+        assert all(o.kind == "frame" and o.config()["settings"]["gi"] == 1 and o.config()["options"] == ch.OPTION_DEFAULTS for o in off)
+
+
+class FakeScene:
+    """what Handle.configure and Handle.run call on a fray_amd.Scene, recorded: the switch is state behind the handle as the options are"""
+    def __init__(self):
+        import types
+        self.desc = types.SimpleNamespace(settings=bytearray(8), camera=bytearray(8))
+        self.settings, self.camera = types.SimpleNamespace(), types.SimpleNamespace()
+        self.options, self.switch, self.log = {}, ch.TIGHT_GATES_DEFAULT, []
+
+    def beginFrame(self):
+        self.log.append("beginFrame")
+
+    def set_option(self, name, value):
+        self.options[name] = value
+        self.log.append("set_option")
+
+    def tight_gates(self, enable=None):
+        if enable is not None:
+            self.switch = int(bool(enable))
+            self.log.append("tight_gates")
+        return self.switch, 2
+
+    def get_option(self, name):
+        return 0
+
+    def update(self):
+        raise AssertionError("no operation here edits a table")
+
+
+def test_configure_writes_the_switch_before_every_call(monkeypatch):
+    """Handle.configure over a fake scene: every operation writes the switch, after the view and the options and before its call -- so the frame of an
+    operation does not depend on an earlier operation having flipped it"""
+    monkeypatch.setattr(ch.C, "memmove", lambda *a: None)
+    monkeypatch.setattr(ch.C, "byref", lambda x: x)
+    h = object.__new__(ch.Handle)
+    h.s, h.facts, h.settings0, h.camera0, h.tables, h.edited = FakeScene(), ch.SCENE_FACTS["cornell_box"], b"", b"", "original", False
+    seen = []
+    ops = {o.name: o for o in ch.operations("cornell_box")}
+    for name, want in (("pt", 1), ("pt-no-tight-gates", 0), ("pt", 1), ("pt-no-tight-gates", 0), ("pt-no-tight-gates", 0), ("adaptive", 1), ("primary", 1)):
+        op = ch.Op(name, lambda hd: seen.append(hd.s.tight_gates()[0]) or {}, ops[name].settings, ops[name].camera, ops[name].options, ops[name].tables,
+                   ops[name].kind, ops[name].tight_gates)
+        h.s.log = []
+        h.run(op)
+        assert seen[-1] == want and h.s.switch == want, name
+        assert h.s.log.count("tight_gates") == 1 and h.s.log.index("tight_gates") > max(i for i, c in enumerate(h.s.log) if c != "tight_gates"), h.s.log
+        assert h.s.options == ch.OPTION_DEFAULTS
 
 
 # ---- the comparer, over a handle that leaks -----------------------------------------------------------------------------------------------------------

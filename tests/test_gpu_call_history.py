@@ -22,7 +22,7 @@ from test_trace_host import ADVERSARIAL, flag_word
 pytestmark = pytest.mark.gpu
 
 SEED = 11
-ARC = 201               # calls per arc of the circuit: eight arcs a scene, measured 0.17 to 0.95 s each (DESIGN.md "What the call histories show")
+ARC = 201               # calls per arc of the circuit: eight arcs a scene of forty operations (cornell_box, with forty-one: a short ninth), measured 0.17 to 0.95 s each (DESIGN.md "What the call histories show")
 WORDS = dict(ch.SCENES_BY_WORD)
 
 # Figures of frayhip_scene_get_option that may depend on what ran before, each for a reason in the code:
@@ -139,6 +139,7 @@ def test_a_fresh_handle_has_the_defaults_and_accepts_every_option(fray, abi, cas
     """the library itself asked for the names of abi.OPTION_NAMES: each reads back call_history's default on a fresh handle and is accepted; another name is refused"""
     s = cases("textured_plain").handle.renew().s
     assert {k: s.get_option(k) for k in abi.OPTION_NAMES} == ch.OPTION_DEFAULTS
+    assert s.tight_gates()[0] == ch.TIGHT_GATES_DEFAULT                   # the switch that is no option name
     for k in abi.OPTION_NAMES:
         s.set_option(k, ch.OPTION_DEFAULTS[k])
     for k in abi.FIGURE_NAMES + ("no_such_option",):
