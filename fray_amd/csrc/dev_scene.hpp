@@ -181,6 +181,13 @@ struct DCamera {
 // frayhip_scene_tight_gates chooses the half DScene::gates points to (render_impl.hpp), so the producers run one code on either.
 struct DGate { double lo[3], hi[3]; float cf[3], hf[3]; float Mf; int32_t exact; float guard; int32_t nDirs; float nf[FRAY_GATE_MAX_DIRS][3]; };      // 160 B
 
+// Miss records of the first bounce (dev_trace.hpp camera_skip_nodes, frayhip_scene_camera_skip): per eligible node -- an untransformed mesh without a KD-tree, of at most
+// FRAY_GATECERT_MAX_TRIS triangles (two suffice: a wall), node index below 32, accepted by gatecert_make -- DGateTight's content, made from the node's own triangles exactly
+// as the tight half of the gate table is, and the node's index.  A wave of camera rays that all pass a record's certificate does not ask that node.  At most
+// FRAY_CAMSKIP_MAX records, in node order; further nodes get none and are always asked.  The table's unused tail is zero.
+#define FRAY_CAMSKIP_MAX 16
+struct DCamSkip { float cf[3], hf[3]; float Mf, guard; float nf[FRAY_GATE_MAX_DIRS][3]; int32_t nDirs, node; };      // 112 B
+
 struct DScene {
     const FRAY_RO DNode* nodes;
     const FRAY_RO DNodeX* nodesX;
@@ -210,6 +217,9 @@ struct DScene {
     int32_t skipNullSegments;      // option "skip_null_segments": the timed path-tracing kernels do not queue a next-event segment whose contribution is +0 in all three channels (dev_shade.hpp nee_prepare)
     int32_t segCertAll;            // every node is a segment-plane node or lies in an exact gate (scene_arena.hpp fill_editable): a segment that passes every plane and every gate is visible
     int32_t certifiedSegments;     // option "certified_segments" (and "segment_planes", and segCertAll): path_shade stores the term of such a segment itself instead of queueing it
+    // Miss records of the first bounce (DCamSkip above).  nCamSkip is the frame's: 0 while frayhip_scene_camera_skip is switched off (frame_scene).
+    const FRAY_RO DCamSkip* camSkip;
+    int32_t nCamSkip, padCamSkip;
 };
 
 // Work decomposition of a frame: the reference's 48x48 buckets (sdl.cpp:243-262), of which this

@@ -1041,8 +1041,11 @@ FD void light_record(const FRAY_RO DLight& L, V3 o, V3 d, V3& ip, V3& norm)
 // gateFree: the ray's producer PROVED that it misses every gate of the scene (kernels.hpp ray_gate_class with DScene::gatesExact; dev_misscert.hpp): the
 // gated nodes' geometry then reports no intersection, as the reference computes it, and is not asked (the counting variants ask: a CsgOp node's
 // calls are part of their counters).
-template <int ST>
-FD void closest_hit(const DScene& S, V3 o, V3 d, HitT<ST>& best, Cnt& c, bool gateFree = false)
+// CAMSKIP: compiled with the test for the nodes in `skipNodes` (camera_skip_nodes below: the first bounce of the leanest timed variant only -- every other
+// instantiation is the code it was without it).  Bit i: the certificate of dev_gatecert.hpp holds for node i and EVERY ray of the wave, so the node's mesh
+// reports no intersection as the reference computes it; wave-uniform, a scalar branch before the node's record is touched.
+template <int ST, bool CAMSKIP = false>
+FD void closest_hit(const DScene& S, V3 o, V3 d, HitT<ST>& best, Cnt& c, bool gateFree = false, uint32_t skipNodes = 0u)
 {
     bump<ST>(c.closest);
     best.node = -1;
@@ -1056,6 +1059,7 @@ FD void closest_hit(const DScene& S, V3 o, V3 d, HitT<ST>& best, Cnt& c, bool ga
     for (int i = 0; i < nn; i++) {
         double dist, t, l2 = 0, l3 = 0;
         int tri = -1;
+        if constexpr (CAMSKIP) { if (i < 32 && ((skipNodes >> i) & 1u)) continue; }
         if constexpr (!(ST & 1)) { if (S.nodes[i].gated) { if (gateFree) continue; } }        // (the node's word first: wave-uniform, a scalar branch for every node that is not gated)
         if constexpr ((ST & 2) != 0) {
             // Cube / CSG variants: the winning intersection as its geometry reported it travels with the hit record (finalize_hit)
@@ -1109,6 +1113,35 @@ FD uint32_t segment_skip_nodes(const DScene& S, V3 a, V3 b, bool live)
     const int nS = S.nSegNodes;
     for (int j = 0; j < nS; j++)
         if ((S.segNodeMasks[j] & ~certified) == 0u) skipNodes |= 1u << j;
+    return skipNodes;
+}
+
+// The first bounce's shortcut (k_pt_bounce<0, false, true>; frayhip_scene_camera_skip): the nodes no camera ray of this wave can hit.  A first-bounce wave is one
+// 8x8 pixel tile at one sample index: it sees one wall, sometimes two, and closest_hit would still ask every mesh -- the reference's bounding box of an OBJ mesh
+// holds the loader's dummy vertex (0, 0, 0), which for three of cornell_box's walls makes it the whole room.  Called by the WHOLE wave before closest_hit(): each
+// lane evaluates dev_gatecert.hpp's certificate (box part, guards, bounds on the ray -- ray_surely_misses_mesh_f32) for every miss record (dev_scene.hpp DCamSkip)
+// on its own camera ray, converted to FP32 as ray_gate_class<true> converts it; a lane that is not live passes.  Under the certificate no triangle of the node's
+// mesh accepts the ray, whatever `best` is and whether the mesh's box test passes or not, so a node whose record every lane passes reports nothing to this wave.
+// Returns those nodes, bit `node`: a wave-uniform word, computed in wave-uniform control flow, so that it and everything derived from it stay in scalar registers.
+FD uint32_t camera_skip_nodes(const DScene& S, V3 o, V3 d, bool live)
+{
+    const int nR = S.nCamSkip;
+    if (nR <= 0) return 0u;
+    const float dx = (float)d.x, dy = (float)d.y, dz = (float)d.z;
+    const float dsum = fabsf(dx) + fabsf(dy) + fabsf(dz);
+    const float ox = (float)o.x, oy = (float)o.y, oz = (float)o.z;
+    const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
+    const bool range = gate_ray_range(dsum, omax, ox + oy + oz);
+    const lanes_t all = lanes(true);
+    uint32_t skipNodes = 0;
+    for (int r = 0; r < nR; r++) {
+        const FRAY_RO DCamSkip& R = S.camSkip[r];
+        // ray_surely_misses_mesh_f32's three parts
+        bool miss = ray_surely_misses_box_f32(R.cf[0], R.cf[1], R.cf[2], R.hf[0], R.hf[1], R.hf[2], R.Mf, ox, oy, oz, dx, dy, dz, omax, dsum);
+        miss = miss & gate_guard_f32(R, dx, dy, dz, dsum);
+        miss = miss & range;
+        if (lanes(!live || miss) == all) skipNodes |= 1u << R.node;
+    }
     return skipNodes;
 }
 

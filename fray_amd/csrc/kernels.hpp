@@ -1197,7 +1197,9 @@ struct LongRng { uint32_t* cols; uint32_t nPaths; DFrame F; int nItems, s0; };
 // reading them from a queue -- no 92-byte path record written and read back per camera sample, one launch less per batch.
 struct FirstArgs { DCamera C; DFrame F; int nItems, s0; uint32_t n; const uint32_t* x397; unsigned short* termCount; };
 // segCertified (may be null): the batch lane's count of next-event segments path_shade certified instead of queueing (render_state.hpp kSegCertifiedOffset), one atomic per wave
-struct BounceArgs { DScene S; PathQueue Qin, Qout; ShadowQueue SQ; QMetaRO metaIn; QMeta* metaOut; QMeta* metaShadow; TermBuf TB; StereoBuf SB; LongRng LR; DStats* st; FirstArgs FA; unsigned long long* segCertified; };
+// camSkipped (may be null): two words of the batch lane (render_state.hpp kCamSkippedOffset) -- the (wave, node) pairs the first bounce skipped by its miss records
+// (dev_trace.hpp camera_skip_nodes) and the wave iterations that evaluated them, one atomic each per wave
+struct BounceArgs { DScene S; PathQueue Qin, Qout; ShadowQueue SQ; QMetaRO metaIn; QMeta* metaOut; QMeta* metaShadow; TermBuf TB; StereoBuf SB; LongRng LR; DStats* st; FirstArgs FA; unsigned long long* segCertified; unsigned long long* camSkipped; };
 // ARITH: how the translation unit was compiled -- 0 = the reference's arithmetic (-ffp-contract=off: every hit record and every colour is the CPU reference build's, bit
 // for bit), 1 = -ffp-contract=fast (render_contract.hip: multiply-add pairs fused; only for rays AFTER a sample's first closest hit, i.e. colour within
 // north_star's 1e-4 RMS, option "fp_contract").  The parameter only names the kernel apart in profiles; the code is the same source.
@@ -1228,6 +1230,10 @@ static __global__ __launch_bounds__(256, waves_for(ST, kd_variant(ST) ? FRAY_BOU
 #ifdef FRAY_STAMPS
     stamp_begin();
 #endif
+    // the first bounce of the leanest timed variant leaves out the nodes its wave's camera rays provably miss (camera_skip_nodes).  Not the counting variants, whose
+    // counters are the reference's: they ask every node
+    constexpr bool CAMSKIP = FIRST && tight_variant(ST);
+    uint32_t camSkipped = 0, camWaves = 0;                                                // (wave-uniform)
     constexpr bool SORT = FRAY_SORT && !FIRST && sort_variant(ST);
     const uint32_t sortN = (uint32_t)FRAY_SORT_N;
     for (uint32_t b0 = ws.begin, b1 = 0; b0 < ws.end; b0 = b1) {            // (a kernel that does not sort takes its whole share in one go)
@@ -1254,6 +1260,7 @@ static __global__ __launch_bounds__(256, waves_for(ST, kd_variant(ST) ? FRAY_BOU
         bool cont = false, shadow = false, gateFree = false;
         uint32_t shadowBack = 0;
         PathStateT<G> ps;
+        if constexpr (CAMSKIP) { ps.o = v3(0, 0, 0); ps.d = v3(0, 0, 0); }               // (every lane's ray is read below, a dead lane's too)
         bool live = di < b1;
         uint32_t i = di, seed0 = 0;
         if constexpr (FIRST) {
@@ -1280,11 +1287,19 @@ static __global__ __launch_bounds__(256, waves_for(ST, kd_variant(ST) ? FRAY_BOU
                 live = !(ps.d.x == 0 && ps.d.y == 0 && ps.d.z == 0);            // k_pt_init's mark of a slot without a path
             }
         }
+        uint32_t skipNodes = 0;                                                           // (wave-uniform)
+        if constexpr (CAMSKIP) {
+            if (S.nCamSkip > 0 && lanes(live) != 0) {
+                skipNodes = camera_skip_nodes(S, ps.o, ps.d, live);
+                camSkipped += (uint32_t)__builtin_popcount(skipNodes);
+                camWaves++;
+            }
+        }
         if (live) {
             STAMP(0);
             // entry test of pathtrace() (main.cpp:173-176) was applied before this path was queued
             HitT<ST> h;
-            closest_hit<ST>(S, ps.o, ps.d, h, c, gateFree);
+            closest_hit<ST, CAMSKIP>(S, ps.o, ps.d, h, c, gateFree, skipNodes);
             if constexpr (FIRST) {
                 // the rest of the path's state, made after the search so that it is not live across it: the generators stand where the camera ray left them
                 ps.pm = c3(1, 1, 1); ps.slot = di; ps.depth = 0; ps.flags = 0;
@@ -1338,6 +1353,10 @@ static __global__ __launch_bounds__(256, waves_for(ST, kd_variant(ST) ? FRAY_BOU
             unsigned long long* const total = KARG(BounceArgs, kernel_args<BounceArgs>(), segCertified);
             const uint32_t nCert = shadowCount[threadIdx.x >> 6][2];
             if (total && nCert) atomicAdd(total, (unsigned long long)nCert);
+        }
+        if constexpr (CAMSKIP) {
+            unsigned long long* const pairs = KARG(BounceArgs, kernel_args<BounceArgs>(), camSkipped);
+            if (pairs && camWaves) { atomicAdd(pairs, (unsigned long long)camSkipped); atomicAdd(pairs + 1, (unsigned long long)camWaves); }
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {

@@ -542,6 +542,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 unsigned long long* segTotal;       // this lane's running total of shadow-queue entries (render_state.hpp kSegTotalsOffset)
                 unsigned long long* segSkipped;     // ... and of the nodes its shadow launches skipped by the segment-plane certificate (kSegSkippedOffset)
                 unsigned long long* segCertified;   // ... and of the segments its bounce launches certified instead of queueing (kSegCertifiedOffset)
+                unsigned long long* camSkipped;     // ... and the two words of its first bounces' skipped nodes and wave iterations (kCamSkippedOffset)
             } lane[FRAY_PT_LANES];
             unsigned char* p = (unsigned char*)sc->d_work;
             float* sum = (float*)p; p += ((size_t)nItems * 12 + 255) / 256 * 256;
@@ -552,6 +553,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 L.segTotal = (unsigned long long*)((unsigned char*)sc->d_stats + kSegTotalsOffset) + k;
                 L.segSkipped = (unsigned long long*)((unsigned char*)sc->d_stats + kSegSkippedOffset) + k;
                 L.segCertified = (unsigned long long*)((unsigned char*)sc->d_stats + kSegCertifiedOffset) + k;
+                L.camSkipped = (unsigned long long*)((unsigned char*)sc->d_stats + kCamSkippedOffset) + 2 * k;
                 p = carve_queue(p, nQueue, L.Q[0]);
                 p = carve_queue(p, nQueue, L.Q[1]);
                 p = carve_shadow(p, nQueue, L.SQ);
@@ -603,7 +605,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                         const LongRng LR{L.mtCols, (uint32_t)nPaths, F, nItems, s0};
                         const TermBuf TB{L.terms, L.termCount, (uint32_t)nPaths, b};
                         const FirstArgs FA{C, F, nItems, s0, (uint32_t)((size_t)nItems * cn), x397, L.termCount};
-                        const BounceArgs BA{S, L.Q[b & 1], L.Q[(b + 1) & 1], L.SQ, mIn, L.meta + ((b + 1) & 1), L.meta + 2, TB, save, LR, sc->d_stats, FA, L.segCertified};
+                        const BounceArgs BA{S, L.Q[b & 1], L.Q[(b + 1) & 1], L.SQ, mIn, L.meta + ((b + 1) & 1), L.meta + 2, TB, save, LR, sc->d_stats, FA, L.segCertified, L.camSkipped};
                         // option "fp_contract": bounces after a sample's first closest hit (and every visibility query) are colour, bounded by RMS and not by
                         // bits -- they run the kernels compiled with fused multiply-adds (render_contract.hip; not built for the Cube / CSG variants, which
                         // measured slower with it)
@@ -665,8 +667,8 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
     HIP_TRY(hipEventRecord(sc->evB, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     drain.armed = false;                    // every lane was joined into `stream` above
-    struct Back { DStats ds[2]; unsigned long long segTotal[FRAY_PT_LANES], segSkipped[FRAY_PT_LANES], segCertified[FRAY_PT_LANES]; } back;         // the two counter blocks, the lanes' shadow-queue totals, skipped nodes and certified segments: one copy
-    static_assert(offsetof(Back, segTotal) == kSegTotalsOffset && offsetof(Back, segSkipped) == kSegSkippedOffset && offsetof(Back, segCertified) == kSegCertifiedOffset,
+    struct Back { DStats ds[2]; unsigned long long segTotal[FRAY_PT_LANES], segSkipped[FRAY_PT_LANES], segCertified[FRAY_PT_LANES], camSkipped[FRAY_PT_LANES][2]; } back;         // the two counter blocks, the lanes' shadow-queue totals, skipped nodes, certified segments and first-bounce skips: one copy
+    static_assert(offsetof(Back, segTotal) == kSegTotalsOffset && offsetof(Back, segSkipped) == kSegSkippedOffset && offsetof(Back, segCertified) == kSegCertifiedOffset && offsetof(Back, camSkipped) == kCamSkippedOffset,
                   "the shadow-queue totals, the skipped nodes and the certified segments follow the counter blocks");
     HIP_TRY(hipMemcpy(&back, sc->d_stats, sizeof back, hipMemcpyDeviceToHost));
     const DStats (&dsv)[2] = back.ds;
@@ -678,6 +680,8 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
     sc->lastShadowSegments += sc->lastShadowCertified;
     sc->lastShadowNodesSkipped = 0;
     for (int k = 0; k < FRAY_PT_LANES; k++) sc->lastShadowNodesSkipped += (long long)back.segSkipped[k];
+    sc->lastCameraSkipped = sc->lastCameraWaves = 0;
+    for (int k = 0; k < FRAY_PT_LANES; k++) { sc->lastCameraSkipped += (long long)back.camSkipped[k][0]; sc->lastCameraWaves += (long long)back.camSkipped[k][1]; }
     {
         unsigned long long ft[4] = {0, 0, 0, 0};
         if (fanTotals) HIP_TRY(hipMemcpy(ft, fanTotals, sizeof ft, hipMemcpyDeviceToHost));

@@ -82,6 +82,8 @@ struct frayhip_scene {
     bool segmentPlanes = true;        // option "segment_planes": k_pt_shadow skips, per wave, the eligible nodes whose triangles' planes no live segment crosses (dev_segcert.hpp)
     bool certifiedSegments = true;    // option "certified_segments": path_shade stores the term of a next-event segment proven unoccluded itself instead of queueing it (dev_trace.hpp segment_certified; needs segmentPlanes and DScene::segCertAll)
     bool tightGates = true;           // frayhip_scene_tight_gates: the producers test an eligible mesh's gate by its own triangles' box and a guard (dev_gatecert.hpp) instead of its reference box
+    bool cameraSkip = true;           // frayhip_scene_camera_skip: a first-bounce wave leaves out the meshes all its camera rays provably miss (dev_trace.hpp camera_skip_nodes, dev_scene.hpp DCamSkip)
+    long long lastCameraSkipped = 0, lastCameraWaves = 0;   // the last frame's (wave, node) pairs skipped that way, and the first-bounce wave iterations that evaluated the records (frayhip_scene_camera_skip)
     long long lastShadowCertified = 0;   // the last frame's next-event segments decided that way (frayhip_scene_get_option "shadow_segments_certified"); they are part of lastShadowSegments
     long long lastShadowNodesSkipped = 0;   // the last frame's sum over k_pt_shadow's wave iterations of the nodes skipped that way (frayhip_scene_get_option "shadow_nodes_skipped")
     long long lastShadowSegments = 0; // the last frame's next-event segments the timed kernels decided, shadow-queue entries over all its launches plus the certified ones (frayhip_scene_get_option "shadow_segments"; render_impl frames)
@@ -125,11 +127,13 @@ namespace frayhip_detail {
 // ... and, in the gap before the cursors, one running total of shadow-queue entries per batch lane (k_scan adds each launch's total to its lane's word:
 // the launches of a lane are ordered by its stream, so no atomic is needed); and after those, per batch lane, the nodes k_pt_shadow's waves skipped by the
 // segment-plane certificate (one atomic per wave at the kernel's end); and after those, per batch lane, the next-event segments k_pt_bounce's waves certified
-// instead of queueing (the same pattern)
+// instead of queueing (the same pattern); and after those, per batch lane, two words: the (wave, node) pairs the first bounce skipped by its miss records and the
+// wave iterations that evaluated them (the same pattern)
 constexpr size_t kSegTotalsOffset = 2 * sizeof(DStats);
 constexpr size_t kSegSkippedOffset = kSegTotalsOffset + FRAY_PT_LANES * sizeof(unsigned long long);
 constexpr size_t kSegCertifiedOffset = kSegSkippedOffset + FRAY_PT_LANES * sizeof(unsigned long long);
-constexpr size_t kCursorOffset = (kSegCertifiedOffset + FRAY_PT_LANES * sizeof(unsigned long long) + 255) / 256 * 256;
+constexpr size_t kCamSkippedOffset = kSegCertifiedOffset + FRAY_PT_LANES * sizeof(unsigned long long);
+constexpr size_t kCursorOffset = (kCamSkippedOffset + 2 * FRAY_PT_LANES * sizeof(unsigned long long) + 255) / 256 * 256;
 constexpr size_t kStatsBytes = kCursorOffset + 3 * sizeof(DCursors);     // sets of tile cursors: a batch's closest-hit and any-hit kernels; the three passes of speculative Whitted
 
 DCamera camera_begin_frame(const frayhip_camera& c, int W, int H);

@@ -33,6 +33,7 @@ struct ArenaFacts {
     int32_t extGeometry, kdMeshes, textured, whittedNeedsRecursion, lightDraws, lightSampleCount, specFanMax;
     int32_t nGates, gatesExact, nSegPlanes, nSegNodes, segCertAll;
     int32_t nTightGates;                      // gates whose entry in the table's tight half differs: eligible meshes (dev_gatecert.hpp)
+    int32_t nCamSkip, tCamSkip;               // miss records of the first bounce (dev_scene.hpp DCamSkip) and their table
     int32_t nNodes, nLights, nMeshes, nTextures;
     int32_t envPresent, envLoaded, envWidth[6], envHeight[6];
     int64_t envTexelOffset[6];
@@ -98,7 +99,7 @@ inline bool shader_uses_uv(const frayhip_scene_desc& d, int s, int depth = 0)
 // segment planes, the primitives, shaders, layers, lights and texture records, and the scene facts that follow from them.  arena_build runs it on the
 // freshly laid out arena and arena_update on an arena built earlier, so an updated arena equals a fresh one byte for byte.  tab[t] is where table t
 // can be written.  Read besides `d`: the DMesh table (the header scalars of every mesh) and the DTri table of every mesh without a KD-tree and with
-// at most FRAY_GATECERT_MAX_TRIS triangles (arena_keeps_tris: the segment planes of the small ones, the tight gate records of the others) -- never a
+// at most FRAY_GATECERT_MAX_TRIS triangles (arena_keeps_tris: the segment planes of the small ones, the tight gate records of the others, the first bounce's miss records of both) -- never a
 // mesh array or the texel pool of `d`.  Every inner pointer is written null
 // (arena_place); the unused tails of the gate and segment-plane tables are zeroed.  F: the t* indices and the counts are read, the editable facts written.
 inline bool arena_keeps_tris(const DMesh& M) { return !M.hasKd && M.nTris > 0 && M.nTris <= FRAY_GATECERT_MAX_TRIS; }
@@ -372,6 +373,29 @@ inline void fill_editable(const frayhip_scene_desc& d, const ArenaMeshTables* me
         if (nGates) memcpy(tab[F.tGates], gates, (size_t)nGates * sizeof(DGate));
         if (nGates) memcpy(tab[F.tGates] + FRAY_MAX_GATES * sizeof(DGate), tight, (size_t)nGates * sizeof(DGate));
     }
+    // Miss records of the first bounce (dev_scene.hpp DCamSkip): every untransformed tree-less mesh node of at most FRAY_GATECERT_MAX_TRIS triangles whose index a
+    // 32-bit word holds and which gatecert_make accepts -- no FRAY_GATE_MIN_TRIS floor, a two-triangle wall qualifies -- in node order, FRAY_CAMSKIP_MAX at most.
+    // Made from the DTri table like the tight entries above; the gate table, `gated` and the segment planes do not know of them.
+    int nCamSkip = 0;
+    {
+        DCamSkip recs[FRAY_CAMSKIP_MAX];
+        memset(recs, 0, sizeof recs);
+        for (int i = 0; i < d.n_nodes && i < 32 && nCamSkip < FRAY_CAMSKIP_MAX; i++) {
+            const DNode& N = nodes[i];
+            if (!(N.tlTris > 0 && N.tlTris <= FRAY_GATECERT_MAX_TRIS && N.xfIdentity)) continue;
+            const DTri* const tris = (const DTri*)tab[meshTables[N.geomIndex].tris];
+            GateTri gt[FRAY_GATECERT_MAX_TRIS];
+            for (int t = 0; t < N.tlTris; t++) gt[t] = GateTri{tris[t].A, tris[t].AB, tris[t].AC, tris[t].N};
+            DGateTight T;
+            if (!gatecert_make(T, gt, N.tlTris)) continue;
+            DCamSkip& o = recs[nCamSkip++];
+            for (int k = 0; k < 3; k++) { o.cf[k] = T.cf[k]; o.hf[k] = T.hf[k]; }
+            o.Mf = T.Mf; o.guard = T.guard; o.nDirs = T.nDirs; o.node = i;
+            memcpy(o.nf, T.nf, sizeof o.nf);
+        }
+        memcpy(tab[F.tCamSkip], recs, sizeof recs);
+    }
+    F.nCamSkip = nCamSkip;
     if (!nodes.empty()) memcpy(tab[F.tNodes], nodes.data(), nodes.size() * sizeof(DNode));
     if (!tex.empty()) memcpy(tab[F.tTex], tex.data(), tex.size() * sizeof(DTexture));
 
@@ -552,6 +576,8 @@ inline void arena_build(const frayhip_scene_desc& d, ArenaBuilt& B)
     A.reserve((size_t)d.n_textures * sizeof(DTexture));
     F.tTex = A.last();
     if (!meshes.empty()) memcpy(A.host.data() + oMeshes, meshes.data(), meshes.size() * sizeof(DMesh));
+    A.reserve(FRAY_CAMSKIP_MAX * sizeof(DCamSkip));                           // the first bounce's miss records (DCamSkip): last, so that every other table stands where it stood
+    F.tCamSkip = A.last();
 
     F.nNodes = d.n_nodes; F.nLights = d.n_lights; F.nMeshes = d.n_meshes; F.nTextures = d.n_textures;
     F.envPresent = d.environment.present;
@@ -584,7 +610,7 @@ inline void arena_update(const frayhip_scene_desc& d, ArenaBuilt& B)
 // the tables arena_update writes: none of them grows with a mesh or with the texel pool
 inline std::vector<int32_t> arena_editable_tables(const ArenaFacts& F)
 {
-    return {F.tNodes, F.tNodesX, F.tGates, F.tSegPlanes, F.tSegMasks, F.tPlanes, F.tSpheres, F.tCubes, F.tShaders, F.tLayers, F.tLights, F.tTex};
+    return {F.tNodes, F.tNodesX, F.tGates, F.tSegPlanes, F.tSegMasks, F.tPlanes, F.tSpheres, F.tCubes, F.tShaders, F.tLayers, F.tLights, F.tTex, F.tCamSkip};
 }
 
 // write[t]: where table t can be written now (the staging copy, or the table itself); addr[t]: where the kernels, or the host harness, will find it.
@@ -617,6 +643,8 @@ inline void arena_place(const ArenaFacts& F, const ArenaMeshTables* meshTables, 
     S.segPlanes = (const FRAY_RO DSegPlane*)addr[F.tSegPlanes];
     S.segNodeMasks = (const FRAY_RO uint32_t*)addr[F.tSegMasks];
     S.nSegPlanes = F.nSegPlanes; S.nSegNodes = F.nSegNodes; S.segCertAll = F.segCertAll;
+    S.camSkip = (const FRAY_RO DCamSkip*)addr[F.tCamSkip];
+    S.nCamSkip = F.nCamSkip; S.padCamSkip = 0;
     S.planes = (const FRAY_RO DPlane*)addr[F.tPlanes];
     S.spheres = (const FRAY_RO DSphere*)addr[F.tSpheres];
     S.cubes = (const FRAY_RO DCube*)addr[F.tCubes];

@@ -684,6 +684,14 @@ class Scene:
         _check(lib.frayhip_scene_tight_gates(self._dev, -1 if enable is None else int(bool(enable)), C.byref(on), C.byref(n)))
         return int(on.value), int(n.value)
 
+    def camera_skip(self, enable=None):
+        """frayhip_scene_camera_skip: switches the first bounce's shortcut on or off (None leaves the switch alone) and returns (enabled, miss records, the last
+        frame's skipped (wave, node) pairs, its first-bounce wave iterations): a wave of camera rays leaves out the eligible meshes all its rays provably miss."""
+        self._need_dev()
+        on, n, skipped, waves = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _check(lib.frayhip_scene_camera_skip(self._dev, -1 if enable is None else int(bool(enable)), C.byref(on), C.byref(n), C.byref(skipped), C.byref(waves)))
+        return int(on.value), int(n.value), int(skipped.value), int(waves.value)
+
     def get_option(self, name):
         """frayhip_scene_get_option: an option's value, or a figure of the last frame ("fans_filed", "fan_children", "fan_children_looked_up", "fans_given_up", "contracted_launches", "shadow_segments",
         "shadow_segments_certified", "certified_segments_eligible", "segment_plane_nodes", "shadow_nodes_skipped", "seed_table_bytes", "seed_launches", "seed_planes_reused", "batch_lanes")."""

@@ -400,6 +400,17 @@ int  frayhip_scene_get_option(frayhip_scene* s, const char* name, int64_t* value
  * enable: 1 / 0 switches it on / off (not while the scene renders), -1 leaves it.  enabled, eligible (either may be null): the switch, and the number
  * of gates of the scene, as last uploaded or updated, that are eligible. */
 int  frayhip_scene_tight_gates(frayhip_scene* s, int enable, int64_t* enabled, int64_t* eligible);
+/* Camera skip.  Path tracing, first bounce: a wave of camera rays -- one 8x8 pixel tile at one sample index -- leaves out every ELIGIBLE mesh that all its
+ * rays provably miss.  Eligible: a mesh node that is untransformed, has no KD-tree and at most 32 triangles (two suffice: a wall), a node index below 32, and
+ * triangles the certificate of fray_amd/csrc/dev_gatecert.hpp admits (as for tight gates above); the first 16 such nodes get a miss record, made from the
+ * node's own triangles.  Under the certificate no triangle of the mesh accepts the ray as the reference's own arithmetic computes it, so the picture is the
+ * same bit for bit (tests/test_gpu_camera_skip.py).  On by default; the environment variable FRAYHIP_CAMERA_SKIP=0 presets it off at frayhip_scene_create.
+ * Takes effect in the frames of frayhip_render* whose first bounce makes its own camera rays (mono, register generators) on the leanest timed kernel of the
+ * exact arithmetic -- a sample's first bounce runs that kernel under option "fp_contract" too; the counting kernels ask every node.
+ * enable: 1 / 0 switches it on / off (not while the scene renders), -1 leaves it.  enabled, eligible, skipped, waves (each may be null): the switch; the
+ * number of miss records of the scene, as last uploaded or updated; the last frame's (wave, node) pairs left out; and the first-bounce wave iterations of
+ * 64 camera rays that evaluated the records (those with a ray in the frame). */
+int  frayhip_scene_camera_skip(frayhip_scene* s, int enable, int64_t* enabled, int64_t* eligible, int64_t* skipped, int64_t* waves);
 
 /* Threads: a frayhip_scene renders one frame at a time (it owns one workspace and one set of
  * counters), as the reference calls render() from one thread at a time (main.cpp:407-412,448);
