@@ -25,7 +25,11 @@ src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --he
                          python -m fray_amd scene.fray -o out.bmp --denoise --frames N --move NODE DX DY DZ --motion-vectors --change-samples K
                                                                                          (the sequence with a probe of K samples per frame that finds
                                                                                           what the move changed in the light -- the node's shadow -- and
-                                                                                          shortens the history there; with or without --split)"""
+                                                                                          shortens the history there; with or without --split)
+                         python -m fray_amd scene.fray -o out.bmp --refine TOL --max-spp N [--accumulate FILE.npz] [--noise-out FILE.npy] [--denoise]
+                                                                                         (samples spent where the frame is noisy: each pixel sampled
+                                                                                          until its relative standard error is TOL or it holds N samples;
+                                                                                          --denoise: the result filtered with its own noise estimate)"""
 import argparse
 import json
 import os
@@ -89,6 +93,13 @@ def build_parser():
                          "state of another size or seed is refused.  With --time-limit the state that was cut short is saved and can be continued")
     ap.add_argument("--noise-out", metavar="FILE.npy",
                     help="with --accumulate: also save the noise buffer, float32 [H, W] (the variance estimate of the mean's luminance)")
+    ap.add_argument("--refine", type=float, metavar="TOL",
+                    help="refined frame (Scene.refine; path-traced mono frames): passes of a sample map and the samples it asks for, until every pixel's "
+                         "relative standard error is <= TOL or the pixel holds --max-spp samples; prints one JSON line with the passes, the samples and "
+                         "the mean spp.  With --accumulate the state in FILE.npz is continued and saved; with --denoise the frame goes through the "
+                         "a-trous filter with its own noise estimate as the variance (denoise_signal, demodulate=0)")
+    ap.add_argument("--max-spp", type=int, metavar="N", help="with --refine: the most samples a pixel may hold (required)")
+    ap.add_argument("--refine-passes", type=int, default=8, metavar="P", help="with --refine: the most passes (default 8)")
     ap.add_argument("--components-out", metavar="FILE.npz",
                     help="component frame (Scene.render_components; path-traced mono frames): render the frame's samples with direct and indirect light "
                          "kept apart and save direct, indirect, noise_direct, noise_indirect, samples and seed; the picture is their sum")
@@ -126,6 +137,17 @@ def check_args(ap, a):
         ap.error("--denoise cannot be combined with --adaptive: denoising adaptive frames is not supported")
     if a.denoise and a.time_limit is not None:
         ap.error("--denoise cannot be combined with --time-limit: the denoiser needs the whole frame")
+    if a.refine is not None:
+        if a.max_spp is None or a.max_spp < 1 or a.max_spp > (1 << 24):
+            ap.error("--refine needs --max-spp N, 1 <= N <= 2^24")
+        if not (a.refine > 0 and a.refine < float("inf")):
+            ap.error("--refine: TOL must be finite and > 0")
+        if a.refine_passes < 1:
+            ap.error("--refine-passes must be >= 1")
+        if a.adaptive is not None or a.probe or a.frames is not None or a.time_limit is not None or a.split or a.components_out or a.progress:
+            ap.error("--refine cannot be combined with --adaptive, --probe, --frames, --time-limit, --progress, --split or --components-out")
+    elif a.max_spp is not None:
+        ap.error("--max-spp needs --refine")
     if a.frames is not None and not a.denoise and not a.move:
         ap.error("--frames needs --denoise: a sequence is rendered with temporal accumulation and the filter")
     if a.move and a.frames is None:
@@ -145,10 +167,10 @@ def check_args(ap, a):
         ap.error("--frames must be >= 1")
     if a.frames is not None and a.features_out:
         ap.error("--frames cannot be combined with --features-out")
-    if a.accumulate and (a.denoise or a.adaptive is not None or a.probe):
-        ap.error("--accumulate cannot be combined with --denoise, --adaptive or --probe")
-    if a.noise_out and not a.accumulate:
-        ap.error("--noise-out needs --accumulate")
+    if a.accumulate and ((a.denoise and a.refine is None) or a.adaptive is not None or a.probe):
+        ap.error("--accumulate cannot be combined with --denoise (but with --refine), --adaptive or --probe")
+    if a.noise_out and not (a.accumulate or a.refine is not None):
+        ap.error("--noise-out needs --accumulate or --refine")
     if a.spp is not None and a.accumulate and a.spp < 1:
         ap.error("--spp must be >= 1")
     if a.split and a.adaptive is not None:
@@ -172,6 +194,16 @@ def check_components(ap, a, s):
         ap.error("%s needs a path-traced scene (gi on): a Whitted frame has no direct / indirect split" % flag)
     if s.camera.stereoSeparation > 0:
         ap.error("%s is not offered for stereo frames" % flag)
+
+
+def check_refine(ap, a, s):
+    """--refine, once the scene is parsed (before it is uploaded): a sample map is rendered on a mono path-traced frame."""
+    if a.refine is None:
+        return
+    if not s.settings.gi:
+        ap.error("--refine needs a path-traced scene (gi on)")
+    if s.camera.stereoSeparation > 0:
+        ap.error("--refine is not offered for stereo frames")
 
 
 def save_components(path, direct, indirect, noise_direct, noise_indirect, samples, seed):
@@ -236,6 +268,7 @@ def main(argv=None):
     if a.yaw_step is None:
         a.yaw_step = 0.0 if a.move else 1.0
     check_components(ap, a, s)
+    check_refine(ap, a, s)
     state = load_accumulation(ap, a, s) if a.accumulate else None
     s.beginRender(a.device)
     if a.probe:
@@ -276,7 +309,26 @@ def main(argv=None):
                 move_nodes(s, a.move)           # the generator renders the next frame when it is asked for it: after this edit
         print("Rendered %d frames in %.2fs" % (a.frames, time.time() - t0))
         return 0
-    if a.denoise and a.split:
+    if a.refine is not None:
+        from . import denoise_signal
+        img, state, noise, info = s.refine(state, a.refine, a.max_spp, passes=a.refine_passes, seed=a.seed)
+        held = state.count_plane()
+        st = info
+        print(json.dumps({"passes": info["passes"], "samples": info["samples"], "mean_spp": float(held.mean()), "min_spp": int(held.min()),
+                          "max_spp": int(held.max())}))
+        spp_text = "refined to tolerance %g, mean %.2f spp" % (a.refine, held.mean())
+        if a.accumulate:
+            print("wrote", state.save(a.accumulate))
+        if a.noise_out:
+            np.save(a.noise_out, noise)
+            print("wrote", a.noise_out)
+        if a.denoise:
+            feat = s.render_features(min(a.feature_samples, max(int(held.max()), 1)), seed=a.seed)
+            if a.features_out:
+                np.save(a.features_out, feat)
+            img = denoise_signal(img, noise, feat, demodulate=0)
+            spp_text += ", denoised with its own noise estimate"
+    elif a.denoise and a.split:
         img, raw, info = s.render_denoised_split(seed=a.seed, feature_samples=a.feature_samples)
         st = info["render"]
         spp_text = "%d spp, direct and indirect light denoised apart: features %.1f ms, filters %.1f + %.1f ms" % (

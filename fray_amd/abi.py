@@ -183,6 +183,16 @@ class Samples(C.Structure):
     _fields_ = [("sample_first", i32), ("sample_count", i32), ("samples_done", i32), ("_pad", i32)]
 
 
+class SamplesMap(C.Structure):
+    _fields_ = [("samples", u64), ("count_min", i32), ("count_max", i32)]
+
+
+# struct frayhip_sample_map (a struct tag without a typedef, as frayhip_denoise: the name is also the entry point's)
+class SampleMap(C.Structure):
+    _fields_ = [("tolerance", C.c_float), ("lum_floor", C.c_float), ("min_count", i32), ("max_count", i32), ("max_add", i32), ("grow", i32),
+                ("pixels", u64), ("samples", u64)]
+
+
 # struct frayhip_denoise (a struct tag without a typedef: the name is also the entry point's, so it is not in STRUCTS, which mirrors the typedefs)
 class Denoise(C.Structure):
     _fields_ = [("levels", i32), ("demodulate", i32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float),
@@ -222,7 +232,7 @@ STRUCTS = {"frayhip_transform": Transform, "frayhip_geom_ref": GeomRef, "frayhip
            "frayhip_scene_desc": SceneDesc, "frayhip_frame": Frame, "frayhip_stats": Stats,
            "frayhip_progress": Progress, "frayhip_progressive": Progressive,
            "frayhip_shade_request": ShadeRequest, "frayhip_adaptive": Adaptive, "frayhip_samples": Samples,
-           "frayhip_view": View}
+           "frayhip_view": View, "frayhip_samples_map": SamplesMap}
 
 # Every symbol include/frayhip.h declares: name -> (restype, argtypes)
 VP = C.c_void_p
@@ -255,6 +265,11 @@ SYMBOLS = {
     "frayhip_render_samples_device": (C.c_int, [VP, P(Frame), P(Samples), P(Progressive), VP, VP, VP, VP, P(Stats)]),
     "frayhip_render_components": (C.c_int, [VP, P(Frame), P(Samples), P(Progressive), VP, VP, VP, VP, VP, VP, P(Stats)]),
     "frayhip_render_components_device": (C.c_int, [VP, P(Frame), P(Samples), P(Progressive), VP, VP, VP, VP, VP, VP, VP, P(Stats)]),
+    "frayhip_render_samples_map": (C.c_int, [VP, P(Frame), P(SamplesMap), VP, VP, VP, VP, VP, P(Stats)]),
+    "frayhip_render_samples_map_device": (C.c_int, [VP, P(Frame), P(SamplesMap), VP, VP, VP, VP, VP, VP, P(Stats)]),
+    "frayhip_sample_map_defaults": (C.c_int, [P(SampleMap)]),
+    "frayhip_sample_map": (C.c_int, [C.c_int, C.c_int, VP, VP, P(SampleMap), VP, P(Stats)]),
+    "frayhip_sample_map_device": (C.c_int, [C.c_int, C.c_int, VP, VP, P(SampleMap), VP, VP, P(Stats)]),
     "frayhip_render_features": (C.c_int, [VP, P(Frame), C.c_int, VP, P(Stats)]),
     "frayhip_render_features_device": (C.c_int, [VP, P(Frame), C.c_int, VP, VP, P(Stats)]),
     "frayhip_render_features_motion": (C.c_int, [VP, P(Frame), C.c_int, P(Transform), C.c_int, VP, VP, P(Stats)]),

@@ -116,10 +116,11 @@ int frayhip_sizeof(const char* n)
     FRAYHIP_SZ(frayhip_layer) FRAYHIP_SZ(frayhip_light) FRAYHIP_SZ(frayhip_camera) FRAYHIP_SZ(frayhip_settings)
     FRAYHIP_SZ(frayhip_environment) FRAYHIP_SZ(frayhip_scene_desc) FRAYHIP_SZ(frayhip_frame) FRAYHIP_SZ(frayhip_stats)
     FRAYHIP_SZ(frayhip_progress) FRAYHIP_SZ(frayhip_progressive) FRAYHIP_SZ(frayhip_shade_request) FRAYHIP_SZ(frayhip_adaptive) FRAYHIP_SZ(frayhip_samples)
-    FRAYHIP_SZ(frayhip_view)
+    FRAYHIP_SZ(frayhip_view) FRAYHIP_SZ(frayhip_samples_map)
     if (!strcmp(n, "frayhip_denoise")) return (int)sizeof(struct frayhip_denoise);   // a struct tag: the name is also a function's
     if (!strcmp(n, "frayhip_temporal")) return (int)sizeof(struct frayhip_temporal);
     if (!strcmp(n, "frayhip_change")) return (int)sizeof(struct frayhip_change);
+    if (!strcmp(n, "frayhip_sample_map")) return (int)sizeof(struct frayhip_sample_map);
 #undef FRAYHIP_SZ
     return -1;
 }

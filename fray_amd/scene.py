@@ -302,6 +302,64 @@ def change_frame(before, after, motion=None, stats=False, stream=None, radius=3,
     return (out, st.as_dict()) if stats else out
 
 
+_SAMPLE_MAP_FIELDS = ("tolerance", "lum_floor", "min_count", "max_count", "max_add", "grow")
+_MAX_COUNT = 1 << 24
+
+
+def sample_map_params(**params):
+    """frayhip_sample_map_defaults, with the named fields replaced (tolerance, lum_floor, min_count, max_count, max_add, grow), checked as the
+    library checks them (ValueError).  max_count has no default: the caller sets it."""
+    p = abi.SampleMap()
+    _check(lib.frayhip_sample_map_defaults(C.byref(p)))
+    for k, v in params.items():
+        if k not in _SAMPLE_MAP_FIELDS:
+            raise TypeError("sample_map: unknown parameter %r (known: %s)" % (k, ", ".join(_SAMPLE_MAP_FIELDS)))
+        setattr(p, k, float(v) if k in ("tolerance", "lum_floor") else int(v))
+    if "max_count" not in params:
+        raise ValueError("sample_map: max_count must be given (it has no default)")
+    for k in ("tolerance", "lum_floor"):
+        v = float(params.get(k, getattr(p, k)))
+        if not (math.isfinite(v) and v > 0):
+            raise ValueError("sample_map: %s must be finite and > 0, got %r" % (k, v))
+    if p.min_count < 1:
+        raise ValueError("sample_map: min_count must be >= 1, got %d" % p.min_count)
+    if not (p.min_count <= p.max_count <= _MAX_COUNT):
+        raise ValueError("sample_map: max_count must be min_count .. 2^24, got %d (min_count %d)" % (p.max_count, p.min_count))
+    if p.max_add < 1:
+        raise ValueError("sample_map: max_add must be >= 1, got %d" % p.max_add)
+    if not (2 <= p.grow <= 16):
+        raise ValueError("sample_map: grow must be 2..16, got %d" % p.grow)
+    return p
+
+
+def sample_map(state, stats=False, stream=None, **params):
+    """The sample map of a state (frayhip_sample_map): how many more samples each pixel of the Accumulation `state` needs before the standard error
+    of its mean's luminance is `tolerance` times that luminance, every pixel brought to min_count first and none past max_count (params: see
+    sample_map_params; the formula is in include/frayhip.h "sample maps").  A numpy state goes through the host entry, a state on the GPU through
+    the device entry, on `stream` (None: the current stream).  Returns (add, info): add int32 [H, W] of the state's kind -- what
+    Scene.render_samples_map takes -- and info {"pixels": pixels with add > 0, "samples": the sum of add}, both over the whole frame, with
+    "stats" (ms_total, ms_kernels) when stats=True."""
+    who = "sample_map"
+    if not isinstance(state, Accumulation):
+        raise TypeError("%s: state must be an Accumulation, got %s" % (who, type(state).__name__))
+    p = sample_map_params(**params)
+    state.check(who, state.size, state.seed, state.bucket_first, state.bucket_stride)
+    W, H = state.size
+    count = state.count_plane()
+    st = abi.Stats()
+    if not state.on_device:
+        add = np.zeros((H, W), np.int32)
+        _check(lib.frayhip_sample_map(W, H, _ptr(state.state), _ptr(count), C.byref(p), _ptr(add), C.byref(st)))
+    else:
+        with _DeviceCall(state.state.device, stream) as call:
+            add = call.torch.zeros((H, W), dtype=call.torch.int32, device=state.state.device)
+            _check(lib.frayhip_sample_map_device(W, H, _ptr(state.state), _ptr(count), C.byref(p), _ptr(add), call.handle, C.byref(st)))
+    info = {"pixels": int(p.pixels), "samples": int(p.samples)}
+    if stats:
+        info["stats"] = st.as_dict()
+    return add, info
+
+
 def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, stream=None, motion=None, change=None, **params):
     """The temporal stage of include/frayhip.h (frayhip_temporal_accumulate): rgb [H, W, 3] and feat [H, W, 10] of the current frame, prev_view
     (view_from_camera of the previous frame's camera) and hist_in [H, W, 12] (the previous call's history), both None for the first frame;
@@ -515,10 +573,13 @@ class Accumulation:
     """The state of a resumable frame (include/frayhip.h "resumable frames"): `state`, float32 [H, W, 4] -- per pixel the FP32 sum of its samples'
     colours and the second moment of their luminance -- as a numpy array (Scene.render_samples then goes through the host entry) or a torch tensor
     on the GPU (the device entry); `samples_done`, the samples per pixel it holds; and what it belongs to: `seed`, `size` (W, H) and the bucket
-    share (`bucket_first`, `bucket_stride`) that was rendered into it.  The scene, its view and its settings are the caller's to keep unchanged."""
+    share (`bucket_first`, `bucket_stride`) that was rendered into it.  The scene, its view and its settings are the caller's to keep unchanged.
+    `counts`: None while every pixel holds `samples_done` samples; after Scene.render_samples_map has given the pixels different numbers, the int32
+    [H, W] plane (of the state's kind) of how many each one holds, and samples_done is then the smallest of them."""
 
-    def __init__(self, state, samples_done=0, seed=42, size=None, bucket_first=0, bucket_stride=1):
+    def __init__(self, state, samples_done=0, seed=42, size=None, bucket_first=0, bucket_stride=1, counts=None):
         self.state = state
+        self.counts = counts
         self.samples_done = int(samples_done)
         self.seed = int(seed) & 0xffffffff
         self.size = (int(size[0]), int(size[1])) if size is not None else (int(state.shape[1]), int(state.shape[0]))
@@ -559,15 +620,47 @@ class Accumulation:
             ok = isinstance(st, np.ndarray) and st.dtype == np.float32 and st.flags.c_contiguous and st.flags.writeable
         if not ok or tuple(st.shape) != (H, W, abi.ACCUM_CHANNELS):
             raise ValueError("%s: the state must be a contiguous float32 numpy array or GPU torch tensor shaped %s" % (who, (H, W, abi.ACCUM_CHANNELS)))
+        ct = self.counts
+        if ct is not None:
+            if self.on_device:
+                ok = _torch_tensor(ct) and ct.is_cuda and ct.dtype == torch.int32 and ct.is_contiguous() and ct.device == st.device
+            else:
+                ok = isinstance(ct, np.ndarray) and ct.dtype == np.int32 and ct.flags.c_contiguous and ct.flags.writeable
+            if not ok or tuple(ct.shape) != (H, W):
+                raise ValueError("%s: the state's counts must be a contiguous int32 plane of the state's kind shaped %s" % (who, (H, W)))
+
+    def count_plane(self):
+        """The per-pixel sample counts as an int32 [H, W] plane of the state's kind: `counts`, or a new plane of samples_done everywhere."""
+        if self.counts is not None:
+            return self.counts
+        W, H = self.size
+        if self.on_device:
+            import torch
+            return torch.full((H, W), self.samples_done, dtype=torch.int32, device=self.state.device)
+        return np.full((H, W), self.samples_done, np.int32)
+
+    def require_uniform(self, who):
+        """For the calls that add the same number of samples to every pixel: a counts plane that holds one value collapses back to samples_done;
+        one that does not is refused (ValueError)."""
+        if self.counts is None:
+            return
+        lo, hi = int(self.counts.min()), int(self.counts.max())
+        if lo != hi:
+            raise ValueError("%s: the state's pixels hold different numbers of samples (%d .. %d, Scene.render_samples_map); only "
+                             "render_samples_map can continue it" % (who, lo, hi))
+        self.samples_done, self.counts = lo, None
 
     def save(self, path):
         """Writes the state in .npz format to `path` as it is given (a tensor is copied to the host); load() reads it back as a numpy state.
         Returns the path."""
         path = os.fspath(path)
         arr = self.state.cpu().numpy() if self.on_device else self.state
+        extra = {}
+        if self.counts is not None:          # only a state with per-pixel counts carries the plane: files of uniform states stay as they were
+            extra["counts"] = self.counts.cpu().numpy() if self.on_device else self.counts
         with open(path, "wb") as f:
             np.savez(f, state=arr, samples_done=np.int64(self.samples_done), seed=np.uint32(self.seed), size=np.array(self.size, np.int64),
-                     share=np.array([self.bucket_first, self.bucket_stride], np.int64))
+                     share=np.array([self.bucket_first, self.bucket_stride], np.int64), **extra)
         return path
 
     @classmethod
@@ -577,7 +670,9 @@ class Accumulation:
             if missing:
                 raise ValueError("Accumulation.load: %s is not a saved state (no %s)" % (path, ", ".join(missing)))
             state = np.ascontiguousarray(z["state"], dtype=np.float32)
-            return cls(state, int(z["samples_done"]), int(z["seed"]), tuple(int(v) for v in z["size"]), int(z["share"][0]), int(z["share"][1]))
+            counts = np.ascontiguousarray(z["counts"], dtype=np.int32) if "counts" in z.files else None
+            return cls(state, int(z["samples_done"]), int(z["seed"]), tuple(int(v) for v in z["size"]), int(z["share"][0]), int(z["share"][1]),
+                       counts)
 
 
 class Scene:
@@ -892,6 +987,7 @@ class Scene:
         elif not isinstance(state, Accumulation):
             raise TypeError("%s: state must be an Accumulation, got %s" % (who, type(state).__name__))
         state.check(who, (W, H), seed, bucket_first, bucket_stride)
+        state.require_uniform(who)
         self._need_dev()
         st = abi.Stats()
         fr = self._frame(abi.MODE_RENDER, state.seed, bucket_first, bucket_stride, spp_chunk, stats)
@@ -949,6 +1045,7 @@ class Scene:
         sd, si = state
         for a in (sd, si):
             a.check(who, (W, H), seed, bucket_first, bucket_stride)
+            a.require_uniform(who)
         if sd is si or sd.state is si.state:
             raise ValueError("%s: the direct and the indirect state are the same object" % who)
         if sd.on_device != si.on_device:
@@ -986,6 +1083,83 @@ class Scene:
             info = st.as_dict()
         out = (rgb[0], rgb[1], state) + ((var[0], var[1]) if noise else ())
         return out + ((info,) if (stats or progress is not None) else ())
+
+    # ---- sample maps (include/frayhip.h "sample maps") ----
+    def render_samples_map(self, add, state=None, seed=42, bucket_first=0, bucket_stride=1, spp_chunk=0, stats=False, noise=False, stream=None):
+        """Adds add[y, x] more samples to each pixel of a frame (frayhip_render_samples_map): pixel p's samples count[p] .. count[p] + add[p] - 1,
+        where count is what the state holds of it.  add: int32 [H, W], >= 0, of the state's kind (numpy: the host entry; a GPU tensor: the device
+        entry, on `stream`); state: an Accumulation, or None to start a numpy one.  Mono path-traced frames only.
+
+        Returns (rgb, state[, noise][, stats]) as render_samples.  Every pixel of the call's buckets is, bit for bit, that pixel of render() at the
+        number of samples it now holds; one that holds none is (0, 0, 0) with noise 0.  The state is updated in place: while its pixels hold
+        different numbers, state.counts is their int32 plane and only this call can continue the state; once they agree again it collapses
+        back to samples_done.  stats["samples"] is the sum of add over the call's pixels."""
+        who = "render_samples_map"
+        W, H = self.frame_size
+        if state is None:
+            state = Accumulation.empty((W, H), seed, bucket_first, bucket_stride)
+        elif not isinstance(state, Accumulation):
+            raise TypeError("%s: state must be an Accumulation, got %s" % (who, type(state).__name__))
+        state.check(who, (W, H), seed, bucket_first, bucket_stride)
+        if _torch_tensor(add) != state.on_device:
+            raise TypeError("%s: add must be of the state's kind (a numpy array for a numpy state, a GPU tensor for a state on the GPU)" % who)
+        if state.on_device:
+            import torch
+            if not add.is_cuda or add.device != state.state.device or add.dtype != torch.int32:
+                raise TypeError("%s: add must be an int32 tensor on the state's device" % who)
+            add = add.contiguous()
+        else:
+            add = np.asarray(add)
+            if add.dtype != np.int32:
+                raise TypeError("%s: add must be int32, got %s" % (who, add.dtype))
+            add = np.ascontiguousarray(add)
+        if tuple(add.shape) != (H, W):
+            raise ValueError("%s: add must be shaped %s, got %s" % (who, (H, W), tuple(add.shape)))
+        self._need_dev()
+        count = state.count_plane()
+        st = abi.Stats()
+        fr = self._frame(abi.MODE_RENDER, state.seed, bucket_first, bucket_stride, spp_chunk, stats)
+        req = abi.SamplesMap()
+        if not state.on_device:
+            rgb = np.zeros((H, W, 3), np.float32)
+            var = np.zeros((H, W), np.float32) if noise else None
+            _check(lib.frayhip_render_samples_map(self._dev, C.byref(fr), C.byref(req), _ptr(state.state), _ptr(count), _ptr(add), _ptr(rgb), _ptr(var),
+                                                  C.byref(st)))
+        else:
+            with _DeviceCall(state.state.device, stream) as call:
+                rgb = call.torch.zeros((H, W, 3), dtype=call.torch.float32, device=state.state.device)
+                var = call.torch.zeros((H, W), dtype=call.torch.float32, device=state.state.device) if noise else None
+                _check(lib.frayhip_render_samples_map_device(self._dev, C.byref(fr), C.byref(req), _ptr(state.state), _ptr(count), _ptr(add), _ptr(rgb),
+                                                             _ptr(var), call.handle, C.byref(st)))
+        state.samples_done = req.count_min
+        state.counts = None if req.count_min == req.count_max else count
+        out = (rgb, state) + ((var,) if noise else ())
+        return out + ((st.as_dict(),) if stats else ())
+
+    def refine(self, state, tolerance, max_count, passes=8, seed=42, bucket_first=0, bucket_stride=1, spp_chunk=0, stream=None, **params):
+        """Spends samples where the frame needs them: up to `passes` times, sample_map(state, tolerance=..., max_count=..., **params) and
+        render_samples_map of its map; stops when a map is empty.  state: an Accumulation (None starts a numpy one; the first pass then brings
+        every pixel to min_count).  Returns (rgb, state, noise, info): the frame, the state, the variance estimate of the mean's luminance --
+        denoise_signal's `variance` with demodulate=0 -- and info {"passes": passes that rendered, "samples": samples they added, "ms_kernels":
+        their kernel time}."""
+        W, H = self.frame_size
+        if state is None:
+            state = Accumulation.empty((W, H), seed, bucket_first, bucket_stride)
+        done = {"passes": 0, "samples": 0, "ms_kernels": 0.0}
+        rgb = noise = None
+        for _ in range(int(passes)):
+            add, info = sample_map(state, stream=stream, tolerance=tolerance, max_count=max_count, **params)
+            if info["pixels"] == 0:
+                break
+            rgb, state, noise, st = self.render_samples_map(add, state, seed, bucket_first, bucket_stride, spp_chunk, stats=True, noise=True, stream=stream)
+            if st["samples"] == 0:          # the map's pixels all lie outside the call's buckets
+                break
+            done["passes"] += 1
+            done["samples"] += int(st["samples"])
+            done["ms_kernels"] += st["ms_kernels"]
+        if rgb is None:                     # nothing to add: the frame of what the state holds
+            rgb, state, noise = self.render_samples_map(state.count_plane() * 0, state, seed, bucket_first, bucket_stride, spp_chunk, noise=True, stream=stream)
+        return rgb, state, noise, done
 
     # ---- adaptive frames (include/frayhip.h "adaptive frames") ----
     def _adaptive_request(self, threshold, min_spp, err_floor):

@@ -709,6 +709,89 @@ int  frayhip_render_components_device(frayhip_scene* s, const frayhip_frame* f, 
                                       float* d_accum_direct, float* d_accum_indirect, float* d_rgb_direct, float* d_rgb_indirect,
                                       float* d_noise_direct, float* d_noise_indirect, void* hip_stream, frayhip_stats* st);
 
+/* ---- sample maps (per-pixel sample counts on a resumable frame) ---------------------------------------------------------------------------------
+ * frayhip_render_samples gives every pixel of the call's buckets the same number of samples; here the caller says how many more each pixel gets.
+ * For a mono, path-traced frame (settings.gi on, camera.stereoSeparation == 0).  accum is frayhip_render_samples' state (W*H rows {sum.r, sum.g,
+ * sum.b, m2}); count (W*H int32, in/out) says how many samples each pixel's row holds; add (W*H int32, in) how many more it gets.
+ *
+ * Per pixel p of the call's buckets (frame.bucket_first / bucket_stride, as frayhip_render), n = count[p], a = add[p]:
+ *   a > 0   the pixel's samples n .. n + a - 1 -- the (seed, pixel, sample) samples frayhip_render and frayhip_render_samples trace -- are added to
+ *           its row in sample order with that entry's arithmetic (a sample's terms folded innermost first, sum = sum + c, l = ((c.r + c.g) + c.b)
+ *           / 3.0f, m2 = m2 + l * l).  With n == 0 the row's contents are ignored and it starts at (0, 0, 0, 0).  Then count[p] = n + a.
+ *   a == 0  row and count are untouched.
+ *   After the call the row IS the row frayhip_render_samples produces for samples 0 .. N-1, N = count[p], bit for bit, however the samples were
+ *   cut into map calls, uniform calls and batches; the caller's word about what the row held before is trusted, as there.
+ * rgb (W*H*3) and noise (W*H), both optional, are written for EVERY pixel of the call's buckets, with frayhip_render_samples' formulas and the
+ *   pixel's own N: rgb = sum / (float)N (= frayhip_render at N samples per pixel, bit for bit) and the noise estimate given there.  A pixel with
+ *   N == 0 knows nothing: it gets rgb (0, 0, 0) and noise 0 -- give every pixel a sample before the frame is shown or denoised.
+ * Pixels outside the call's buckets are untouched in accum, count, rgb and noise, and their add is not read.
+ * Independence: no bit depends on frame.spp_chunk (the most samples of a pixel in one batch; 0 = auto), on the options pt_budget_mib or
+ *   pt_lanes, on the order or composition of waves, or on the handle's call history.  All work of a call runs on one stream.
+ * Arithmetic: always the exact kernels, as adaptive frames: option fp_contract does not apply and "contracted_launches" reads 0 afterwards.
+ * Seed table: neither read nor altered, as a frayhip_render_samples call with sample_first > 0.
+ * Black frames: with maxTraceDepth < 0 the call adds +0 for each sample, and the samples are counted.
+ * A call whose add is zero in all its pixels launches no tracing kernel and returns FRAYHIP_OK with samples == 0 (rgb and noise are still written).
+ * How it runs: layers of at most cn samples per pixel (cn from the work budget or spp_chunk).  The layer at offset k0 lists the pixels with
+ *   add > k0; entry i takes min(cn, add_i - k0) samples, and an exclusive scan of these gives every entry a contiguous range of path slots, so a
+ *   batch is dense: no path is traced for a sample nobody asked for, and the number of launches does not grow with the number of distinct values
+ *   in add.  Kernels: k_map_init, k_map_count / k_compact_scan / k_map_offsets, k_map_expand, k_seed_map, k_pt_init_map, the frame's k_meta_dense,
+ *   k_pt_bounce / k_scan / k_pt_shadow, k_map_fold, k_map_resolve, k_map_flag / k_compact_*, k_map_finish (samplemap_variant.hip).
+ * *st as frayhip_render_adaptive: ms_total, ms_kernels, samples (== m->samples, with or without FRAYHIP_FRAME_STATS), ms_trace / trace_launches,
+ *   ms_shadow / shadow_launches and, with the flag, the work counters of this call's samples only.
+ * The host entry copies accum, count and add in (rgb and noise too when the call renders a subset of the buckets) and accum, count, rgb and noise
+ *   out.  The _device entry takes DEVICE pointers -- d_accum 16-byte aligned, the others 4-byte -- and follows frayhip_render_device's stream
+ *   contract.
+ * FRAYHIP_E_ARG, with the entry's name in frayhip_last_error(): a NULL scene, frame, request, accum, count or add; mode != FRAYHIP_MODE_RENDER;
+ *   bucket arguments that frayhip_render refuses; any overlap among the five buffers; a misaligned device pointer; a call on a scene whose frame
+ *   is being rendered; and any add[p] < 0, count[p] < 0 or count[p] + add[p] > 2^24 in the call's buckets.  The host entry checks the planes
+ *   before it touches the device; the device entry checks them in its first kernel and returns with nothing written.
+ * FRAYHIP_E_UNSUPPORTED: gi off (Whitted), stereo and long generators (maxTraceDepth >= 20), for frayhip_render_adaptive's reasons.
+ * Not offered: component (direct / indirect) states under a map, a sample budget normalised over the frame, progress callbacks and cancel. */
+typedef struct frayhip_samples_map {
+    uint64_t samples;        /* out: sum of add over the pixels the call rendered                               */
+    int32_t  count_min;      /* out: smallest and largest count after the call among the pixels of the call's   */
+    int32_t  count_max;      /*      buckets (0, 0 when the call has no pixel)                                  */
+} frayhip_samples_map;
+
+int  frayhip_render_samples_map(frayhip_scene* s, const frayhip_frame* f, frayhip_samples_map* m, float* accum, int32_t* count,
+                                const int32_t* add, float* rgb, float* noise, frayhip_stats* st);
+int  frayhip_render_samples_map_device(frayhip_scene* s, const frayhip_frame* f, frayhip_samples_map* m, float* d_accum, int32_t* d_count,
+                                       const int32_t* d_add, float* d_rgb, float* d_noise, void* hip_stream, frayhip_stats* st);
+
+/* The map from a state (scene-free, one kernel: k_sample_map, samplemap.hip): how many more samples each pixel needs before the standard error
+ * of its mean's luminance is `tolerance` times that luminance (or times lum_floor, for a dark pixel).  FP32 throughout, no contraction
+ * (tests/sample_map_ref.py restates it in numpy).  Per pixel, N = count[p], over all W*H pixels:
+ *       N >= max_count:  add = 0
+ *       N <  min_count:  target = min_count
+ *       else  mean = sum / (float)N;  lbar = ((mean.r + mean.g) + mean.b) / 3.0f
+ *             v = fmaxf(0, m2 / (float)N - lbar * lbar);  noise = N >= 2 ? v / (float)(N - 1) : lbar * lbar
+ *             ref = fmaxf(lbar, lum_floor);  t = tolerance * ref;  need = ceilf((float)N * (noise / (t * t)))
+ *             target = need <= (float)max_count ? max(N, (int)need) : max_count       (a NaN need asks for max_count: never stops a pixel early)
+ *             target = min(target, grow * N)
+ *       add = min(min(target, max_count) - N, max_add)
+ *   grow bounds how far one pass trusts an estimate made from N samples; 2 is a maintainer's choice, not a measurement.
+ * pixels = the number of pixels with add > 0 and samples = the sum of add, over all W*H pixels: a caller who renders a bucket share ignores the
+ *   rest, as frayhip_render_samples_map does.
+ * Device pointers: accum 16-byte aligned, count and add 4-byte; the stream contract and *st (ms_total, ms_kernels) as frayhip_change_frame_device.
+ * FRAYHIP_E_ARG, before the device is touched: width or height < 1 or W*H > 2^30; a NULL pointer; a tolerance or lum_floor that is not finite and
+ *   > 0; min_count < 1, max_count < min_count or > 2^24; max_add < 1; grow outside 2..16; overlapping buffers; a misaligned device pointer. */
+/* A struct tag without a typedef, as frayhip_denoise. */
+struct frayhip_sample_map {
+    float    tolerance;      /* in:  relative standard error aimed at; finite and > 0, default 0.05                      */
+    float    lum_floor;      /* in:  the luminance a dark pixel's error is measured against; finite and > 0, default 0.01 */
+    int32_t  min_count;      /* in:  every pixel is brought to this count first; 1 <= min_count <= max_count, default 4   */
+    int32_t  max_count;      /* in:  no pixel goes past it; <= 2^24; no default (0): the caller sets it                   */
+    int32_t  max_add;        /* in:  the most one map gives a pixel; >= 1, default 2^24                                   */
+    int32_t  grow;           /* in:  a pixel's target is at most grow * N; 2..16, default 2                               */
+    uint64_t pixels;         /* out: pixels with add > 0                                                                  */
+    uint64_t samples;        /* out: the sum of add                                                                       */
+};
+int  frayhip_sample_map_defaults(struct frayhip_sample_map* p);
+int  frayhip_sample_map(int width, int height, const float* accum, const int32_t* count, struct frayhip_sample_map* p, int32_t* add,
+                        frayhip_stats* st);
+int  frayhip_sample_map_device(int width, int height, const float* d_accum, const int32_t* d_count, struct frayhip_sample_map* p,
+                               int32_t* d_add, void* hip_stream, frayhip_stats* st);
+
 /* ---- feature frames (first-hit guides for a denoiser) ---------------------------------------------------------------------------------------
  * For every pixel of the call's buckets (frame.bucket_first / bucket_stride, as frayhip_render; other pixels untouched), the FP32 mean, in
  * sample order, of the first-hit features of the frame's own camera samples 0 .. n_samples - 1: sample i is the film position and the pinhole
@@ -1021,7 +1104,8 @@ int  frayhip_temporal_accumulate_split_adaptive_device(int width, int height, co
 /* Not covered: SVGF's wider 3 x 3 retry when no bilinear tap counts, feeding a filtered level back into the history, moved lights and the
  * shadows and reflections of moved objects (only a pixel's own first hit is carried back: frayhip_render_features_motion), motion blur,
  * specular motion vectors (what a mirror shows moves with the camera while its first hit does not), learned
- * denoisers, adaptive and stereo frames, and denoising across ranks (gather the frame and its features first: frayhip_gather_buckets takes a
+ * denoisers, frayhip_render_adaptive's frames (they return no variance; a state refined under a sample map does: "sample maps") and stereo frames,
+ * and denoising across ranks (gather the frame and its features first: frayhip_gather_buckets takes a
  * channel count).  With a change frame the accumulation does shorten the history under a moved light and under the shadows and reflections of
  * moved objects (the history is dropped or faded there, not carried to where the shadow went).  Still not covered with it: a moved node's own pixels entering changed light (their difference is masked: they are the motion frame's
  * business), view-dependent change under camera motion, and any tuning beyond gain. */
