@@ -29,7 +29,10 @@ src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --he
                          python -m fray_amd scene.fray -o out.bmp --refine TOL --max-spp N [--accumulate FILE.npz] [--noise-out FILE.npy] [--denoise]
                                                                                          (samples spent where the frame is noisy: each pixel sampled
                                                                                           until its relative standard error is TOL or it holds N samples;
-                                                                                          --denoise: the result filtered with its own noise estimate)"""
+                                                                                          --denoise: the result filtered with its own noise estimate)
+                         python -m fray_amd scene.fray -o out.bmp --refine TOL --max-spp N --denoise --split [--components-out FILE.npz]
+                                                                                         (the same samples kept apart as direct and indirect light
+                                                                                          under one map, each component filtered on its own, then added)"""
 import argparse
 import json
 import os
@@ -97,7 +100,8 @@ def build_parser():
                     help="refined frame (Scene.refine; path-traced mono frames): passes of a sample map and the samples it asks for, until every pixel's "
                          "relative standard error is <= TOL or the pixel holds --max-spp samples; prints one JSON line with the passes, the samples and "
                          "the mean spp.  With --accumulate the state in FILE.npz is continued and saved; with --denoise the frame goes through the "
-                         "a-trous filter with its own noise estimate as the variance (denoise_signal, demodulate=0)")
+                         "a-trous filter with its own noise estimate as the variance (denoise_signal, demodulate=0); with --denoise --split the "
+                         "samples are kept apart as direct and indirect light (Scene.render_denoised_split(refine=TOL)) and each is filtered on its own")
     ap.add_argument("--max-spp", type=int, metavar="N", help="with --refine: the most samples a pixel may hold (required)")
     ap.add_argument("--refine-passes", type=int, default=8, metavar="P", help="with --refine: the most passes (default 8)")
     ap.add_argument("--components-out", metavar="FILE.npz",
@@ -144,8 +148,12 @@ def check_args(ap, a):
             ap.error("--refine: TOL must be finite and > 0")
         if a.refine_passes < 1:
             ap.error("--refine-passes must be >= 1")
-        if a.adaptive is not None or a.probe or a.frames is not None or a.time_limit is not None or a.split or a.components_out or a.progress:
-            ap.error("--refine cannot be combined with --adaptive, --probe, --frames, --time-limit, --progress, --split or --components-out")
+        if a.adaptive is not None or a.probe or a.frames is not None or a.time_limit is not None or a.progress:
+            ap.error("--refine cannot be combined with --adaptive, --probe, --frames, --time-limit or --progress")
+        if a.components_out and not a.split:
+            ap.error("--refine with --components-out needs --denoise --split")
+        if a.split and a.noise_out:
+            ap.error("--refine --split cannot be combined with --noise-out: --components-out saves both components' noise")
     elif a.max_spp is not None:
         ap.error("--max-spp needs --refine")
     if a.frames is not None and not a.denoise and not a.move:
@@ -309,7 +317,21 @@ def main(argv=None):
                 move_nodes(s, a.move)           # the generator renders the next frame when it is asked for it: after this edit
         print("Rendered %d frames in %.2fs" % (a.frames, time.time() - t0))
         return 0
-    if a.refine is not None:
+    if a.refine is not None and a.split:
+        img, raw, info = s.render_denoised_split(seed=a.seed, feature_samples=a.feature_samples, refine=a.refine, max_count=a.max_spp,
+                                                 passes=a.refine_passes)
+        st = info["render"]
+        held = info["refine"]["counts"]
+        print(json.dumps({"passes": st["passes"], "samples": st["samples"], "mean_spp": float(held.mean()), "min_spp": int(held.min()),
+                          "max_spp": int(held.max())}))
+        spp_text = "refined to tolerance %g, mean %.2f spp, direct and indirect light denoised apart: features %.1f ms, filters %.1f + %.1f ms" % (
+            a.refine, held.mean(), info["features"]["ms_kernels"], info["denoise_direct"]["ms_kernels"], info["denoise_indirect"]["ms_kernels"])
+        if a.features_out:
+            np.save(a.features_out, info["features_frame"])
+        if a.components_out:
+            save_components(a.components_out, info["direct_rgb"], info["indirect_rgb"], info["noise_direct"], info["noise_indirect"],
+                            int(held.max()), a.seed)
+    elif a.refine is not None:
         from . import denoise_signal
         img, state, noise, info = s.refine(state, a.refine, a.max_spp, passes=a.refine_passes, seed=a.seed)
         held = state.count_plane()

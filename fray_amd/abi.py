@@ -267,9 +267,13 @@ SYMBOLS = {
     "frayhip_render_components_device": (C.c_int, [VP, P(Frame), P(Samples), P(Progressive), VP, VP, VP, VP, VP, VP, VP, P(Stats)]),
     "frayhip_render_samples_map": (C.c_int, [VP, P(Frame), P(SamplesMap), VP, VP, VP, VP, VP, P(Stats)]),
     "frayhip_render_samples_map_device": (C.c_int, [VP, P(Frame), P(SamplesMap), VP, VP, VP, VP, VP, VP, P(Stats)]),
+    "frayhip_render_components_map": (C.c_int, [VP, P(Frame), P(SamplesMap), VP, VP, VP, VP, VP, VP, VP, VP, P(Stats)]),
+    "frayhip_render_components_map_device": (C.c_int, [VP, P(Frame), P(SamplesMap), VP, VP, VP, VP, VP, VP, VP, VP, VP, P(Stats)]),
     "frayhip_sample_map_defaults": (C.c_int, [P(SampleMap)]),
     "frayhip_sample_map": (C.c_int, [C.c_int, C.c_int, VP, VP, P(SampleMap), VP, P(Stats)]),
     "frayhip_sample_map_device": (C.c_int, [C.c_int, C.c_int, VP, VP, P(SampleMap), VP, VP, P(Stats)]),
+    "frayhip_sample_map_pair": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(SampleMap), VP, P(Stats)]),
+    "frayhip_sample_map_pair_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(SampleMap), VP, VP, P(Stats)]),
     "frayhip_render_features": (C.c_int, [VP, P(Frame), C.c_int, VP, P(Stats)]),
     "frayhip_render_features_device": (C.c_int, [VP, P(Frame), C.c_int, VP, VP, P(Stats)]),
     "frayhip_render_features_motion": (C.c_int, [VP, P(Frame), C.c_int, P(Transform), C.c_int, VP, VP, P(Stats)]),

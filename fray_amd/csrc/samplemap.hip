@@ -1,10 +1,12 @@
-// C ABI, sample maps from a state (include/frayhip.h "sample maps"): frayhip_sample_map_defaults, frayhip_sample_map and its _device entry.  A
+// C ABI, sample maps from a state (include/frayhip.h "sample maps"): frayhip_sample_map_defaults, frayhip_sample_map and its _device entry, and
+// frayhip_sample_map_pair / _pair_device for a pair of component states (the two components' mean luminances and noise estimates added).  A
 // resumable state and its per-pixel sample counts go in; out comes the `add` plane of frayhip_render_samples_map: how many more samples each pixel
 // needs before the standard error of its mean's luminance is `tolerance` times that luminance.  Scene-free, FP32 throughout; the Makefile builds
 // this object as it builds denoise.o (-ffp-contract=off, correctly rounded divide), so every product below is rounded where it is written
 // (tests/sample_map_ref.py restates it in numpy, and the two agree bit for bit).
 //
-//   k_sample_map   per pixel: k_acc_mean's mean and noise at the pixel's own N, the count at which that noise would meet the tolerance, the caps
+//   k_sample_map<PAIR>   per pixel: k_acc_mean's mean and noise at the pixel's own N (PAIR: of both states, added), the count at which that noise
+//                        would meet the tolerance, the caps
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -18,6 +20,7 @@
 struct SampleMapArgs {
     size_t n;
     const float4* accum;        // one row a pixel: {sum.rgb, m2}
+    const float4* accum2;       // the indirect state of a pair (accum is then the direct one); null otherwise
     const int32_t* count;
     int32_t* add;
     float tolerance, lumFloor;
@@ -25,6 +28,16 @@ struct SampleMapArgs {
     unsigned long long* totals; // [0] pixels with add > 0, [1] the sum of add
 };
 
+// k_acc_mean's mean luminance and noise of one row at N samples
+__device__ __forceinline__ void sm_row(const float4 row, int N, float fn, float& lbar, float& noise)
+{
+    const float mr = row.x / fn, mg = row.y / fn, mb = row.z / fn;
+    lbar = tp_lum(mr, mg, mb);
+    const float v = fmaxf(0.0f, row.w / fn - lbar * lbar);
+    noise = N >= 2 ? v / (float)(N - 1) : lbar * lbar;
+}
+
+template <bool PAIR>
 static __global__ __launch_bounds__(256) void k_sample_map(SampleMapArgs A)
 {
     __shared__ unsigned long long sPix, sSum;
@@ -38,12 +51,15 @@ static __global__ __launch_bounds__(256) void k_sample_map(SampleMapArgs A)
             int target;
             if (N < A.minCount) target = A.minCount;
             else {
-                const float4 row = A.accum[p];
                 const float fn = (float)N;
-                const float mr = row.x / fn, mg = row.y / fn, mb = row.z / fn;
-                const float lbar = tp_lum(mr, mg, mb);
-                const float v = fmaxf(0.0f, row.w / fn - lbar * lbar);
-                const float noise = N >= 2 ? v / (float)(N - 1) : lbar * lbar;          // k_acc_mean's
+                float lbar, noise;
+                sm_row(A.accum[p], N, fn, lbar, noise);
+                if (PAIR) {          // the components are separate signals to the split filter, and their errors add in the final sum
+                    float lbarI, noiseI;
+                    sm_row(A.accum2[p], N, fn, lbarI, noiseI);
+                    lbar = lbar + lbarI;
+                    noise = noise + noiseI;
+                }
                 const float ref = fmaxf(lbar, A.lumFloor);
                 const float t = A.tolerance * ref;
                 const float need = ceilf(fn * (noise / (t * t)));
@@ -68,11 +84,14 @@ using namespace frayhip_temporal_detail;
 constexpr int kMaxCount = 1 << 24;
 
 // Every check of both entries, in this order; none touches the device
-int check(const char* who, int W, int H, const float* accum, const int32_t* count, const struct frayhip_sample_map* p, const int32_t* add, bool device)
+// (pair: accum is the direct state and accum2 the indirect one)
+int check(const char* who, int W, int H, const float* accum, const float* accum2, bool pair, const int32_t* count, const struct frayhip_sample_map* p,
+          const int32_t* add, bool device)
 {
     if (W < 1 || H < 1) return bad(who, "width and height must be >= 1");
     if ((long long)W * H > (1ll << 30)) return bad(who, "more than 2^30 pixels");
-    if (!accum) return bad(who, "null accum");
+    if (!accum) return bad(who, pair ? "null accum_direct" : "null accum");
+    if (pair && !accum2) return bad(who, "null accum_indirect");
     if (!count) return bad(who, "null count");
     if (!p) return bad(who, "null parameters");
     if (!add) return bad(who, "null add");
@@ -84,17 +103,24 @@ int check(const char* who, int W, int H, const float* accum, const int32_t* coun
     if (p->max_add < 1) return bad(who, "max_add must be >= 1");
     if (p->grow < 2 || p->grow > 16) return bad(who, "grow must be 2..16");
     if (device) {
-        if (misaligned(accum, 16)) return bad(who, "device pointer to the state not 16-byte aligned");
+        if (misaligned(accum, 16) || (pair && misaligned(accum2, 16))) return bad(who, "device pointer to the state not 16-byte aligned");
         if (misaligned(count, 4) || misaligned(add, 4)) return bad(who, "device pointer to a plane not 4-byte aligned");
     }
     const size_t n = (size_t)W * H;
     if (overlaps(add, 4 * n, accum, 16 * n) || overlaps(add, 4 * n, count, 4 * n)) return bad(who, "add must not overlap an input");
+    if (pair) {
+        if (overlaps(add, 4 * n, accum2, 16 * n)) return bad(who, "add must not overlap an input");
+        if (overlaps(accum2, 16 * n, accum, 16 * n)) return bad(who, "accum_indirect must not overlap accum_direct");
+        if (overlaps(count, 4 * n, accum, 16 * n)) return bad(who, "count must not overlap accum_direct");
+        if (overlaps(count, 4 * n, accum2, 16 * n)) return bad(who, "count must not overlap accum_indirect");
+        return FRAYHIP_OK;
+    }
     if (overlaps(count, 4 * n, accum, 16 * n)) return bad(who, "count must not overlap accum");
     return FRAYHIP_OK;
 }
 
 // The device path of both entries (device pointers, checked).  A negative count is read as a pixel below min_count.
-int run(int W, int H, const float* accum, const int32_t* count, struct frayhip_sample_map* p, int32_t* add, hipStream_t stream, frayhip_stats* st,
+int run(int W, int H, const float* accum, const float* accum2, const int32_t* count, struct frayhip_sample_map* p, int32_t* add, hipStream_t stream, frayhip_stats* st,
         std::chrono::steady_clock::time_point t0)
 {
     struct Totals {
@@ -104,7 +130,7 @@ int run(int W, int H, const float* accum, const int32_t* count, struct frayhip_s
     HIP_TRY(hipMalloc((void**)&totals.d, 16));
     SampleMapArgs A{};
     A.n = (size_t)W * H;
-    A.accum = (const float4*)accum; A.count = count; A.add = add;
+    A.accum = (const float4*)accum; A.accum2 = (const float4*)accum2; A.count = count; A.add = add;
     A.tolerance = p->tolerance; A.lumFloor = p->lum_floor;
     A.minCount = p->min_count; A.maxCount = p->max_count; A.maxAdd = p->max_add; A.grow = p->grow;
     A.totals = totals.d;
@@ -114,7 +140,8 @@ int run(int W, int H, const float* accum, const int32_t* count, struct frayhip_s
     struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{stream};
     HIP_TRY(hipMemsetAsync(totals.d, 0, 16, stream));
     HIP_TRY(hipEventRecord(E.a, stream));
-    hipLaunchKernelGGL(k_sample_map, dim3(grid_for(A.n)), dim3(256), 0, stream, A);
+    if (accum2) hipLaunchKernelGGL(k_sample_map<true>, dim3(grid_for(A.n)), dim3(256), 0, stream, A);
+    else hipLaunchKernelGGL(k_sample_map<false>, dim3(grid_for(A.n)), dim3(256), 0, stream, A);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(E.b, stream));
     unsigned long long h[2] = {0, 0};
@@ -156,15 +183,15 @@ int frayhip_sample_map_device(int width, int height, const float* d_accum, const
                               frayhip_stats* st)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    if (const int rc = check("frayhip_sample_map_device", width, height, d_accum, d_count, p, d_add, true)) return rc;
-    return run(width, height, d_accum, d_count, p, d_add, (hipStream_t)hip_stream, st, t0);
+    if (const int rc = check("frayhip_sample_map_device", width, height, d_accum, nullptr, false, d_count, p, d_add, true)) return rc;
+    return run(width, height, d_accum, nullptr, d_count, p, d_add, (hipStream_t)hip_stream, st, t0);
 }
 
 int frayhip_sample_map(int width, int height, const float* accum, const int32_t* count, struct frayhip_sample_map* p, int32_t* add, frayhip_stats* st)
 {
     const auto t0 = std::chrono::steady_clock::now();
     const char* who = "frayhip_sample_map";
-    if (const int rc = check(who, width, height, accum, count, p, add, false)) return rc;
+    if (const int rc = check(who, width, height, accum, nullptr, false, count, p, add, false)) return rc;
     const size_t n = (size_t)width * height;
     // one allocation, the 16-byte rows first: the state, the counts, then add
     DeviceArrays B(std::string(who) + ": out of device memory");
@@ -174,7 +201,38 @@ int frayhip_sample_map(int width, int height, const float* accum, const int32_t*
     int32_t* d_add = d_count + n;
     HIP_TRY(hipMemcpy(d_accum, accum, n * 16, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_count, count, n * 4, hipMemcpyHostToDevice));
-    if (const int rc = run(width, height, d_accum, d_count, p, d_add, nullptr, st, t0)) return rc;
+    if (const int rc = run(width, height, d_accum, nullptr, d_count, p, d_add, nullptr, st, t0)) return rc;
+    HIP_TRY(hipMemcpy(add, d_add, n * 4, hipMemcpyDeviceToHost));
+    if (st) st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return FRAYHIP_OK;
+}
+
+int frayhip_sample_map_pair_device(int width, int height, const float* d_accum_direct, const float* d_accum_indirect, const int32_t* d_count,
+                                   struct frayhip_sample_map* p, int32_t* d_add, void* hip_stream, frayhip_stats* st)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (const int rc = check("frayhip_sample_map_pair_device", width, height, d_accum_direct, d_accum_indirect, true, d_count, p, d_add, true)) return rc;
+    return run(width, height, d_accum_direct, d_accum_indirect, d_count, p, d_add, (hipStream_t)hip_stream, st, t0);
+}
+
+int frayhip_sample_map_pair(int width, int height, const float* accum_direct, const float* accum_indirect, const int32_t* count, struct frayhip_sample_map* p,
+                            int32_t* add, frayhip_stats* st)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const char* who = "frayhip_sample_map_pair";
+    if (const int rc = check(who, width, height, accum_direct, accum_indirect, true, count, p, add, false)) return rc;
+    const size_t n = (size_t)width * height;
+    // one allocation, the 16-byte rows first: the two states, the counts, then add
+    DeviceArrays B(std::string(who) + ": out of device memory");
+    float* d_direct;
+    if (const int rc = B.alloc(d_direct, n * 10)) return rc;
+    float* d_indirect = d_direct + 4 * n;
+    int32_t* d_count = (int32_t*)(d_indirect + 4 * n);
+    int32_t* d_add = d_count + n;
+    HIP_TRY(hipMemcpy(d_direct, accum_direct, n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_indirect, accum_indirect, n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_count, count, n * 4, hipMemcpyHostToDevice));
+    if (const int rc = run(width, height, d_direct, d_indirect, d_count, p, d_add, nullptr, st, t0)) return rc;
     HIP_TRY(hipMemcpy(add, d_add, n * 4, hipMemcpyDeviceToHost));
     if (st) st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return FRAYHIP_OK;

@@ -9,6 +9,8 @@ constexpr int kMapMaxSamples = 1 << 24;          // (float)N is exact up to here
 
 // One call, already checked but for the planes' values (gi on, mono, register generators): the frame's buckets and the five buffers in device
 // memory (rgb / noise may be null).  samplemap_impl fills in the rest; badPlanes: its first kernel met a value the entry refuses, nothing was written.
+// A component call (frayhip_render_components_map) has a second state: accum / rgb / noise are then the direct state's and the *Indirect ones the
+// indirect state's (accumIndirect set, the two outputs optional); all three null is the single-state call, launch for launch.
 struct SampleMapCall {
     int bucketFirst, bucketStride;
     uint32_t seed;
@@ -19,6 +21,9 @@ struct SampleMapCall {
     const int32_t* add;
     float* rgb;
     float* noise;
+    float* accumIndirect = nullptr;
+    float* rgbIndirect = nullptr;
+    float* noiseIndirect = nullptr;
     uint64_t samples = 0;
     int countMin = 0, countMax = 0;
     bool badPlanes = false;

@@ -18,6 +18,9 @@
 //   k_map_flag / k_compact_*   the next layer's list: the entries with add > k0 + cn
 //   k_map_finish         count += add, and k_acc_mean's rgb and noise with the pixel's own N, for every pixel of the call's buckets
 // k_map_black answers maxTraceDepth < 0.  Launches per layer and batch do not depend on how many distinct values the map holds.
+// A call with a second state (frayhip_render_components_map: SampleMapCall::accumIndirect) runs the same layers, lists and tracing and, chosen at
+// run time, k_map_fold_split / k_map_resolve_split / k_map_finish_split / k_map_black_split in place of the four above: term 0 of a sample into the
+// direct row, the fold of its other terms (kept in the slot's term-1 planes, so the workspace is the same) into the indirect one.
 #include "samplemap.hpp"
 #include "dev_compact.hpp"
 #include "render_impl.hpp"
@@ -278,6 +281,138 @@ static __global__ __launch_bounds__(256) void k_map_resolve(DFrame F, MapBatch B
     }
 }
 
+// ---- two states (frayhip_render_components_map): a sample's term 0 is its direct light, the fold of its terms 1 .. n-1 its indirect light
+// k_acc_resolve_terms_split's first half, one thread per slot: term 0 stays where it is, as stored; the fold of the others, begun at (0, 0, 0) and
+// innermost first, goes into the slot's term-1 planes (a traced call has nBounce >= 2, so they exist; in the loop form term 1 is the last one read,
+// before it is overwritten).  A wave reads and writes each plane in one piece, as k_map_fold does.
+static __global__ __launch_bounds__(256) void k_map_fold_split(uint32_t total, TermBuf TB)
+{
+    for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < total; slot += gridDim.x * blockDim.x) {
+        const int n = (int)TB.n[slot];
+        C3 result = c3(0, 0, 0);
+        if (n <= 8) {
+            // up to eight terms: every load issued before the first addition
+            float tr[8], tg[8], tb[8];
+#pragma unroll
+            for (int k = 1; k < 8; k++) {
+                tr[k] = tg[k] = tb[k] = 0.0f;
+                if (k < n) {
+                    const size_t q = (size_t)k * 3 * TB.nPaths + slot;
+                    tr[k] = TB.t[q]; tg[k] = TB.t[q + TB.nPaths]; tb[k] = TB.t[q + 2 * (size_t)TB.nPaths];
+                }
+            }
+#pragma unroll
+            for (int k = 7; k >= 1; k--)
+                if (k < n) result = c3(tr[k], tg[k], tb[k]) + result;
+        } else {
+            for (int k = n - 1; k >= 1; k--) {
+                const size_t q = (size_t)k * 3 * TB.nPaths + slot;
+                result = c3(TB.t[q], TB.t[q + TB.nPaths], TB.t[q + 2 * (size_t)TB.nPaths]) + result;
+            }
+        }
+        const size_t q1 = (size_t)3 * TB.nPaths + slot;
+        TB.t[q1] = result.r; TB.t[q1 + TB.nPaths] = result.g; TB.t[q1 + 2 * (size_t)TB.nPaths] = result.b;
+        if (n == 0) { TB.t[slot] = 0.0f; TB.t[slot + TB.nPaths] = 0.0f; TB.t[slot + 2 * (size_t)TB.nPaths] = 0.0f; }          // no term: direct light (0, 0, 0)
+    }
+}
+
+// The second half, per entry, for both rows: term 0 of the entry's slots into the direct row, the fold in their term-1 planes into the indirect one
+static __global__ __launch_bounds__(256) void k_map_resolve_split(DFrame F, MapBatch B, TermBuf TB, float4* __restrict__ direct, float4* __restrict__ indirect)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B.np; i += gridDim.x * blockDim.x) {
+        int x, y;
+        const size_t p = map_pixel(F, B.list[B.p0 + i], x, y);
+        const bool fresh = B.count[p] + B.k0 == 0;
+        float4 rowD = fresh ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : direct[p];
+        float4 rowI = fresh ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : indirect[p];
+        const uint32_t s0 = (uint32_t)B.off[i], s1 = (uint32_t)B.off[i + 1];
+        const size_t plane1 = (size_t)3 * TB.nPaths;
+        // one walk per component (the rows do not depend on each other): a thread then has three address streams in flight, as in k_map_resolve,
+        // and its cache lines still serve the whole walk; with all six at once they did not (33 M slots: 1.53 ms in one walk, 0.99 ms in two; the
+        // single-state resolve takes 0.52 ms)
+        for (uint32_t slot = s0; slot < s1; slot++)
+            map_add(rowD, c3(TB.t[slot], TB.t[slot + TB.nPaths], TB.t[slot + 2 * (size_t)TB.nPaths]));
+        for (uint32_t slot = s0; slot < s1; slot++)
+            map_add(rowI, c3(TB.t[plane1 + slot], TB.t[plane1 + slot + TB.nPaths], TB.t[plane1 + slot + 2 * (size_t)TB.nPaths]));
+        direct[p] = rowD;
+        indirect[p] = rowI;
+    }
+}
+
+// k_map_black for two states: one +0 into both rows, the samples counted once
+static __global__ __launch_bounds__(256) void k_map_black_split(DFrame F, int nItems, const int32_t* __restrict__ add, const int32_t* __restrict__ count,
+                                                                float4* __restrict__ direct, float4* __restrict__ indirect, DStats* st)
+{
+    unsigned long long n = 0;
+    for (int item = blockIdx.x * blockDim.x + threadIdx.x; item < nItems; item += gridDim.x * blockDim.x) {
+        int x, y;
+        if (!item_pixel(F, item, x, y)) continue;
+        const size_t p = (size_t)y * F.W + x;
+        const int a = add[p];
+        if (a <= 0) continue;
+        const bool fresh = count[p] == 0;
+        float4 rowD = fresh ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : direct[p];
+        float4 rowI = fresh ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : indirect[p];
+        map_add(rowD, c3(0, 0, 0));
+        map_add(rowI, c3(0, 0, 0));
+        direct[p] = rowD;
+        indirect[p] = rowI;
+        n += (unsigned long long)a;
+    }
+    if (n) atomicAdd(&st->samples, n);
+}
+
+// k_map_finish's rgb and noise of one state's row at N >= 1 samples (k_acc_mean's arithmetic); either output may be null
+FD void map_mean(const float4* __restrict__ accum, size_t p, int n, float* __restrict__ rgb, float* __restrict__ noise)
+{
+    if (!rgb && !noise) return;
+    const float4 row = accum[p];
+    const C3 m = c3(row.x, row.y, row.z) / (float)n;
+    if (rgb) { rgb[p * 3] = m.r; rgb[p * 3 + 1] = m.g; rgb[p * 3 + 2] = m.b; }
+    if (noise) {
+        const float lbar = map_lum(m);
+        const float v = fmaxf(0.0f, row.w / (float)n - lbar * lbar);
+        noise[p] = n >= 2 ? v / (float)(n - 1) : lbar * lbar;
+    }
+}
+
+// k_map_finish for two states: count += add once, then each component's rgb and noise from its own row and the pixel's N; all four outputs optional
+static __global__ __launch_bounds__(256) void k_map_finish_split(DFrame F, int nItems, const int32_t* __restrict__ add, int32_t* __restrict__ count,
+                                                                 const float4* __restrict__ direct, const float4* __restrict__ indirect,
+                                                                 float* __restrict__ rgbD, float* __restrict__ rgbI, float* __restrict__ noiseD,
+                                                                 float* __restrict__ noiseI, MapHead* head)
+{
+    __shared__ int sMaxInv, sMax;
+    if (threadIdx.x == 0) { sMaxInv = 0; sMax = 0; }
+    __syncthreads();
+    int tMax = 0, tMaxInv = 0;
+    for (int item = blockIdx.x * blockDim.x + threadIdx.x; item < nItems; item += gridDim.x * blockDim.x) {
+        int x, y;
+        if (!item_pixel(F, item, x, y)) continue;
+        const size_t p = (size_t)y * F.W + x;
+        const int a = add[p], n = count[p] + a;
+        if (a > 0) count[p] = n;
+        tMax = max(tMax, n);
+        tMaxInv = max(tMaxInv, frayhip_detail::kMapMaxSamples - n);
+        if (n == 0) {
+            if (rgbD) { rgbD[p * 3] = 0.0f; rgbD[p * 3 + 1] = 0.0f; rgbD[p * 3 + 2] = 0.0f; }
+            if (rgbI) { rgbI[p * 3] = 0.0f; rgbI[p * 3 + 1] = 0.0f; rgbI[p * 3 + 2] = 0.0f; }
+            if (noiseD) noiseD[p] = 0.0f;
+            if (noiseI) noiseI[p] = 0.0f;
+            continue;
+        }
+        map_mean(direct, p, n, rgbD, noiseD);
+        map_mean(indirect, p, n, rgbI, noiseI);
+    }
+    if (tMax) atomicMax(&sMax, tMax);
+    if (tMaxInv) atomicMax(&sMaxInv, tMaxInv);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (sMax) atomicMax(&head->cntMax, sMax);
+        if (sMaxInv) atomicMax(&head->cntMaxInv, sMaxInv);
+    }
+}
+
 // maxTraceDepth < 0: pathtrace() returns black before it looks at the scene.  k_acc_black's arithmetic for the pixels the map names: one addition
 // of +0 (the later ones change nothing), the samples counted.
 static __global__ __launch_bounds__(256) void k_map_black(DFrame F, int nItems, const int32_t* __restrict__ add, const int32_t* __restrict__ count,
@@ -361,6 +496,8 @@ int samplemap_impl(frayhip_scene* sc, SampleMapCall& q, hipStream_t stream, fray
     q.samples = 0;
     q.countMin = q.countMax = 0;
     q.badPlanes = false;
+    const bool pair = q.accumIndirect != nullptr;          // a component call: the split fold, resolve and finish
+    const char* who = pair ? "frayhip_render_components_map" : "frayhip_render_samples_map";
     HIP_TRY(hipMemsetAsync(sc->d_stats, 0, kStatsBytes, stream));
     HIP_TRY(hipEventRecord(sc->evA, stream));
     size_t nTraceEvents = 0, nShadowEvents = 0;
@@ -424,7 +561,10 @@ int samplemap_impl(frayhip_scene* sc, SampleMapCall& q, hipStream_t stream, fray
         q.samples = h.samples;
         const int addMax = h.addMax;
 
-        if (black) {
+        if (black && pair) {
+            hipLaunchKernelGGL(k_map_black_split, dim3(grid_for((size_t)nItems)), dim3(256), 0, stream, F, nItems, q.add, (const int32_t*)q.count, (float4*)q.accum,
+                               (float4*)q.accumIndirect, sc->d_stats);
+        } else if (black) {
             hipLaunchKernelGGL(k_map_black, dim3(grid_for((size_t)nItems)), dim3(256), 0, stream, F, nItems, q.add, (const int32_t*)q.count, (float4*)q.accum, sc->d_stats);
         } else if (nActive > 0) {
             int maxLayer = addMax;
@@ -473,7 +613,7 @@ int samplemap_impl(frayhip_scene* sc, SampleMapCall& q, hipStream_t stream, fray
                     if (const int rc = read_head()) return rc;
                     const size_t m = (size_t)h.slots;
                     if (m < (size_t)mp || m > (size_t)mp * (size_t)cn || m > slots) {
-                        set_error("frayhip_render_samples_map: a batch's slot count is out of range (the add plane changed during the call?)");
+                        set_error(std::string(who) + ": a batch's slot count is out of range (the add plane changed during the call?)");
                         return FRAYHIP_E_ARG;
                     }
                     hipLaunchKernelGGL(k_map_expand, dim3(grid_for(m)), dim3(256), 0, stream, (const int*)off, mp, (uint32_t)m, slotEntry);
@@ -481,8 +621,13 @@ int samplemap_impl(frayhip_scene* sc, SampleMapCall& q, hipStream_t stream, fray
                     hipLaunchKernelGGL(k_meta_dense, dim3(1), dim3(64), 0, stream, meta, (uint32_t)m);
                     hipLaunchKernelGGL(k_pt_init_map<ST>, dim3(grid_for(m)), dim3(256), 0, stream, C, F, B, (uint32_t)m, Q[0], termCount, (const uint32_t*)x397, sc->d_stats);
                     if (const int rc = pt_bounces<ST>(sc, S, Q, SQ, TB, nBounce, bounce_grid(m, alone), stream, nTraceEvents, nShadowEvents)) return rc;
-                    hipLaunchKernelGGL(k_map_fold, dim3(grid_for(m)), dim3(256), 0, stream, (uint32_t)m, TB);
-                    hipLaunchKernelGGL(k_map_resolve, dim3(grid_for((size_t)mp)), dim3(256), 0, stream, F, B, TB, (float4*)q.accum);
+                    if (pair) {
+                        hipLaunchKernelGGL(k_map_fold_split, dim3(grid_for(m)), dim3(256), 0, stream, (uint32_t)m, TB);
+                        hipLaunchKernelGGL(k_map_resolve_split, dim3(grid_for((size_t)mp)), dim3(256), 0, stream, F, B, TB, (float4*)q.accum, (float4*)q.accumIndirect);
+                    } else {
+                        hipLaunchKernelGGL(k_map_fold, dim3(grid_for(m)), dim3(256), 0, stream, (uint32_t)m, TB);
+                        hipLaunchKernelGGL(k_map_resolve, dim3(grid_for((size_t)mp)), dim3(256), 0, stream, F, B, TB, (float4*)q.accum);
+                    }
                 }
                 k0 += cn;
                 if (k0 >= addMax) break;
@@ -490,7 +635,11 @@ int samplemap_impl(frayhip_scene* sc, SampleMapCall& q, hipStream_t stream, fray
                 if (const int rc = compact(nActive, nActive)) return rc;
             }
         }
-        hipLaunchKernelGGL(k_map_finish, dim3(grid_for((size_t)nItems)), dim3(256), 0, stream, F, nItems, q.add, q.count, (const float4*)q.accum, q.rgb, q.noise, head);
+        if (pair)
+            hipLaunchKernelGGL(k_map_finish_split, dim3(grid_for((size_t)nItems)), dim3(256), 0, stream, F, nItems, q.add, q.count, (const float4*)q.accum,
+                               (const float4*)q.accumIndirect, q.rgb, q.rgbIndirect, q.noise, q.noiseIndirect, head);
+        else
+            hipLaunchKernelGGL(k_map_finish, dim3(grid_for((size_t)nItems)), dim3(256), 0, stream, F, nItems, q.add, q.count, (const float4*)q.accum, q.rgb, q.noise, head);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(sc->evB, stream));
         if (const int rc = read_head()) return rc;
@@ -502,7 +651,7 @@ int samplemap_impl(frayhip_scene* sc, SampleMapCall& q, hipStream_t stream, fray
     DStats dsv[2];
     HIP_TRY(hipMemcpy(dsv, sc->d_stats, sizeof dsv, hipMemcpyDeviceToHost));
     if (dsv[0].rngOverflow || dsv[1].rngOverflow) {
-        set_error("frayhip_render_samples_map: a camera sample left the supported envelope (a generator past 227 words; a CsgOp operand with more "
+        set_error(std::string(who) + ": a camera sample left the supported envelope (a generator past 227 words; a CsgOp operand with more "
                   "intersections than the device path holds)");
         return FRAYHIP_E_UNSUPPORTED;
     }

@@ -338,8 +338,12 @@ def sample_map(state, stats=False, stream=None, **params):
     sample_map_params; the formula is in include/frayhip.h "sample maps").  A numpy state goes through the host entry, a state on the GPU through
     the device entry, on `stream` (None: the current stream).  Returns (add, info): add int32 [H, W] of the state's kind -- what
     Scene.render_samples_map takes -- and info {"pixels": pixels with add > 0, "samples": the sum of add}, both over the whole frame, with
-    "stats" (ms_total, ms_kernels) when stats=True."""
+    "stats" (ms_total, ms_kernels) when stats=True.
+    state may also be a pair (direct, indirect) of component states holding the same samples (Scene.render_components_map): the map then comes from
+    frayhip_sample_map_pair, which adds the two components' mean luminances and their noise estimates, and is what render_components_map takes."""
     who = "sample_map"
+    if isinstance(state, (tuple, list)):
+        return _sample_map_pair(who, state, stats, stream, params)
     if not isinstance(state, Accumulation):
         raise TypeError("%s: state must be an Accumulation, got %s" % (who, type(state).__name__))
     p = sample_map_params(**params)
@@ -354,6 +358,47 @@ def sample_map(state, stats=False, stream=None, **params):
         with _DeviceCall(state.state.device, stream) as call:
             add = call.torch.zeros((H, W), dtype=call.torch.int32, device=state.state.device)
             _check(lib.frayhip_sample_map_device(W, H, _ptr(state.state), _ptr(count), C.byref(p), _ptr(add), call.handle, C.byref(st)))
+    info = {"pixels": int(p.pixels), "samples": int(p.samples)}
+    if stats:
+        info["stats"] = st.as_dict()
+    return add, info
+
+
+def _component_pair(who, state, size, seed, bucket_first, bucket_stride):
+    """The checks of a pair (direct, indirect) of component states whose pixels may hold different numbers of samples (render_components' checks,
+    but instead of uniform counts the two count planes must be equal).  Returns (direct, indirect, count plane of the direct state)."""
+    if not (isinstance(state, (tuple, list)) and len(state) == 2 and all(isinstance(a, Accumulation) for a in state)):
+        raise TypeError("%s: state must be a pair (direct, indirect) of Accumulations" % who)
+    sd, si = state
+    for a in (sd, si):
+        a.check(who, size, seed, bucket_first, bucket_stride)
+    if sd is si or sd.state is si.state:
+        raise ValueError("%s: the direct and the indirect state are the same object" % who)
+    if sd.on_device != si.on_device:
+        raise ValueError("%s: one state is a numpy array and the other a GPU tensor" % who)
+    if sd.on_device and sd.state.device != si.state.device:
+        raise ValueError("%s: the states are on different devices" % who)
+    cd, ci = sd.count_plane(), si.count_plane()
+    if not bool((cd == ci).all()):
+        raise ValueError("%s: the direct and the indirect state hold different numbers of samples in some pixel (the two count planes must be equal)" % who)
+    return sd, si, cd
+
+
+def _sample_map_pair(who, state, stats, stream, params):
+    """sample_map of a pair of component states (frayhip_sample_map_pair)."""
+    if not (len(state) == 2 and all(isinstance(a, Accumulation) for a in state)):
+        raise TypeError("%s: state must be an Accumulation or a pair (direct, indirect) of Accumulations" % who)
+    p = sample_map_params(**params)
+    sd, si, count = _component_pair(who, state, state[0].size, state[0].seed, state[0].bucket_first, state[0].bucket_stride)
+    W, H = sd.size
+    st = abi.Stats()
+    if not sd.on_device:
+        add = np.zeros((H, W), np.int32)
+        _check(lib.frayhip_sample_map_pair(W, H, _ptr(sd.state), _ptr(si.state), _ptr(count), C.byref(p), _ptr(add), C.byref(st)))
+    else:
+        with _DeviceCall(sd.state.device, stream) as call:
+            add = call.torch.zeros((H, W), dtype=call.torch.int32, device=sd.state.device)
+            _check(lib.frayhip_sample_map_pair_device(W, H, _ptr(sd.state), _ptr(si.state), _ptr(count), C.byref(p), _ptr(add), call.handle, C.byref(st)))
     info = {"pixels": int(p.pixels), "samples": int(p.samples)}
     if stats:
         info["stats"] = st.as_dict()
@@ -1085,6 +1130,63 @@ class Scene:
         return out + ((info,) if (stats or progress is not None) else ())
 
     # ---- sample maps (include/frayhip.h "sample maps") ----
+    def _add_plane(self, who, add, state):
+        """The add plane of a map call, checked against the state it goes with: int32 [H, W] of the state's kind, contiguous."""
+        W, H = self.frame_size
+        if _torch_tensor(add) != state.on_device:
+            raise TypeError("%s: add must be of the state's kind (a numpy array for a numpy state, a GPU tensor for a state on the GPU)" % who)
+        if state.on_device:
+            import torch
+            if not add.is_cuda or add.device != state.state.device or add.dtype != torch.int32:
+                raise TypeError("%s: add must be an int32 tensor on the state's device" % who)
+            add = add.contiguous()
+        else:
+            add = np.asarray(add)
+            if add.dtype != np.int32:
+                raise TypeError("%s: add must be int32, got %s" % (who, add.dtype))
+            add = np.ascontiguousarray(add)
+        if tuple(add.shape) != (H, W):
+            raise ValueError("%s: add must be shaped %s, got %s" % (who, (H, W), tuple(add.shape)))
+        return add
+
+    def render_components_map(self, add, state=None, seed=42, bucket_first=0, bucket_stride=1, spp_chunk=0, stats=False, noise=False, stream=None):
+        """render_samples_map with direct and indirect light kept apart (frayhip_render_components_map): add[y, x] more samples to each pixel of a
+        pair of component states, state = (direct, indirect) as render_components takes it, or None to start a numpy pair.  The two states must
+        hold the same number of samples in every pixel (ValueError otherwise), but the pixels may differ among themselves.
+
+        Returns (direct_rgb, indirect_rgb, state[, noise_direct, noise_indirect][, stats]) as render_components.  Every pixel of the call's buckets
+        is, bit for bit, that pixel of render_components at the number of samples it now holds; one that holds none is (0, 0, 0) with noise 0.
+        The states are updated in place: each carries its own `counts` plane and samples_done, and both collapse back to uniform states once all
+        pixels agree.  stats["samples"] is the sum of add over the call's pixels."""
+        who = "render_components_map"
+        W, H = self.frame_size
+        if state is None:
+            state = (Accumulation.empty((W, H), seed, bucket_first, bucket_stride), Accumulation.empty((W, H), seed, bucket_first, bucket_stride))
+        sd, si, count = _component_pair(who, state, (W, H), seed, bucket_first, bucket_stride)
+        add = self._add_plane(who, add, sd)
+        self._need_dev()
+        st = abi.Stats()
+        fr = self._frame(abi.MODE_RENDER, sd.seed, bucket_first, bucket_stride, spp_chunk, stats)
+        req = abi.SamplesMap()
+        if not sd.on_device:
+            rgb = [np.zeros((H, W, 3), np.float32) for _ in range(2)]
+            var = [np.zeros((H, W), np.float32) if noise else None for _ in range(2)]
+            _check(lib.frayhip_render_components_map(self._dev, C.byref(fr), C.byref(req), _ptr(sd.state), _ptr(si.state), _ptr(count), _ptr(add),
+                                                     _ptr(rgb[0]), _ptr(rgb[1]), _ptr(var[0]), _ptr(var[1]), C.byref(st)))
+        else:
+            with _DeviceCall(sd.state.device, stream) as call:
+                rgb = [call.torch.zeros((H, W, 3), dtype=call.torch.float32, device=sd.state.device) for _ in range(2)]
+                var = [call.torch.zeros((H, W), dtype=call.torch.float32, device=sd.state.device) if noise else None for _ in range(2)]
+                _check(lib.frayhip_render_components_map_device(self._dev, C.byref(fr), C.byref(req), _ptr(sd.state), _ptr(si.state), _ptr(count),
+                                                                _ptr(add), _ptr(rgb[0]), _ptr(rgb[1]), _ptr(var[0]), _ptr(var[1]), call.handle,
+                                                                C.byref(st)))
+        uniform = req.count_min == req.count_max
+        sd.samples_done = si.samples_done = req.count_min
+        sd.counts = None if uniform else count
+        si.counts = None if uniform else (count.clone() if sd.on_device else count.copy())          # each state carries its own plane
+        out = (rgb[0], rgb[1], state) + ((var[0], var[1]) if noise else ())
+        return out + ((st.as_dict(),) if stats else ())
+
     def render_samples_map(self, add, state=None, seed=42, bucket_first=0, bucket_stride=1, spp_chunk=0, stats=False, noise=False, stream=None):
         """Adds add[y, x] more samples to each pixel of a frame (frayhip_render_samples_map): pixel p's samples count[p] .. count[p] + add[p] - 1,
         where count is what the state holds of it.  add: int32 [H, W], >= 0, of the state's kind (numpy: the host entry; a GPU tensor: the device
@@ -1101,20 +1203,7 @@ class Scene:
         elif not isinstance(state, Accumulation):
             raise TypeError("%s: state must be an Accumulation, got %s" % (who, type(state).__name__))
         state.check(who, (W, H), seed, bucket_first, bucket_stride)
-        if _torch_tensor(add) != state.on_device:
-            raise TypeError("%s: add must be of the state's kind (a numpy array for a numpy state, a GPU tensor for a state on the GPU)" % who)
-        if state.on_device:
-            import torch
-            if not add.is_cuda or add.device != state.state.device or add.dtype != torch.int32:
-                raise TypeError("%s: add must be an int32 tensor on the state's device" % who)
-            add = add.contiguous()
-        else:
-            add = np.asarray(add)
-            if add.dtype != np.int32:
-                raise TypeError("%s: add must be int32, got %s" % (who, add.dtype))
-            add = np.ascontiguousarray(add)
-        if tuple(add.shape) != (H, W):
-            raise ValueError("%s: add must be shaped %s, got %s" % (who, (H, W), tuple(add.shape)))
+        add = self._add_plane(who, add, state)
         self._need_dev()
         count = state.count_plane()
         st = abi.Stats()
@@ -1136,30 +1225,39 @@ class Scene:
         out = (rgb, state) + ((var,) if noise else ())
         return out + ((st.as_dict(),) if stats else ())
 
-    def refine(self, state, tolerance, max_count, passes=8, seed=42, bucket_first=0, bucket_stride=1, spp_chunk=0, stream=None, **params):
+    def refine(self, state, tolerance, max_count, passes=8, seed=42, bucket_first=0, bucket_stride=1, spp_chunk=0, stream=None, split=False, **params):
         """Spends samples where the frame needs them: up to `passes` times, sample_map(state, tolerance=..., max_count=..., **params) and
         render_samples_map of its map; stops when a map is empty.  state: an Accumulation (None starts a numpy one; the first pass then brings
         every pixel to min_count).  Returns (rgb, state, noise, info): the frame, the state, the variance estimate of the mean's luminance --
         denoise_signal's `variance` with demodulate=0 -- and info {"passes": passes that rendered, "samples": samples they added, "ms_kernels":
-        their kernel time}."""
+        their kernel time}.
+        With a pair (direct, indirect) of component states, or split=True and state=None (a numpy pair is started), the loop runs the pair's
+        sample_map and render_components_map and returns (direct_rgb, indirect_rgb, state, noise_direct, noise_indirect, info)."""
         W, H = self.frame_size
+        pair = isinstance(state, (tuple, list)) or (state is None and split)
+        if split and not pair:
+            raise TypeError("refine: split=True takes a pair (direct, indirect) of Accumulations, or None")
         if state is None:
-            state = Accumulation.empty((W, H), seed, bucket_first, bucket_stride)
+            new = lambda: Accumulation.empty((W, H), seed, bucket_first, bucket_stride)
+            state = (new(), new()) if pair else new()
+        step = self.render_components_map if pair else self.render_samples_map
         done = {"passes": 0, "samples": 0, "ms_kernels": 0.0}
-        rgb = noise = None
+        out = None
         for _ in range(int(passes)):
             add, info = sample_map(state, stream=stream, tolerance=tolerance, max_count=max_count, **params)
             if info["pixels"] == 0:
                 break
-            rgb, state, noise, st = self.render_samples_map(add, state, seed, bucket_first, bucket_stride, spp_chunk, stats=True, noise=True, stream=stream)
+            out = step(add, state, seed, bucket_first, bucket_stride, spp_chunk, stats=True, noise=True, stream=stream)
+            st = out[-1]
             if st["samples"] == 0:          # the map's pixels all lie outside the call's buckets
                 break
             done["passes"] += 1
             done["samples"] += int(st["samples"])
             done["ms_kernels"] += st["ms_kernels"]
-        if rgb is None:                     # nothing to add: the frame of what the state holds
-            rgb, state, noise = self.render_samples_map(state.count_plane() * 0, state, seed, bucket_first, bucket_stride, spp_chunk, noise=True, stream=stream)
-        return rgb, state, noise, done
+        if out is None:                     # nothing to add: the frame of what the state holds
+            held = (state[0] if pair else state).count_plane()
+            out = step(held * 0, state, seed, bucket_first, bucket_stride, spp_chunk, noise=True, stream=stream) + (None,)
+        return out[:-1] + (done,)
 
     # ---- adaptive frames (include/frayhip.h "adaptive frames") ----
     def _adaptive_request(self, threshold, min_spp, err_floor):
@@ -1295,25 +1393,39 @@ class Scene:
         out, dst = denoise(raw, feat, half, stats=True, **params)
         return out, raw, {"render": rst, "features": fst, "denoise": dst, "rgb_half": half, "features_frame": feat}
 
-    def render_denoised_split(self, seed=42, feature_samples=4, **params):
+    def render_denoised_split(self, seed=42, feature_samples=4, refine=None, max_count=None, passes=8, **params):
         """A frame whose direct and indirect light are filtered apart: (denoised, raw, info).  The components of the frame's spp samples come from
         render_components with their noise estimates, each goes through denoise_signal with the feature frame (demodulate=0: the states' noise is
         in rgb's domain) and the two results are added in FP32.  raw = direct_rgb + indirect_rgb.  params: denoise_params, but demodulate=1 is
         refused (ValueError).  info: the "render", "features", "denoise_direct" and "denoise_indirect" stats dicts, the filtered components
-        "direct" and "indirect", and their inputs "direct_rgb", "indirect_rgb", "noise_direct", "noise_indirect" and "features_frame"."""
+        "direct" and "indirect", and their inputs "direct_rgb", "indirect_rgb", "noise_direct", "noise_indirect" and "features_frame".
+        refine=TOL: the components come from Scene.refine on a new pair of states instead (tolerance TOL, at most max_count samples in a pixel --
+        required -- and at most `passes` passes); "render" is then refine's info, info gains "refine" (that info with "counts", the int32 [H, W]
+        plane of samples held) and the features take min(feature_samples, the largest count) samples."""
+        if refine is None and max_count is not None:
+            raise ValueError("render_denoised_split: max_count needs refine")
+        if refine is not None and max_count is None:
+            raise ValueError("render_denoised_split: refine needs max_count")
         if params.get("demodulate", 0):
             raise ValueError("render_denoised_split: demodulate=1 is not offered: the components' noise is in rgb's domain, not demodulated")
         params = dict(params, demodulate=0)
         denoise_params(**params)                # unknown names are refused before anything is rendered
         self._need_dev()
-        spp = self.samples_per_pixel()
-        d_rgb, i_rgb, _state, d_noise, i_noise, rst = self.render_components(spp, seed=seed, noise=True, stats=True)
+        extra = {}
+        if refine is None:
+            spp = self.samples_per_pixel()
+            d_rgb, i_rgb, _state, d_noise, i_noise, rst = self.render_components(spp, seed=seed, noise=True, stats=True)
+        else:
+            d_rgb, i_rgb, state, d_noise, i_noise, rst = self.refine(None, refine, max_count, passes=passes, seed=seed, split=True)
+            held = state[0].count_plane()
+            spp = max(int(held.max()), 1)
+            extra["refine"] = dict(rst, counts=held)
         feat, fst = self.render_features(min(int(feature_samples), spp), seed=seed, stats=True)
         d_out, dst = denoise_signal(d_rgb, d_noise, feat, stats=True, **params)
         i_out, ist = denoise_signal(i_rgb, i_noise, feat, stats=True, **params)
-        return d_out + i_out, d_rgb + i_rgb, {"render": rst, "features": fst, "denoise_direct": dst, "denoise_indirect": ist, "direct": d_out,
-                                              "indirect": i_out, "direct_rgb": d_rgb, "indirect_rgb": i_rgb, "noise_direct": d_noise,
-                                              "noise_indirect": i_noise, "features_frame": feat}
+        return d_out + i_out, d_rgb + i_rgb, dict({"render": rst, "features": fst, "denoise_direct": dst, "denoise_indirect": ist, "direct": d_out,
+                                                   "indirect": i_out, "direct_rgb": d_rgb, "indirect_rgb": i_rgb, "noise_direct": d_noise,
+                                                   "noise_indirect": i_noise, "features_frame": feat}, **extra)
 
     def _sequence_samples(self, fr, count, state, stream):
         """render_sequence's own call of frayhip_render_samples_device (state: an Accumulation) or frayhip_render_components_device (a pair of

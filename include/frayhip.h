@@ -746,7 +746,20 @@ int  frayhip_render_components_device(frayhip_scene* s, const frayhip_frame* f, 
  *   is being rendered; and any add[p] < 0, count[p] < 0 or count[p] + add[p] > 2^24 in the call's buckets.  The host entry checks the planes
  *   before it touches the device; the device entry checks them in its first kernel and returns with nothing written.
  * FRAYHIP_E_UNSUPPORTED: gi off (Whitted), stereo and long generators (maxTraceDepth >= 20), for frayhip_render_adaptive's reasons.
- * Not offered: component (direct / indirect) states under a map, a sample budget normalised over the frame, progress callbacks and cancel. */
+ * Not offered: a sample budget normalised over the frame, progress callbacks and cancel (component states under a map: see below).
+ *
+ * Component states under a map (frayhip_render_components_map): the call above for the two states of frayhip_render_components, accum_direct and
+ *   accum_indirect, with ONE count plane -- the two states always hold the same samples.  The tracing is the map call's own; only the end differs:
+ *   a sample's term 0 is added, as stored, to the direct row and the fold of its terms 1 .. n-1 (begun at (0, 0, 0), innermost first; (0, 0, 0) when
+ *   n == 1) to the indirect row, both in sample order with the arithmetic above (k_map_fold_split, k_map_resolve_split; k_map_finish_split writes
+ *   count += add once and each component's rgb and noise from its own row with the pixel's N; k_map_black_split answers maxTraceDepth < 0: one +0
+ *   into both rows, the samples counted once).  After the call each state's row of a pixel holding N samples IS the row frayhip_render_components
+ *   leaves for samples 0 .. N-1, bit for bit.  rgb_direct, rgb_indirect, noise_direct and noise_indirect are all optional; a pixel with N == 0
+ *   gets zeros in all of them.  Everything else is the contract above: buckets (pixels outside are untouched in all seven written buffers and
+ *   their add is not read), a == 0, n == 0 (both rows ignored), the host entry's copy-in rule per buffer, independence, exact kernels only, the
+ *   seed table, *st and m.  FRAYHIP_E_ARG as above with the entry's name, and also a NULL or (device) misaligned second state -- both states
+ *   16-byte aligned -- and any overlap among the eight buffers ("X must not overlap Y", with the argument names below).
+ *   FRAYHIP_E_UNSUPPORTED as above. */
 typedef struct frayhip_samples_map {
     uint64_t samples;        /* out: sum of add over the pixels the call rendered                               */
     int32_t  count_min;      /* out: smallest and largest count after the call among the pixels of the call's   */
@@ -757,6 +770,13 @@ int  frayhip_render_samples_map(frayhip_scene* s, const frayhip_frame* f, frayhi
                                 const int32_t* add, float* rgb, float* noise, frayhip_stats* st);
 int  frayhip_render_samples_map_device(frayhip_scene* s, const frayhip_frame* f, frayhip_samples_map* m, float* d_accum, int32_t* d_count,
                                        const int32_t* d_add, float* d_rgb, float* d_noise, void* hip_stream, frayhip_stats* st);
+int  frayhip_render_components_map(frayhip_scene* s, const frayhip_frame* f, frayhip_samples_map* m, float* accum_direct, float* accum_indirect,
+                                   int32_t* count, const int32_t* add, float* rgb_direct, float* rgb_indirect, float* noise_direct,
+                                   float* noise_indirect, frayhip_stats* st);
+int  frayhip_render_components_map_device(frayhip_scene* s, const frayhip_frame* f, frayhip_samples_map* m, float* d_accum_direct,
+                                          float* d_accum_indirect, int32_t* d_count, const int32_t* d_add, float* d_rgb_direct,
+                                          float* d_rgb_indirect, float* d_noise_direct, float* d_noise_indirect, void* hip_stream,
+                                          frayhip_stats* st);
 
 /* The map from a state (scene-free, one kernel: k_sample_map, samplemap.hip): how many more samples each pixel needs before the standard error
  * of its mean's luminance is `tolerance` times that luminance (or times lum_floor, for a dark pixel).  FP32 throughout, no contraction
@@ -774,7 +794,13 @@ int  frayhip_render_samples_map_device(frayhip_scene* s, const frayhip_frame* f,
  *   rest, as frayhip_render_samples_map does.
  * Device pointers: accum 16-byte aligned, count and add 4-byte; the stream contract and *st (ms_total, ms_kernels) as frayhip_change_frame_device.
  * FRAYHIP_E_ARG, before the device is touched: width or height < 1 or W*H > 2^30; a NULL pointer; a tolerance or lum_floor that is not finite and
- *   > 0; min_count < 1, max_count < min_count or > 2^24; max_add < 1; grow outside 2..16; overlapping buffers; a misaligned device pointer. */
+ *   > 0; min_count < 1, max_count < min_count or > 2^24; max_add < 1; grow outside 2..16; overlapping buffers; a misaligned device pointer.
+ * The map from a PAIR of component states (frayhip_sample_map_pair; the same kernel, k_sample_map<PAIR>; tests/sample_map_pair_ref.py restates it):
+ *   one count plane, the same parameters.  For each component c in {direct, indirect}: mean_c, lbar_c, v_c and noise_c as above from that state's
+ *   row and the pixel's N; then lbar = lbar_d + lbar_i and noise = noise_d + noise_i, and everything from ref = fmaxf(lbar, lum_floor) on, and
+ *   the N >= max_count and N < min_count cases, are unchanged.  Adding the two variances ignores the covariance of a sample's direct and indirect
+ *   light: a maintainer's choice, not a measurement -- the split filter treats the components as separate signals, and their errors add in the
+ *   final sum.  FRAYHIP_E_ARG as above, and a NULL or (device) misaligned second state and any overlap among the four buffers. */
 /* A struct tag without a typedef, as frayhip_denoise. */
 struct frayhip_sample_map {
     float    tolerance;      /* in:  relative standard error aimed at; finite and > 0, default 0.05                      */
@@ -791,6 +817,10 @@ int  frayhip_sample_map(int width, int height, const float* accum, const int32_t
                         frayhip_stats* st);
 int  frayhip_sample_map_device(int width, int height, const float* d_accum, const int32_t* d_count, struct frayhip_sample_map* p,
                                int32_t* d_add, void* hip_stream, frayhip_stats* st);
+int  frayhip_sample_map_pair(int width, int height, const float* accum_direct, const float* accum_indirect, const int32_t* count,
+                             struct frayhip_sample_map* p, int32_t* add, frayhip_stats* st);
+int  frayhip_sample_map_pair_device(int width, int height, const float* d_accum_direct, const float* d_accum_indirect, const int32_t* d_count,
+                                    struct frayhip_sample_map* p, int32_t* d_add, void* hip_stream, frayhip_stats* st);
 
 /* ---- feature frames (first-hit guides for a denoiser) ---------------------------------------------------------------------------------------
  * For every pixel of the call's buckets (frame.bucket_first / bucket_stride, as frayhip_render; other pixels untouched), the FP32 mean, in

@@ -11,7 +11,15 @@ after --warmup.  Every call adds its samples on top of a state of 4 samples per 
 
 (b) is to be read against a quarter of samples_16: what sparsity costs in wave coherence and in fixed work per call.
 
-    python tools/sample_map_rate.py [--rounds 7] [--warmup 2] [--out FILE]"""
+--split measures component states under a map instead (frayhip_render_components_map_device), on a pair of states of 4 samples per pixel:
+
+  components_16        frayhip_render_components_device, samples 4 .. 19 of every pixel
+  pair_uniform_16      frayhip_render_components_map_device with add = 16 everywhere, against components_16
+  map_uniform_16, map_random_16, map_tiles_16      the single-state maps above, and
+  pair_random_16, pair_tiles_16                    the pair maps of the same add: the same rays, a second row in the resolve and the finish
+  sample_map, sample_map_pair                      frayhip_sample_map_device and frayhip_sample_map_pair_device alone
+
+    python tools/sample_map_rate.py [--split] [--rounds 7] [--warmup 2] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -33,6 +41,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out")
+    ap.add_argument("--split", action="store_true", help="measure the pair entries (component states under a map) beside the single-state ones")
     a = ap.parse_args()
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -94,6 +103,78 @@ def main():
         if rc:
             sys.exit("frayhip_sample_map_device: %s" % lib.frayhip_last_error().decode())
         return st.ms_kernels, st.ms_total
+
+    if a.split:
+        with torch.cuda.stream(stream):
+            pair = (fray_amd.Accumulation.empty((W, H), device="cuda"), fray_amd.Accumulation.empty((W, H), device="cuda"))
+            s.render_components(BASE, pair, stream=stream)
+            acc_d, acc_i = torch.empty_like(pair[0].state), torch.empty_like(pair[1].state)
+            rgb_i = torch.empty_like(rgb)
+            noise_i = torch.empty_like(noise)
+        torch.cuda.synchronize()
+
+        def reset_pair():
+            with torch.cuda.stream(stream):
+                acc_d.copy_(pair[0].state)
+                acc_i.copy_(pair[1].state)
+                count.fill_(BASE)
+            stream.synchronize()
+
+        def components():
+            reset_pair()
+            req, st = abi.Samples(sample_first=BASE, sample_count=ADD), abi.Stats()
+            rc = lib.frayhip_render_components_device(s._dev, C.byref(fr), C.byref(req), None, acc_d.data_ptr(), acc_i.data_ptr(), rgb.data_ptr(),
+                                                      rgb_i.data_ptr(), noise.data_ptr(), noise_i.data_ptr(), h, C.byref(st))
+            if rc:
+                sys.exit("frayhip_render_components_device: %s" % lib.frayhip_last_error().decode())
+            return st.ms_kernels, st.ms_total
+
+        def mapped_pair(add):
+            def run():
+                reset_pair()
+                req, st = abi.SamplesMap(), abi.Stats()
+                rc = lib.frayhip_render_components_map_device(s._dev, C.byref(fr), C.byref(req), acc_d.data_ptr(), acc_i.data_ptr(), count.data_ptr(),
+                                                              add.data_ptr(), rgb.data_ptr(), rgb_i.data_ptr(), noise.data_ptr(), noise_i.data_ptr(), h,
+                                                              C.byref(st))
+                if rc:
+                    sys.exit("frayhip_render_components_map_device: %s" % lib.frayhip_last_error().decode())
+                assert req.samples == int(add.sum())
+                return st.ms_kernels, st.ms_total
+            return run
+
+        def sample_map_pair():
+            p, st = fray_amd.sample_map_params(tolerance=0.05, max_count=256), abi.Stats()
+            rc = lib.frayhip_sample_map_pair_device(W, H, acc_d.data_ptr(), acc_i.data_ptr(), count.data_ptr(), C.byref(p), out_add.data_ptr(), h, C.byref(st))
+            if rc:
+                sys.exit("frayhip_sample_map_pair_device: %s" % lib.frayhip_last_error().decode())
+            return st.ms_kernels, st.ms_total
+
+        # every pair map follows the single-state map of the same add; the two sample maps read the states their predecessors left
+        calls = [("map_uniform_16", mapped(uniform)), ("pair_uniform_16", mapped_pair(uniform)), ("map_random_16", mapped(scattered)),
+                 ("pair_random_16", mapped_pair(scattered)), ("map_tiles_16", mapped(tiled)), ("pair_tiles_16", mapped_pair(tiled)),
+                 ("samples_16", samples), ("sample_map", sample_map), ("components_16", components), ("sample_map_pair", sample_map_pair)]
+        times = {k: [] for k, _ in calls}
+        for r in range(a.warmup + a.rounds):
+            for k, fn in calls:
+                v = fn()
+                if r >= a.warmup:
+                    times[k].append(v)
+        res = {k: med(v) for k, v in times.items()}
+        res["map_samples"] = {"uniform": int(uniform.sum()), "random": int(scattered.sum()), "tiles": int(tiled.sum())}
+        ms = lambda k: res[k]["kernels_ms"]
+        res["ratios"] = {"a_pair_over_map_uniform": ms("pair_uniform_16") / ms("map_uniform_16"),
+                         "a_pair_over_map_random": ms("pair_random_16") / ms("map_random_16"),
+                         "a_pair_over_map_tiles": ms("pair_tiles_16") / ms("map_tiles_16"),
+                         "b_uniform_pair_map_over_components": ms("pair_uniform_16") / ms("components_16")}
+        for k, _ in calls:
+            print("%-15s kernels %8.2f ms  call %8.2f ms" % (k, res[k]["kernels_ms"], res[k]["call_ms"]), flush=True)
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        s.close()
+        return
 
     # sample_map follows samples_16 in every round: it reads the state and the counts (BASE, as reset() left them) of that call
     calls = [("map_uniform_16", mapped(uniform)), ("map_random_16", mapped(scattered)), ("map_tiles_16", mapped(tiled)), ("samples_16", samples),
