@@ -288,6 +288,7 @@ DScene frame_scene(const frayhip_scene* s)
     S.segmentPlanes = s->segmentPlanes ? 1 : 0;
     S.certifiedSegments = (s->certifiedSegments && s->segmentPlanes && S.segCertAll) ? 1 : 0;      // (no effect while "segment_planes" is 0)
     if (!s->cameraSkip) S.nCamSkip = 0;          // frayhip_scene_camera_skip switched off: no record, the first bounce asks every node
+    if (!s->shadeShortcuts) S.shadeIdentity = S.lightsDiagonal = S.subdShift = 0;      // frayhip_scene_shade_shortcuts switched off: the kernels take the general forms
     return S;
 }
 
@@ -640,6 +641,7 @@ int frayhip_scene_create(const frayhip_scene_desc* desc, frayhip_scene** out)
     if (const char* e = getenv("FRAYHIP_CERTIFIED_SEGMENTS")) sc->certifiedSegments = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_TIGHT_GATES")) sc->tightGates = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_CAMERA_SKIP")) sc->cameraSkip = atol(e) != 0;
+    if (const char* e = getenv("FRAYHIP_SHADE_SHORTCUTS")) sc->shadeShortcuts = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_FUSED_WHITTED_MAX")) { long v = atol(e); if (v >= 0 && v <= 1024) sc->fusedWhittedMax = (int)v; }
     if (const char* e = getenv("FRAYHIP_CSG_LANES")) { long v = atol(e); if (v >= 1 && v <= FRAY_PT_LANES) sc->csgLanes = (int)v; }
     if (const char* e = getenv("FRAYHIP_SEED_TABLE_MIB")) { long v = atol(e); if (v >= 0 && v <= (1 << 20)) sc->seedTableCapBytes = (size_t)v << 20; }
@@ -746,6 +748,17 @@ int frayhip_scene_camera_skip(frayhip_scene* s, int enable, int64_t* enabled, in
     if (eligible) *eligible = s->edit->F.nCamSkip;
     if (skipped) *skipped = s->lastCameraSkipped;
     if (waves) *waves = s->lastCameraWaves;
+    return FRAYHIP_OK;
+}
+
+int frayhip_scene_shade_shortcuts(frayhip_scene* s, int enable, int64_t* enabled, int64_t* eligible)
+{
+    if (!s) { set_error("frayhip_scene_shade_shortcuts: null scene"); return FRAYHIP_E_ARG; }
+    if (enable < -1 || enable > 1) { set_error("frayhip_scene_shade_shortcuts: enable must be -1, 0 or 1"); return FRAYHIP_E_ARG; }
+    if (enable >= 0 && s->rendering) { set_error("frayhip_scene_shade_shortcuts: the scene is rendering a frame"); return FRAYHIP_E_ARG; }
+    if (enable >= 0) s->shadeShortcuts = enable != 0;
+    if (enabled) *enabled = s->shadeShortcuts ? 1 : 0;
+    if (eligible) *eligible = (s->edit->F.shadeIdentity ? 1 : 0) | (s->edit->F.lightsDiagonal ? 2 : 0);
     return FRAYHIP_OK;
 }
 

@@ -141,7 +141,8 @@ struct DShader {
 struct DLayer { int32_t shader, texture; float opacity[3]; int32_t pad; };
 
 struct DLight {
-    int32_t kind, xSubd, ySubd, pad;
+    int32_t kind, xSubd, ySubd;
+    int32_t xShift;                // log2(xSubd) when xSubd is a power of two, else -1 (light_nth_sample's shortcut: idx & (xSubd - 1), idx >> xShift)
     float color[3], power;
     double pos[3];
     DXform T;
@@ -220,6 +221,14 @@ struct DScene {
     // Miss records of the first bounce (DCamSkip above).  nCamSkip is the frame's: 0 while frayhip_scene_camera_skip is switched off (frame_scene).
     const FRAY_RO DCamSkip* camSkip;
     int32_t nCamSkip, padCamSkip;
+    // Shade shortcuts (frayhip_scene_shade_shortcuts; dev_shade.hpp finalize_hit, light_nth_sample; dev_trace.hpp light_intersect; scene_arena.hpp fill_editable
+    // decides both flags).  Each is the frame's: 0 while the switch is off (frame_scene).
+    // shadeIdentity: EVERY node is an untransformed (DNode::xfIdentity) flat mesh without a KD-tree, of at most normStride triangles, whose shader reads no (u, v)
+    // and which has no bump texture; worldNormals then holds normalized(mulM(g, T.m)) of triangle t of node i at 3 * (i * normStride + t).
+    // lightsDiagonal: every light is a RectLight whose m and inv have zero off-diagonal entries and whose offset components are finite and nonzero.
+    const FRAY_RO double* worldNormals;
+    int32_t normStride, shadeIdentity, lightsDiagonal;
+    int32_t subdShift;             // 1 while the switch is on: light_nth_sample finds a sample's cell by DLight::xShift where the light has one
 };
 
 // Work decomposition of a frame: the reference's 48x48 buckets (sdl.cpp:243-262), of which this

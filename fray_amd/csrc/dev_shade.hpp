@@ -8,6 +8,10 @@
 #include "dev_scene.hpp"
 #include "dev_trace.hpp"
 
+#ifndef FRAY_SHADE_PLUS_ZERO
+#define FRAY_SHADE_PLUS_ZERO 1     // tests/native/shade_shortcut_check.cpp builds a second time with 0 to show that it sees what the shortcut's final + (+0.0) is there for
+#endif
+
 enum { RF_DIFFUSE = 2 };   // vector.h:215-219
 
 struct HitInfo {           // IntersectionInfo, geometry.h:33-39 (after Node::intersect)
@@ -61,9 +65,44 @@ FD void prim_attributes(const DScene& S, int kind, int index, V3 ipl, int code, 
 
 // BARY: the hit record carries no barycentrics (the path tracer's hit queue): they are re-derived for meshes that read them.
 // ANY_UV: needUV is honoured in every variant, also those compiled without texture code (the ray queries' hit record, query_variant.hip).
-template <int ST, bool BARY = false, bool ANY_UV = false>
+// SHORTCUT: compiled with the scalar branch on DScene::shadeIdentity (the path tracer's timed kernels for untransformed scenes, kernels.hpp path_shade;
+// frayhip_scene_shade_shortcuts) -- every other instantiation is the code it was.  Under the flag every node is an untransformed flat mesh whose (u, v) and
+// dNdx / dNdy nothing reads (scene_arena.hpp fill_editable): off = +0 and m = inv = I bit for bit, so the general form below computes
+//     ls = mulM(o - 0, I),  ldir = normalized(mulM(d, I)),  ipl = ls + ldir * t,  ip = mulM(ipl, I) + 0,  norm = normalized(mulM(g, I)).
+// The shortcut loads no transform and computes ldir' = normalized(d), ipl' = o + ldir' * t, ip' = ipl' + (+0.0), norm' = the table's entry.  Proof that ip' and
+// norm' are ip and norm bit for bit, for finite o, d, t and ipl:
+//   (1) v - (+0) is v, the sign of a zero included.  mulM(v, I).x = v.x * 1 + v.y * 0 + v.z * 0: the products are exact, v.y * 0 and v.z * 0 are zeros, and a
+//       nonzero v.x plus zeros is v.x.  So mulM(v, I) is v except in the SIGN of a zero component (a sum of zeros is -0 only when all are -0).
+//   (2) Hence ls is o and mulM(d, I) is d up to signs of zeros.  normalized() squares the components (a square does not see the sign of a zero) and scales each by the
+//       same 1 / length: ldir is ldir' up to signs of zeros, and so is ldir * t.
+//   (3) A component of ipl is a sum a + b with a of ls and b of ldir * t.  Where a or b is nonzero in one form it is the same nonzero value in the other, and adding
+//       a zero of either sign to a nonzero value changes nothing: the sums agree unless both terms are zeros, where each form yields a zero.  So ipl is ipl' up to
+//       signs of zeros, and by (1) so is mulM(ipl, I).
+//   (4) x + (+0) is x for nonzero x and +0 for either zero: the final addition maps both forms to the same bits.  The + (+0.0) of the shortcut is therefore needed: without it
+//       a -0 component of ipl' would reach spawn_ray's and nee_prepare's origins, where the general form has +0.
+//   (5) norm: the table holds normalized(mulM(g, m)) of the node's own m, evaluated on the host by the same IEEE multiplications, additions, square root and division
+//       (fill_editable's world_normal) -- in the exact arithmetic the same bits; the fp_contract copy's own normalisation is a relaxed one (dev_math.hpp fray_rsqrt), the table's is the
+//       correctly rounded value it approximates.
+// Finite operands: with a non-finite component v.y * 0 is NaN and (1) fails.  o and d of a live path are finite -- a camera ray, or x.ip + norm * 1e-6 and a unit
+// direction of an earlier finite hit; the ray queries that reach these kernels refuse non-finite rays (shade_variant.hip) -- and a hit stands only with
+// dist = |o - ipl| < 1e99 (closest_hit), which an infinite or NaN component of ipl, or of t behind it, does not pass.
+template <int ST, bool BARY = false, bool ANY_UV = false, bool SHORTCUT = false>
 FD void finalize_hit(const DScene& S, const HitT<ST>& h, V3 o, V3 d, bool needUV, HitInfo& info)
 {
+    if constexpr (SHORTCUT) {
+        // (the fields nothing reads are written before the branch: written on either side of it, their stores are merged with the general form's stores to OTHER fields
+        // behind a selected address, and `info` then lives in scratch memory)
+        info.dNdx = v3(0, 0, 0);
+        info.dNdy = v3(0, 0, 0);
+        info.u = 0; info.v = 0;
+        if (S.shadeIdentity) {
+            const V3 ldir = normalized(d);
+            const V3 ipl = o + ldir * h.t;
+            info.ip = FRAY_SHADE_PLUS_ZERO ? ipl + v3(0.0, 0.0, 0.0) : ipl;
+            info.norm = ld3(S.worldNormals + 3 * (h.node * S.normStride + h.tri));          // (nNodes * normStride <= 2^24: arena_build)
+            return;
+        }
+    }
     const FRAY_RO DNode& N = S.nodes[h.node];
     needUV = needUV && (ANY_UV || tex_variant(ST));           // no texture in the scene reads (u, v)
     const bool needBump = tex_variant(ST) && N.bumpTex >= 0;
@@ -197,16 +236,36 @@ FD C3 environment(const DScene& S, V3 dir, Cnt& c)
 // ---- lights (lights.h:41-47, lights.cpp:31-77,105-108) ---------------------------------------------
 FD int light_num_samples(const FRAY_RO DLight& L) { return L.kind == 0 ? 1 : L.xSubd * L.ySubd; }
 FD C3 light_color(const FRAY_RO DLight& L) { return ldc(L.color) * L.power; }
-template <class G>
-FD void light_nth_sample(const FRAY_RO DLight& L, int idx, V3 shadePos, G& tab, V3& samplePos, C3& color)
+// SHORTCUT (nee_prepare of the path tracer's timed kernels for untransformed scenes; frayhip_scene_shade_shortcuts): compiled with two shortcuts, every other
+// instantiation is the code it was.
+//   The cell, when `shift` (DScene::subdShift: the switch): a light whose xSubd is a power of two carries its log2 (DLight::xShift, else -1).  idx lies in [0, xSubd * ySubd), and for a non-negative idx
+//   idx & (xSubd - 1) and idx >> xShift ARE idx % xSubd and idx / xSubd.
+//   The transform, when `diagonal` (DScene::lightsDiagonal, wave-uniform: every light is a RectLight, the off-diagonal entries of m and inv are zeros, the diagonal ones
+//   finite, the offset's components finite and nonzero): mulM(v, D).x is v.x * D[0] + v.y * 0 + v.z * 0, i.e. v.x * D[0] except in the SIGN of a zero result (finite v:
+//   the other two products are zeros); the shortcut computes the three diagonal products alone.
+//     samplePos: mulM(pl, m) + off.  The x and z components are pl.x * m[0] and pl.z * m[8] up to the sign of a zero, and adding the NONZERO off.x, off.z erases that
+//     sign: a zero of either sign plus off.x is off.x.  The y component is a sum of zeros (pl.y = 0, m[4] finite) plus off.y: off.y itself.  Bit for bit the general
+//     form's.  (With a zero offset component the sum's zero would keep its sign and reach visible()'s reciprocal direction: such a light is not eligible.)
+//     sp: equal up to signs of zeros; its consumers are the comparison sp.y > 0 and length(sp), which do not see them, and dot((0, -1, 0), sp), which is -sp.y
+//     when sp.y is nonzero.  So `color` is the general form's unless sp.y is a zero -- a shade point exactly in the light's plane -- where cw is a zero whose sign
+//     may differ.  nee_prepare, the one caller of this instantiation, discards `color`.
+//   Both forms draw the same two words in the same order.
+template <bool SHORTCUT = false, class G>
+FD void light_nth_sample(const FRAY_RO DLight& L, int idx, V3 shadePos, G& tab, V3& samplePos, C3& color, bool diagonal = false, bool shift = false)
 {
     if (L.kind == 0) {
         samplePos = ld3(L.pos);
         color = ldc(L.color) * L.power;
         return;
     }
-    int col = idx % L.xSubd;
-    int row = idx / L.xSubd;
+    int col, row;
+    if (SHORTCUT && shift && L.xShift >= 0) {
+        col = idx & (L.xSubd - 1);
+        row = idx >> L.xShift;
+    } else {
+        col = idx % L.xSubd;
+        row = idx / L.xSubd;
+    }
     double cellW = L.areaXsize;
     double cellH = L.areaYsize;
     double x0 = col * cellW;
@@ -214,14 +273,18 @@ FD void light_nth_sample(const FRAY_RO DLight& L, int idx, V3 shadePos, G& tab, 
     double p_x = x0 + cellW * rng_float(tab);
     double p_y = y0 + cellH * rng_float(tab);
     V3 pl = v3(p_x - 0.5, 0, p_y - 0.5);
-    V3 sp = mulM(shadePos - ld3(L.T.off), L.T.inv);
+    const V3 rel = shadePos - ld3(L.T.off);
+    V3 sp;
+    if (SHORTCUT && diagonal) sp = v3(rel.x * L.T.inv[0], rel.y * L.T.inv[4], rel.z * L.T.inv[8]);
+    else sp = mulM(rel, L.T.inv);
     if (sp.y > 0) {
         color = c3(0, 0, 0);
     } else {
         float cw = float(fray_div(dot(v3(0, -1, 0), sp), length(sp)));
         color = ldc(L.color) * L.power * (float)L.area * cw;
     }
-    samplePos = mulM(pl, L.T.m) + ld3(L.T.off);
+    if (SHORTCUT && diagonal) samplePos = v3(pl.x * L.T.m[0] + L.T.off[0], L.T.off[1], pl.z * L.T.m[8] + L.T.off[2]);
+    else samplePos = mulM(pl, L.T.m) + ld3(L.T.off);
 }
 FD double light_solid_angle(const FRAY_RO DLight& L, V3 ip)
 {
@@ -357,7 +420,8 @@ FD void spawn_ray(const FRAY_RO DShader& sh, const HitInfo& x, const PathRay& w_
 // search answers, and that is the black term path_shade stores itself when nothing was queued -- so the any-hit search, the gate classification and
 // the queue entry are dropped and no stored word changes.  A -0.0f or NaN channel is NOT such a sample (visible would store it, hidden would store +0).
 // Every random draw happens before the first skip, so the generators leave in the same state either way.
-template <class GR, class GT>
+// SHORTCUT: light_nth_sample's shortcuts (above) under DScene::lightsDiagonal; every other instantiation is the code it was.
+template <bool SHORTCUT = false, class GR, class GT>
 FD bool nee_prepare(const DScene& S, V3 rayDir, const HitInfo& info, C3 pm, const FRAY_RO DShader& sh, GR& rnd, GT& tab, V3& a, V3& b, C3& contrib, bool skipNull)
 {
     if (S.nLights == 0) return false;
@@ -369,7 +433,7 @@ FD bool nee_prepare(const DScene& S, V3 rayDir, const HitInfo& info, C3 pm, cons
     int randSample = rng_int0(rnd, light_num_samples(L) - 1);
     V3 pl;
     C3 unused;
-    light_nth_sample(L, randSample, x, tab, pl, unused);
+    light_nth_sample<SHORTCUT>(L, randSample, x, tab, pl, unused, SHORTCUT && S.lightsDiagonal != 0, SHORTCUT && S.subdShift != 0);
     if (skipNull && (sh.kind == 3 || sh.kind == 4)) return false;   // Reflection / Refraction::eval: zero by construction, known before w_out is normalised
     a = x + info.norm * 1e-6;
     b = pl;

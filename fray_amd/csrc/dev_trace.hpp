@@ -50,6 +50,10 @@ constexpr bool identity_variant(int st) { return FRAY_IDENTITY_SKIP && (st & 14)
 // when rays that pass a mesh's bounding box are filed gate-free (+14 % of its vector instructions); not the fp_contract copy, whose bounce kernel spills
 // nine more registers with the guards (the contracted frame: +3.7 ms of 64; profiles/tight_gates/README.md).  Every other variant's code is what it was.
 constexpr bool tight_variant(int st) { return FRAY_ARITH == 0 && (st & 15) == 0; }
+// The variants whose path-tracing kernels (k_pt_bounce: closest_hit's light loop, path_shade's finalize_hit and nee_prepare) are compiled with the shade shortcuts
+// of frayhip_scene_shade_shortcuts (dev_shade.hpp finalize_hit, light_nth_sample; light_intersect below): flag word 0, in both arithmetics -- the scenes whose nodes can all
+// be untransformed flat meshes.  Not the counting variant, whose code stays the reference's restatement the timed frames are compared with.
+constexpr bool shade_shortcut_variant(int st) { return identity_variant(st) && !(st & 1); }
 
 // Closest-hit record.  Shading attributes (ip, normal, uv, dNdx/dNdy) are re-derived from it for
 // the winning node only (finalize_hit in dev_shade.hpp) -- same arithmetic, so same bits.
@@ -1007,13 +1011,32 @@ FD bool node_intersect(const DScene& S, int i, V3 o, V3 d, LocalRay& lr, double&
 }
 
 // RectLight::intersect (lights.cpp:79-103); point lights are never hit (lights.h:68-71).
-template <int ST>
-FD bool light_intersect(const FRAY_RO DLight& L, V3 o, V3 d, double& dist, Cnt& c)
+// SHORTCUT (closest_hit of the path tracer's timed kernels for untransformed scenes; frayhip_scene_shade_shortcuts): compiled with the form for `diagonal`
+// (DScene::lightsDiagonal, wave-uniform: every light is a RectLight whose m and inv have zero off-diagonal and finite diagonal entries and whose offset's components
+// are finite and nonzero) -- every other instantiation is the code it was.  mulM(v, D).x is v.x * D[0] + v.y * 0 + v.z * 0: for finite v the last two products are
+// zeros, so it is v.x * D[0] except in the SIGN of a zero result; the shortcut computes the three diagonal products alone.  Proof that the answer and `dist` are the
+// general form's:
+//   ls and mulM(d, inv) agree up to signs of zeros; normalized() squares its operand and scales by one factor, so ldir does too.  ls.y >= 0 and ldir.y <= 0 are
+//   comparisons and fabs() drops the sign: the two early returns and `scaling` are the same.  A component of ip = ls + ldir * scaling is the same sum of the same
+//   nonzero terms, or a zero of either sign where both terms are zeros; fabs(ip.x) > 0.5 and fabs(ip.z) > 0.5 do not see that.  A component of mulM(ip, m) is
+//   ip.x * m[0] up to the sign of a zero, and the NONZERO off.x added to a zero of either sign is off.x: the world point is the same bit for bit, and so is dist.
+//   Overflow: where scaling overflows (a ray within 1e-300 of the light's plane's direction) ip has an infinite or NaN component in both forms; one in x or z fails
+//   or passes the fabs comparison alike, and past it dist is NaN in the general form (inf * 0) and inf or NaN in the shortcut -- closest_hit reads dist in `dist < best.dist`
+//   alone, with best.dist <= 1e99, false for both.
+template <int ST, bool SHORTCUT = false>
+FD bool light_intersect(const FRAY_RO DLight& L, V3 o, V3 d, double& dist, Cnt& c, bool diagonal = false)
 {
     if (L.kind == 0) return false;
     bump<ST>(c.prim);
-    V3 ls = mulM(o - ld3(L.T.off), L.T.inv);
-    V3 ldir = normalized(mulM(d, L.T.inv));
+    const V3 rel = o - ld3(L.T.off);
+    V3 ls, ldir;
+    if (SHORTCUT && diagonal) {
+        ls = v3(rel.x * L.T.inv[0], rel.y * L.T.inv[4], rel.z * L.T.inv[8]);
+        ldir = normalized(v3(d.x * L.T.inv[0], d.y * L.T.inv[4], d.z * L.T.inv[8]));
+    } else {
+        ls = mulM(rel, L.T.inv);
+        ldir = normalized(mulM(d, L.T.inv));
+    }
     if (ls.y >= 0) return false;
     if (ldir.y <= 0) return false;
     double travelByY = fabs(ls.y);
@@ -1021,7 +1044,8 @@ FD bool light_intersect(const FRAY_RO DLight& L, V3 o, V3 d, double& dist, Cnt& 
     double scaling = fray_div(travelByY, unitTravel);
     V3 ip = ls + ldir * scaling;
     if (fabs(ip.x) > 0.5 || fabs(ip.z) > 0.5) return false;
-    ip = mulM(ip, L.T.m) + ld3(L.T.off);
+    if (SHORTCUT && diagonal) ip = v3(ip.x * L.T.m[0], ip.y * L.T.m[4], ip.z * L.T.m[8]) + ld3(L.T.off);
+    else ip = mulM(ip, L.T.m) + ld3(L.T.off);
     dist = length(o - ip);
     return true;
 }
@@ -1044,7 +1068,9 @@ FD void light_record(const FRAY_RO DLight& L, V3 o, V3 d, V3& ip, V3& norm)
 // CAMSKIP: compiled with the test for the nodes in `skipNodes` (camera_skip_nodes below: the first bounce of the leanest timed variant only -- every other
 // instantiation is the code it was without it).  Bit i: the certificate of dev_gatecert.hpp holds for node i and EVERY ray of the wave, so the node's mesh
 // reports no intersection as the reference computes it; wave-uniform, a scalar branch before the node's record is touched.
-template <int ST, bool CAMSKIP = false>
+// SHORTCUT: the light loop takes light_intersect's form for diagonal lights under DScene::lightsDiagonal (a scalar branch; the path tracer's timed kernels for
+// untransformed scenes only -- every other instantiation is the code it was).
+template <int ST, bool CAMSKIP = false, bool SHORTCUT = false>
 FD void closest_hit(const DScene& S, V3 o, V3 d, HitT<ST>& best, Cnt& c, bool gateFree = false, uint32_t skipNodes = 0u)
 {
     bump<ST>(c.closest);
@@ -1081,7 +1107,7 @@ FD void closest_hit(const DScene& S, V3 o, V3 d, HitT<ST>& best, Cnt& c, bool ga
     const int nl = S.nLights;
     for (int i = 0; i < nl; i++) {
         double dist;
-        if (light_intersect<ST>(S.lights[i], o, d, dist, c) && dist < best.dist) {
+        if (light_intersect<ST, SHORTCUT>(S.lights[i], o, d, dist, c, SHORTCUT && S.lightsDiagonal != 0) && dist < best.dist) {
             best.node = -2 - i;
             best.dist = dist;
         }

@@ -1130,7 +1130,7 @@ FD void path_shade(const DScene& S, PathStateT<G>& ps, const HitT<ST>& h, const 
         const FRAY_RO DNode& N = S.nodes[h.node];
         const FRAY_RO DShader& sh = S.shaders[N.shader];
         HitInfo info;
-        finalize_hit<ST, BARY>(S, h, ps.o, ps.d, sh.usesUV || N.bumpTex >= 0, info);
+        finalize_hit<ST, BARY, false, shade_shortcut_variant(ST)>(S, h, ps.o, ps.d, sh.usesUV || N.bumpTex >= 0, info);
         apply_bump<ST>(S, h.node, info, c);
         mt_skip(ps.tab, spawn_words(sh));                     // the discarded spawnRay (main.cpp:219-224)
         {
@@ -1138,7 +1138,7 @@ FD void path_shade(const DScene& S, PathStateT<G>& ps, const HitT<ST>& h, const 
             // that it is not carried in registers across the spawn
             V3 sa, sb;
             C3 sc;
-            shadow = nee_prepare(S, ps.d, info, ps.pm, sh, ps.rnd, ps.tab, sa, sb, sc, !(ST & 1) && S.skipNullSegments != 0);   // the counting variants trace every segment the reference traces
+            shadow = nee_prepare<shade_shortcut_variant(ST)>(S, ps.d, info, ps.pm, sh, ps.rnd, ps.tab, sa, sb, sc, !(ST & 1) && S.skipNullSegments != 0);   // the counting variants trace every segment the reference traces
             if (shadow) {
                 // Certified segments (flag word 0 only: the counting variant queues every segment the reference traces; DScene::certifiedSegments is the option,
                 // "segment_planes" and the scene's segCertAll together): the segment's ray misses every gate and its ends lie on one side of every plane entry, so
@@ -1299,7 +1299,7 @@ static __global__ __launch_bounds__(256, waves_for(ST, kd_variant(ST) ? FRAY_BOU
             STAMP(0);
             // entry test of pathtrace() (main.cpp:173-176) was applied before this path was queued
             HitT<ST> h;
-            closest_hit<ST, CAMSKIP>(S, ps.o, ps.d, h, c, gateFree, skipNodes);
+            closest_hit<ST, CAMSKIP, shade_shortcut_variant(ST)>(S, ps.o, ps.d, h, c, gateFree, skipNodes);
             if constexpr (FIRST) {
                 // the rest of the path's state, made after the search so that it is not live across it: the generators stand where the camera ray left them
                 ps.pm = c3(1, 1, 1); ps.slot = di; ps.depth = 0; ps.flags = 0;

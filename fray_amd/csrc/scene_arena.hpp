@@ -34,6 +34,8 @@ struct ArenaFacts {
     int32_t nGates, gatesExact, nSegPlanes, nSegNodes, segCertAll;
     int32_t nTightGates;                      // gates whose entry in the table's tight half differs: eligible meshes (dev_gatecert.hpp)
     int32_t nCamSkip, tCamSkip;               // miss records of the first bounce (dev_scene.hpp DCamSkip) and their table
+    int32_t shadeIdentity, lightsDiagonal;    // the shade shortcuts' eligibility (dev_scene.hpp DScene::shadeIdentity, lightsDiagonal): of the nodes, of the lights
+    int32_t normStride, tWorldNormals;        // the world-normal table (DScene::worldNormals): entries per node (fixed at arena_build), and the table
     int32_t nNodes, nLights, nMeshes, nTextures;
     int32_t envPresent, envLoaded, envWidth[6], envHeight[6];
     int64_t envTexelOffset[6];
@@ -102,6 +104,30 @@ inline bool shader_uses_uv(const frayhip_scene_desc& d, int s, int depth = 0)
 // at most FRAY_GATECERT_MAX_TRIS triangles (arena_keeps_tris: the segment planes of the small ones, the tight gate records of the others, the first bounce's miss records of both) -- never a
 // mesh array or the texel pool of `d`.  Every inner pointer is written null
 // (arena_place); the unused tails of the gate and segment-plane tables are zeroed.  F: the t* indices and the counts are read, the editable facts written.
+// normalized(mulM(g, m)) as finalize_hit (dev_shade.hpp) evaluates it for a flat triangle's normal, operation for operation (dev_math.hpp mulM, length, normalized in
+// the exact arithmetic): IEEE multiplications, additions, one square root and one division, which give the same bits whoever performs them.
+inline void world_normal(const double* g, const double* m, double* out)
+{
+    const double x = g[0] * m[0] + g[1] * m[3] + g[2] * m[6], y = g[0] * m[1] + g[1] * m[4] + g[2] * m[7], z = g[0] * m[2] + g[1] * m[5] + g[2] * m[8];
+    const double r = 1.0 / std::sqrt(x * x + y * y + z * z);
+    out[0] = x * r; out[1] = y * r; out[2] = z * r;
+}
+// A light the diagonal forms of light_intersect and light_nth_sample may serve (DScene::lightsDiagonal): a RectLight whose m and inv have zero off-diagonal and
+// finite diagonal entries and whose offset's components are finite and NONZERO -- the addition of the offset is what erases the sign of a zero product, and a -0
+// component would keep it.
+#ifndef FRAY_LIGHT_ZERO_OFFSET_OK
+#define FRAY_LIGHT_ZERO_OFFSET_OK 0    // tests/native/shade_shortcut_check.cpp builds a second time with 1 to show that it sees what the rule is there for
+#endif
+inline bool light_is_diagonal(const frayhip_light& l)
+{
+    bool ok = l.kind == FRAYHIP_LIGHT_RECT;
+    for (int k = 0; k < 9; k++) {
+        const bool diag = k == 0 || k == 4 || k == 8;
+        ok = ok && (diag ? std::isfinite(l.T.m[k]) && std::isfinite(l.T.invM[k]) : l.T.m[k] == 0.0 && l.T.invM[k] == 0.0);
+    }
+    for (int k = 0; k < 3; k++) ok = ok && std::isfinite(l.T.offset[k]) && (FRAY_LIGHT_ZERO_OFFSET_OK || l.T.offset[k] != 0.0);
+    return ok;
+}
 inline bool arena_keeps_tris(const DMesh& M) { return !M.hasKd && M.nTris > 0 && M.nTris <= FRAY_GATECERT_MAX_TRIS; }
 inline void fill_editable(const frayhip_scene_desc& d, const ArenaMeshTables* meshTables, ArenaFacts& F, unsigned char* const* tab)
 {
@@ -177,7 +203,10 @@ inline void fill_editable(const frayhip_scene_desc& d, const ArenaMeshTables* me
     for (int i = 0; i < d.n_lights; i++) {
         const frayhip_light& l = d.lights[i];
         DLight& o = lights[i];
-        o.kind = l.kind; o.xSubd = l.xSubd; o.ySubd = l.ySubd; o.pad = 0;
+        o.kind = l.kind; o.xSubd = l.xSubd; o.ySubd = l.ySubd;
+        o.xShift = -1;                                                   // light_nth_sample's cell by mask and shift
+        if (l.kind == FRAYHIP_LIGHT_RECT && l.xSubd > 0 && (l.xSubd & (l.xSubd - 1)) == 0)
+            for (o.xShift = 0; (1 << o.xShift) < l.xSubd;) o.xShift++;
         memcpy(o.color, l.color, sizeof o.color);
         o.power = l.power;
         put3(o.pos, l.pos);
@@ -396,6 +425,31 @@ inline void fill_editable(const frayhip_scene_desc& d, const ArenaMeshTables* me
         memcpy(tab[F.tCamSkip], recs, sizeof recs);
     }
     F.nCamSkip = nCamSkip;
+    // Shade shortcuts (frayhip_scene_shade_shortcuts; dev_scene.hpp DScene::shadeIdentity, lightsDiagonal).  The world-normal table: for every node that is an
+    // untransformed flat mesh kept with its triangles (arena_keeps_tris), whose shader reads no (u, v) and which has no bump texture, entry i * normStride + t is
+    // what finalize_hit makes of triangle t's normal; every other entry is zero.  shadeIdentity: every node is such a node.
+    {
+        const size_t entries = (size_t)d.n_nodes * (size_t)F.normStride;
+        double* const wn = (double*)tab[F.tWorldNormals];
+        if (entries) memset(wn, 0, entries * 3 * sizeof(double));
+        bool all = entries > 0;
+        for (int i = 0; i < d.n_nodes && entries; i++) {
+            const DNode& N = nodes[i];
+            bool ok = N.xfIdentity && N.geomKind == FRAYHIP_GEOM_MESH && N.bumpTex < 0 && !shaders[N.shader].usesUV;
+            if (ok) { const DMesh& M = meshes[N.geomIndex]; ok = arena_keeps_tris(M) && !M.smooth && M.nTris <= F.normStride; }
+            all = all && ok;
+            if (!ok) continue;
+            const DTri* const tris = (const DTri*)tab[meshTables[N.geomIndex].tris];
+            for (int t = 0; t < meshes[N.geomIndex].nTris; t++) world_normal(tris[t].g, N.T.m, wn + 3 * ((size_t)i * F.normStride + t));
+        }
+        F.shadeIdentity = all ? 1 : 0;
+    }
+    // lightsDiagonal: every light is one light_is_diagonal accepts
+    {
+        bool all = d.n_lights > 0;
+        for (int i = 0; i < d.n_lights; i++) all = all && light_is_diagonal(d.lights[i]);
+        F.lightsDiagonal = all ? 1 : 0;
+    }
     if (!nodes.empty()) memcpy(tab[F.tNodes], nodes.data(), nodes.size() * sizeof(DNode));
     if (!tex.empty()) memcpy(tab[F.tTex], tex.data(), tex.size() * sizeof(DTexture));
 
@@ -578,6 +632,12 @@ inline void arena_build(const frayhip_scene_desc& d, ArenaBuilt& B)
     if (!meshes.empty()) memcpy(A.host.data() + oMeshes, meshes.data(), meshes.size() * sizeof(DMesh));
     A.reserve(FRAY_CAMSKIP_MAX * sizeof(DCamSkip));                           // the first bounce's miss records (DCamSkip): last, so that every other table stands where it stood
     F.tCamSkip = A.last();
+    // the world-normal table of the shade shortcuts (fill_editable): one entry per node and triangle, FRAY_GATECERT_MAX_TRIS triangles per node -- what a mesh kept
+    // with its triangles has at most; a node's geometry is editable, and like every editable table this one does not grow with a mesh.  After every other table,
+    // which stand where they stood.  None for a scene of more than 4096 nodes (3 MiB; finalize_hit indexes it with 32-bit arithmetic).
+    F.normStride = d.n_nodes <= 4096 ? FRAY_GATECERT_MAX_TRIS : 0;
+    A.reserve((size_t)d.n_nodes * (size_t)F.normStride * 3 * sizeof(double));
+    F.tWorldNormals = A.last();
 
     F.nNodes = d.n_nodes; F.nLights = d.n_lights; F.nMeshes = d.n_meshes; F.nTextures = d.n_textures;
     F.envPresent = d.environment.present;
@@ -610,7 +670,7 @@ inline void arena_update(const frayhip_scene_desc& d, ArenaBuilt& B)
 // the tables arena_update writes: none of them grows with a mesh or with the texel pool
 inline std::vector<int32_t> arena_editable_tables(const ArenaFacts& F)
 {
-    return {F.tNodes, F.tNodesX, F.tGates, F.tSegPlanes, F.tSegMasks, F.tPlanes, F.tSpheres, F.tCubes, F.tShaders, F.tLayers, F.tLights, F.tTex, F.tCamSkip};
+    return {F.tNodes, F.tNodesX, F.tGates, F.tSegPlanes, F.tSegMasks, F.tPlanes, F.tSpheres, F.tCubes, F.tShaders, F.tLayers, F.tLights, F.tTex, F.tCamSkip, F.tWorldNormals};
 }
 
 // write[t]: where table t can be written now (the staging copy, or the table itself); addr[t]: where the kernels, or the host harness, will find it.
@@ -645,6 +705,8 @@ inline void arena_place(const ArenaFacts& F, const ArenaMeshTables* meshTables, 
     S.nSegPlanes = F.nSegPlanes; S.nSegNodes = F.nSegNodes; S.segCertAll = F.segCertAll;
     S.camSkip = (const FRAY_RO DCamSkip*)addr[F.tCamSkip];
     S.nCamSkip = F.nCamSkip; S.padCamSkip = 0;
+    S.worldNormals = (const FRAY_RO double*)addr[F.tWorldNormals];
+    S.normStride = F.normStride; S.shadeIdentity = F.shadeIdentity; S.lightsDiagonal = F.lightsDiagonal; S.subdShift = 1;
     S.planes = (const FRAY_RO DPlane*)addr[F.tPlanes];
     S.spheres = (const FRAY_RO DSphere*)addr[F.tSpheres];
     S.cubes = (const FRAY_RO DCube*)addr[F.tCubes];

@@ -832,6 +832,14 @@ class Scene:
         _check(lib.frayhip_scene_camera_skip(self._dev, -1 if enable is None else int(bool(enable)), C.byref(on), C.byref(n), C.byref(skipped), C.byref(waves)))
         return int(on.value), int(n.value), int(skipped.value), int(waves.value)
 
+    def shade_shortcuts(self, enable=None):
+        """frayhip_scene_shade_shortcuts: switches the shading shortcuts on or off (None leaves the switch alone) and returns (enabled, eligible): bit 0 of eligible --
+        every node is an untransformed flat mesh, shaded without its transform and with a stored world normal; bit 1 -- every light is an axis-scaled RectLight."""
+        self._need_dev()
+        on, el = C.c_int64(0), C.c_int64(0)
+        _check(lib.frayhip_scene_shade_shortcuts(self._dev, -1 if enable is None else int(bool(enable)), C.byref(on), C.byref(el)))
+        return int(on.value), int(el.value)
+
     def get_option(self, name):
         """frayhip_scene_get_option: an option's value, or a figure of the last frame ("fans_filed", "fan_children", "fan_children_looked_up", "fans_given_up", "contracted_launches", "shadow_segments",
         "shadow_segments_certified", "certified_segments_eligible", "segment_plane_nodes", "shadow_nodes_skipped", "seed_table_bytes", "seed_launches", "seed_planes_reused", "batch_lanes")."""

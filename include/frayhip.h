@@ -411,6 +411,18 @@ int  frayhip_scene_tight_gates(frayhip_scene* s, int enable, int64_t* enabled, i
  * number of miss records of the scene, as last uploaded or updated; the last frame's (wave, node) pairs left out; and the first-bounce wave iterations of
  * 64 camera rays that evaluated the records (those with a ray in the frame). */
 int  frayhip_scene_camera_skip(frayhip_scene* s, int enable, int64_t* enabled, int64_t* eligible, int64_t* skipped, int64_t* waves);
+/* Shade shortcuts.  Path tracing, the timed kernels of scenes without Cube / CSG geometry, KD meshes and textures, in both arithmetics: arithmetic whose
+ * result is known before it runs is left out.  Bit 0 of `eligible`, the nodes: EVERY node is an untransformed mesh (offset +0, m = invM = I bit for bit) that is
+ * flat, has no KD-tree, at most 32 triangles, a shader that reads no (u, v) and no bump texture -- a hit is then shaded without the node's transform
+ * (multiplications by 0 and 1) and with the triangle's world normal from a table made at upload.  Bit 1, the lights: every light is a RectLight whose m and invM
+ * have zero off-diagonal and finite diagonal entries and whose offset has three finite nonzero components (scaled along the axes and translated, not rotated)
+ * -- its intersection and its samples use the three diagonal products; a light whose xSubd is a power of two finds a sample's cell by mask and shift.  Every
+ * value that leaves the changed functions is the same bit for bit (the proofs: fray_amd/csrc/dev_shade.hpp finalize_hit, light_nth_sample; dev_trace.hpp
+ * light_intersect), so the picture is (tests/test_gpu_shade_shortcuts.py).  On by default; the environment variable FRAYHIP_SHADE_SHORTCUTS=0 presets it off at
+ * frayhip_scene_create.  The counting kernels take the general forms.
+ * enable: 1 / 0 switches it on / off (not while the scene renders), -1 leaves it.  enabled, eligible (either may be null): the switch, and the two bits of the
+ * scene as last uploaded or updated. */
+int  frayhip_scene_shade_shortcuts(frayhip_scene* s, int enable, int64_t* enabled, int64_t* eligible);
 
 /* Threads: a frayhip_scene renders one frame at a time (it owns one workspace and one set of
  * counters), as the reference calls render() from one thread at a time (main.cpp:407-412,448);
