@@ -26,7 +26,7 @@ src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --he
                                                                                          (the sequence with a probe of K samples per frame that finds
                                                                                           what the move changed in the light -- the node's shadow -- and
                                                                                           shortens the history there; with or without --split)
-                         python -m fray_amd scene.fray -o out.bmp --refine TOL --max-spp N [--accumulate FILE.npz] [--noise-out FILE.npy] [--denoise]
+                         python -m fray_amd scene.fray -o out.bmp --refine TOL --max-spp N [--sample-budget N] [--accumulate FILE.npz] [--noise-out FILE.npy] [--denoise]
                                                                                          (samples spent where the frame is noisy: each pixel sampled
                                                                                           until its relative standard error is TOL or it holds N samples;
                                                                                           --denoise: the result filtered with its own noise estimate)
@@ -104,6 +104,9 @@ def build_parser():
                          "samples are kept apart as direct and indirect light (Scene.render_denoised_split(refine=TOL)) and each is filtered on its own")
     ap.add_argument("--max-spp", type=int, metavar="N", help="with --refine: the most samples a pixel may hold (required)")
     ap.add_argument("--refine-passes", type=int, default=8, metavar="P", help="with --refine: the most passes (default 8)")
+    ap.add_argument("--sample-budget", type=int, metavar="N",
+                    help="with --refine: the most samples the passes may add over the whole frame (Scene.refine(budget=N)): the tolerance is raised until "
+                         "the frame can afford it; the JSON line gains budget, tolerance_reached and stage")
     ap.add_argument("--components-out", metavar="FILE.npz",
                     help="component frame (Scene.render_components; path-traced mono frames): render the frame's samples with direct and indirect light "
                          "kept apart and save direct, indirect, noise_direct, noise_indirect, samples and seed; the picture is their sum")
@@ -154,8 +157,12 @@ def check_args(ap, a):
             ap.error("--refine with --components-out needs --denoise --split")
         if a.split and a.noise_out:
             ap.error("--refine --split cannot be combined with --noise-out: --components-out saves both components' noise")
+        if a.sample_budget is not None and a.sample_budget < 0:
+            ap.error("--sample-budget must be >= 0")
     elif a.max_spp is not None:
         ap.error("--max-spp needs --refine")
+    elif a.sample_budget is not None:
+        ap.error("--sample-budget needs --refine")
     if a.frames is not None and not a.denoise and not a.move:
         ap.error("--frames needs --denoise: a sequence is rendered with temporal accumulation and the filter")
     if a.move and a.frames is None:
@@ -202,6 +209,11 @@ def check_components(ap, a, s):
         ap.error("%s needs a path-traced scene (gi on): a Whitted frame has no direct / indirect split" % flag)
     if s.camera.stereoSeparation > 0:
         ap.error("%s is not offered for stereo frames" % flag)
+
+
+def budget_fields(info):
+    """What --sample-budget adds to --refine's JSON line (nothing without it)."""
+    return {k: info[k] for k in ("budget", "tolerance_reached", "stage") if k in info}
 
 
 def check_refine(ap, a, s):
@@ -319,11 +331,11 @@ def main(argv=None):
         return 0
     if a.refine is not None and a.split:
         img, raw, info = s.render_denoised_split(seed=a.seed, feature_samples=a.feature_samples, refine=a.refine, max_count=a.max_spp,
-                                                 passes=a.refine_passes)
+                                                 passes=a.refine_passes, budget=a.sample_budget)
         st = info["render"]
         held = info["refine"]["counts"]
-        print(json.dumps({"passes": st["passes"], "samples": st["samples"], "mean_spp": float(held.mean()), "min_spp": int(held.min()),
-                          "max_spp": int(held.max())}))
+        print(json.dumps(dict({"passes": st["passes"], "samples": st["samples"], "mean_spp": float(held.mean()), "min_spp": int(held.min()),
+                               "max_spp": int(held.max())}, **budget_fields(st))))
         spp_text = "refined to tolerance %g, mean %.2f spp, direct and indirect light denoised apart: features %.1f ms, filters %.1f + %.1f ms" % (
             a.refine, held.mean(), info["features"]["ms_kernels"], info["denoise_direct"]["ms_kernels"], info["denoise_indirect"]["ms_kernels"])
         if a.features_out:
@@ -333,11 +345,11 @@ def main(argv=None):
                             int(held.max()), a.seed)
     elif a.refine is not None:
         from . import denoise_signal
-        img, state, noise, info = s.refine(state, a.refine, a.max_spp, passes=a.refine_passes, seed=a.seed)
+        img, state, noise, info = s.refine(state, a.refine, a.max_spp, passes=a.refine_passes, seed=a.seed, budget=a.sample_budget)
         held = state.count_plane()
         st = info
-        print(json.dumps({"passes": info["passes"], "samples": info["samples"], "mean_spp": float(held.mean()), "min_spp": int(held.min()),
-                          "max_spp": int(held.max())}))
+        print(json.dumps(dict({"passes": info["passes"], "samples": info["samples"], "mean_spp": float(held.mean()), "min_spp": int(held.min()),
+                               "max_spp": int(held.max())}, **budget_fields(info))))
         spp_text = "refined to tolerance %g, mean %.2f spp" % (a.refine, held.mean())
         if a.accumulate:
             print("wrote", state.save(a.accumulate))

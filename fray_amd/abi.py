@@ -193,6 +193,11 @@ class SampleMap(C.Structure):
                 ("pixels", u64), ("samples", u64)]
 
 
+# struct frayhip_sample_budget (frayhip_sample_map_budget's second struct; a tag without a typedef as well)
+class SampleBudget(C.Structure):
+    _fields_ = [("budget", u64), ("demand", u64), ("tolerance_used", C.c_float), ("cap_used", i32), ("stage", i32), ("reserved", i32)]
+
+
 # struct frayhip_denoise (a struct tag without a typedef: the name is also the entry point's, so it is not in STRUCTS, which mirrors the typedefs)
 class Denoise(C.Structure):
     _fields_ = [("levels", i32), ("demodulate", i32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float),
@@ -275,6 +280,8 @@ SYMBOLS = {
     "frayhip_sample_map_device": (C.c_int, [C.c_int, C.c_int, VP, VP, P(SampleMap), VP, VP, P(Stats)]),
     "frayhip_sample_map_pair": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(SampleMap), VP, P(Stats)]),
     "frayhip_sample_map_pair_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(SampleMap), VP, VP, P(Stats)]),
+    "frayhip_sample_map_budget": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(SampleMap), P(SampleBudget), VP, P(Stats)]),
+    "frayhip_sample_map_budget_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(SampleMap), P(SampleBudget), VP, VP, P(Stats)]),
     "frayhip_render_features": (C.c_int, [VP, P(Frame), C.c_int, VP, P(Stats)]),
     "frayhip_render_features_device": (C.c_int, [VP, P(Frame), C.c_int, VP, VP, P(Stats)]),
     "frayhip_render_features_motion": (C.c_int, [VP, P(Frame), C.c_int, P(Transform), C.c_int, VP, VP, P(Stats)]),

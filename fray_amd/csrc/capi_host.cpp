@@ -121,6 +121,7 @@ int frayhip_sizeof(const char* n)
     if (!strcmp(n, "frayhip_temporal")) return (int)sizeof(struct frayhip_temporal);
     if (!strcmp(n, "frayhip_change")) return (int)sizeof(struct frayhip_change);
     if (!strcmp(n, "frayhip_sample_map")) return (int)sizeof(struct frayhip_sample_map);
+    if (!strcmp(n, "frayhip_sample_budget")) return (int)sizeof(struct frayhip_sample_budget);
 #undef FRAYHIP_SZ
     return -1;
 }

@@ -6,7 +6,7 @@
 // (tests/sample_map_ref.py restates it in numpy, and the two agree bit for bit).
 //
 //   k_sample_map<PAIR>   per pixel: k_acc_mean's mean and noise at the pixel's own N (PAIR: of both states, added), the count at which that noise
-//                        would meet the tolerance, the caps
+//                        would meet the tolerance, the caps (the formula itself: samplemap_formula.hpp, shared with samplemap_budget.hip)
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -15,6 +15,7 @@
 #include <string>
 
 #include "entry_support.hpp"
+#include "samplemap_formula.hpp"
 #include "temporal_common.hpp"
 
 struct SampleMapArgs {
@@ -28,15 +29,6 @@ struct SampleMapArgs {
     unsigned long long* totals; // [0] pixels with add > 0, [1] the sum of add
 };
 
-// k_acc_mean's mean luminance and noise of one row at N samples
-__device__ __forceinline__ void sm_row(const float4 row, int N, float fn, float& lbar, float& noise)
-{
-    const float mr = row.x / fn, mg = row.y / fn, mb = row.z / fn;
-    lbar = tp_lum(mr, mg, mb);
-    const float v = fmaxf(0.0f, row.w / fn - lbar * lbar);
-    noise = N >= 2 ? v / (float)(N - 1) : lbar * lbar;
-}
-
 template <bool PAIR>
 static __global__ __launch_bounds__(256) void k_sample_map(SampleMapArgs A)
 {
@@ -48,25 +40,9 @@ static __global__ __launch_bounds__(256) void k_sample_map(SampleMapArgs A)
         const int N = A.count[p];
         int add = 0;
         if (N < A.maxCount) {
-            int target;
-            if (N < A.minCount) target = A.minCount;
-            else {
-                const float fn = (float)N;
-                float lbar, noise;
-                sm_row(A.accum[p], N, fn, lbar, noise);
-                if (PAIR) {          // the components are separate signals to the split filter, and their errors add in the final sum
-                    float lbarI, noiseI;
-                    sm_row(A.accum2[p], N, fn, lbarI, noiseI);
-                    lbar = lbar + lbarI;
-                    noise = noise + noiseI;
-                }
-                const float ref = fmaxf(lbar, A.lumFloor);
-                const float t = A.tolerance * ref;
-                const float need = ceilf(fn * (noise / (t * t)));
-                target = need <= (float)A.maxCount ? max(N, (int)need) : A.maxCount;     // a NaN need asks for max_count: never stops a pixel early
-                target = min(target, A.grow * N);
-            }
-            add = min(min(target, A.maxCount) - N, A.maxAdd);
+            float noise = 0.0f, ref = 0.0f;
+            if (N >= A.minCount) sm_reduce<PAIR>(A.accum, A.accum2, p, N, A.lumFloor, noise, ref);
+            add = sm_add(N, noise, ref, A.tolerance, A.minCount, A.maxCount, A.maxAdd, A.grow);
         }
         A.add[p] = add;
         if (add > 0) { tPix++; tSum += (unsigned long long)add; }
@@ -80,44 +56,8 @@ namespace {
 
 using namespace frayhip_detail;
 using namespace frayhip_temporal_detail;
-
-constexpr int kMaxCount = 1 << 24;
-
-// Every check of both entries, in this order; none touches the device
-// (pair: accum is the direct state and accum2 the indirect one)
-int check(const char* who, int W, int H, const float* accum, const float* accum2, bool pair, const int32_t* count, const struct frayhip_sample_map* p,
-          const int32_t* add, bool device)
-{
-    if (W < 1 || H < 1) return bad(who, "width and height must be >= 1");
-    if ((long long)W * H > (1ll << 30)) return bad(who, "more than 2^30 pixels");
-    if (!accum) return bad(who, pair ? "null accum_direct" : "null accum");
-    if (pair && !accum2) return bad(who, "null accum_indirect");
-    if (!count) return bad(who, "null count");
-    if (!p) return bad(who, "null parameters");
-    if (!add) return bad(who, "null add");
-    if (!std::isfinite(p->tolerance) || !(p->tolerance > 0)) return bad(who, "tolerance must be finite and > 0");
-    if (!std::isfinite(p->lum_floor) || !(p->lum_floor > 0)) return bad(who, "lum_floor must be finite and > 0");
-    if (p->min_count < 1) return bad(who, "min_count must be >= 1");
-    if (p->max_count < p->min_count) return bad(who, "max_count must be >= min_count");
-    if (p->max_count > kMaxCount) return bad(who, "max_count must be <= 2^24");
-    if (p->max_add < 1) return bad(who, "max_add must be >= 1");
-    if (p->grow < 2 || p->grow > 16) return bad(who, "grow must be 2..16");
-    if (device) {
-        if (misaligned(accum, 16) || (pair && misaligned(accum2, 16))) return bad(who, "device pointer to the state not 16-byte aligned");
-        if (misaligned(count, 4) || misaligned(add, 4)) return bad(who, "device pointer to a plane not 4-byte aligned");
-    }
-    const size_t n = (size_t)W * H;
-    if (overlaps(add, 4 * n, accum, 16 * n) || overlaps(add, 4 * n, count, 4 * n)) return bad(who, "add must not overlap an input");
-    if (pair) {
-        if (overlaps(add, 4 * n, accum2, 16 * n)) return bad(who, "add must not overlap an input");
-        if (overlaps(accum2, 16 * n, accum, 16 * n)) return bad(who, "accum_indirect must not overlap accum_direct");
-        if (overlaps(count, 4 * n, accum, 16 * n)) return bad(who, "count must not overlap accum_direct");
-        if (overlaps(count, 4 * n, accum2, 16 * n)) return bad(who, "count must not overlap accum_indirect");
-        return FRAYHIP_OK;
-    }
-    if (overlaps(count, 4 * n, accum, 16 * n)) return bad(who, "count must not overlap accum");
-    return FRAYHIP_OK;
-}
+using frayhip_samplemap_detail::check;
+using frayhip_samplemap_detail::kMaxCount;
 
 // The device path of both entries (device pointers, checked).  A negative count is read as a pixel below min_count.
 int run(int W, int H, const float* accum, const float* accum2, const int32_t* count, struct frayhip_sample_map* p, int32_t* add, hipStream_t stream, frayhip_stats* st,

@@ -332,7 +332,22 @@ def sample_map_params(**params):
     return p
 
 
-def sample_map(state, stats=False, stream=None, **params):
+def _budget_of(who, budget):
+    """A frame-wide sample budget as the library takes it: None, or an integer 0 .. 2^64 - 1 (bool and float are refused)."""
+    if budget is None:
+        return None
+    if isinstance(budget, bool) or not isinstance(budget, (int, np.integer)):
+        raise TypeError("%s: budget must be an integer or None, got %s" % (who, type(budget).__name__))
+    if not (0 <= int(budget) < 1 << 64):
+        raise ValueError("%s: budget must be 0 .. 2^64 - 1, got %d" % (who, int(budget)))
+    return int(budget)
+
+
+def _budget_info(info, b):
+    info.update(budget=int(b.budget), demand=int(b.demand), tolerance_used=float(b.tolerance_used), cap_used=int(b.cap_used), stage=int(b.stage))
+
+
+def sample_map(state, stats=False, stream=None, budget=None, **params):
     """The sample map of a state (frayhip_sample_map): how many more samples each pixel of the Accumulation `state` needs before the standard error
     of its mean's luminance is `tolerance` times that luminance, every pixel brought to min_count first and none past max_count (params: see
     sample_map_params; the formula is in include/frayhip.h "sample maps").  A numpy state goes through the host entry, a state on the GPU through
@@ -340,25 +355,41 @@ def sample_map(state, stats=False, stream=None, **params):
     Scene.render_samples_map takes -- and info {"pixels": pixels with add > 0, "samples": the sum of add}, both over the whole frame, with
     "stats" (ms_total, ms_kernels) when stats=True.
     state may also be a pair (direct, indirect) of component states holding the same samples (Scene.render_components_map): the map then comes from
-    frayhip_sample_map_pair, which adds the two components' mean luminances and their noise estimates, and is what render_components_map takes."""
+    frayhip_sample_map_pair, which adds the two components' mean luminances and their noise estimates, and is what render_components_map takes.
+    budget: None, or the most samples the map may hand out over the whole frame, an int >= 0 (frayhip_sample_map_budget: the tolerance is raised
+    until the frame can afford it, and where no tolerance is enough a per-pixel cap is lowered; include/frayhip.h has the three stages).  info then
+    gains "budget", "demand" (what `tolerance` asked for), "tolerance_used", "cap_used" (-1: none) and "stage"; "samples" <= budget."""
     who = "sample_map"
+    budget = _budget_of(who, budget)
     if isinstance(state, (tuple, list)):
-        return _sample_map_pair(who, state, stats, stream, params)
+        return _sample_map_pair(who, state, stats, stream, params, budget)
     if not isinstance(state, Accumulation):
         raise TypeError("%s: state must be an Accumulation, got %s" % (who, type(state).__name__))
     p = sample_map_params(**params)
     state.check(who, state.size, state.seed, state.bucket_first, state.bucket_stride)
+    if budget is not None and state.bucket_stride != 1:
+        raise ValueError("%s: budget with a bucket share (bucket_stride %d): the map's totals are frame-wide, so a share cannot own a budget" % (who, state.bucket_stride))
     W, H = state.size
     count = state.count_plane()
     st = abi.Stats()
+    b = abi.SampleBudget(budget=budget or 0)
     if not state.on_device:
         add = np.zeros((H, W), np.int32)
-        _check(lib.frayhip_sample_map(W, H, _ptr(state.state), _ptr(count), C.byref(p), _ptr(add), C.byref(st)))
+        if budget is None:
+            _check(lib.frayhip_sample_map(W, H, _ptr(state.state), _ptr(count), C.byref(p), _ptr(add), C.byref(st)))
+        else:
+            _check(lib.frayhip_sample_map_budget(W, H, _ptr(state.state), None, _ptr(count), C.byref(p), C.byref(b), _ptr(add), C.byref(st)))
     else:
         with _DeviceCall(state.state.device, stream) as call:
             add = call.torch.zeros((H, W), dtype=call.torch.int32, device=state.state.device)
-            _check(lib.frayhip_sample_map_device(W, H, _ptr(state.state), _ptr(count), C.byref(p), _ptr(add), call.handle, C.byref(st)))
+            if budget is None:
+                _check(lib.frayhip_sample_map_device(W, H, _ptr(state.state), _ptr(count), C.byref(p), _ptr(add), call.handle, C.byref(st)))
+            else:
+                _check(lib.frayhip_sample_map_budget_device(W, H, _ptr(state.state), None, _ptr(count), C.byref(p), C.byref(b), _ptr(add), call.handle,
+                                                            C.byref(st)))
     info = {"pixels": int(p.pixels), "samples": int(p.samples)}
+    if budget is not None:
+        _budget_info(info, b)
     if stats:
         info["stats"] = st.as_dict()
     return add, info
@@ -384,22 +415,34 @@ def _component_pair(who, state, size, seed, bucket_first, bucket_stride):
     return sd, si, cd
 
 
-def _sample_map_pair(who, state, stats, stream, params):
-    """sample_map of a pair of component states (frayhip_sample_map_pair)."""
+def _sample_map_pair(who, state, stats, stream, params, budget=None):
+    """sample_map of a pair of component states (frayhip_sample_map_pair; under a budget frayhip_sample_map_budget with both states)."""
     if not (len(state) == 2 and all(isinstance(a, Accumulation) for a in state)):
         raise TypeError("%s: state must be an Accumulation or a pair (direct, indirect) of Accumulations" % who)
     p = sample_map_params(**params)
     sd, si, count = _component_pair(who, state, state[0].size, state[0].seed, state[0].bucket_first, state[0].bucket_stride)
+    if budget is not None and sd.bucket_stride != 1:
+        raise ValueError("%s: budget with a bucket share (bucket_stride %d): the map's totals are frame-wide, so a share cannot own a budget" % (who, sd.bucket_stride))
     W, H = sd.size
     st = abi.Stats()
+    b = abi.SampleBudget(budget=budget or 0)
     if not sd.on_device:
         add = np.zeros((H, W), np.int32)
-        _check(lib.frayhip_sample_map_pair(W, H, _ptr(sd.state), _ptr(si.state), _ptr(count), C.byref(p), _ptr(add), C.byref(st)))
+        if budget is None:
+            _check(lib.frayhip_sample_map_pair(W, H, _ptr(sd.state), _ptr(si.state), _ptr(count), C.byref(p), _ptr(add), C.byref(st)))
+        else:
+            _check(lib.frayhip_sample_map_budget(W, H, _ptr(sd.state), _ptr(si.state), _ptr(count), C.byref(p), C.byref(b), _ptr(add), C.byref(st)))
     else:
         with _DeviceCall(sd.state.device, stream) as call:
             add = call.torch.zeros((H, W), dtype=call.torch.int32, device=sd.state.device)
-            _check(lib.frayhip_sample_map_pair_device(W, H, _ptr(sd.state), _ptr(si.state), _ptr(count), C.byref(p), _ptr(add), call.handle, C.byref(st)))
+            if budget is None:
+                _check(lib.frayhip_sample_map_pair_device(W, H, _ptr(sd.state), _ptr(si.state), _ptr(count), C.byref(p), _ptr(add), call.handle, C.byref(st)))
+            else:
+                _check(lib.frayhip_sample_map_budget_device(W, H, _ptr(sd.state), _ptr(si.state), _ptr(count), C.byref(p), C.byref(b), _ptr(add), call.handle,
+                                                            C.byref(st)))
     info = {"pixels": int(p.pixels), "samples": int(p.samples)}
+    if budget is not None:
+        _budget_info(info, b)
     if stats:
         info["stats"] = st.as_dict()
     return add, info
@@ -1233,15 +1276,22 @@ class Scene:
         out = (rgb, state) + ((var,) if noise else ())
         return out + ((st.as_dict(),) if stats else ())
 
-    def refine(self, state, tolerance, max_count, passes=8, seed=42, bucket_first=0, bucket_stride=1, spp_chunk=0, stream=None, split=False, **params):
+    def refine(self, state, tolerance, max_count, passes=8, seed=42, bucket_first=0, bucket_stride=1, spp_chunk=0, stream=None, split=False, budget=None,
+               **params):
         """Spends samples where the frame needs them: up to `passes` times, sample_map(state, tolerance=..., max_count=..., **params) and
         render_samples_map of its map; stops when a map is empty.  state: an Accumulation (None starts a numpy one; the first pass then brings
         every pixel to min_count).  Returns (rgb, state, noise, info): the frame, the state, the variance estimate of the mean's luminance --
         denoise_signal's `variance` with demodulate=0 -- and info {"passes": passes that rendered, "samples": samples they added, "ms_kernels":
         their kernel time}.
         With a pair (direct, indirect) of component states, or split=True and state=None (a numpy pair is started), the loop runs the pair's
-        sample_map and render_components_map and returns (direct_rgb, indirect_rgb, state, noise_direct, noise_indirect, info)."""
+        sample_map and render_components_map and returns (direct_rgb, indirect_rgb, state, noise_direct, noise_indirect, info).
+        budget: None, or the most samples the whole call may add, an int >= 0: each pass asks sample_map for a map under what is left of it, and
+        the loop also ends when nothing is left.  info then gains "budget", "tolerance_reached" (the last map's tolerance_used; `tolerance` when no
+        map was made) and "stage" (that map's).  A budget with bucket_stride != 1 is refused (ValueError): the map's totals are frame-wide."""
         W, H = self.frame_size
+        budget = _budget_of("refine", budget)
+        if budget is not None and bucket_stride != 1:
+            raise ValueError("refine: budget with a bucket share (bucket_stride %d): the map's totals are frame-wide, so a share cannot own a budget" % bucket_stride)
         pair = isinstance(state, (tuple, list)) or (state is None and split)
         if split and not pair:
             raise TypeError("refine: split=True takes a pair (direct, indirect) of Accumulations, or None")
@@ -1250,9 +1300,16 @@ class Scene:
             state = (new(), new()) if pair else new()
         step = self.render_components_map if pair else self.render_samples_map
         done = {"passes": 0, "samples": 0, "ms_kernels": 0.0}
+        if budget is not None:
+            done.update(budget=budget, tolerance_reached=float(np.float32(tolerance)), stage=0)
         out = None
         for _ in range(int(passes)):
-            add, info = sample_map(state, stream=stream, tolerance=tolerance, max_count=max_count, **params)
+            left = None if budget is None else budget - done["samples"]
+            if left == 0:
+                break
+            add, info = sample_map(state, stream=stream, tolerance=tolerance, max_count=max_count, budget=left, **params)
+            if left is not None:
+                done["tolerance_reached"], done["stage"] = info["tolerance_used"], info["stage"]
             if info["pixels"] == 0:
                 break
             out = step(add, state, seed, bucket_first, bucket_stride, spp_chunk, stats=True, noise=True, stream=stream)
@@ -1401,7 +1458,7 @@ class Scene:
         out, dst = denoise(raw, feat, half, stats=True, **params)
         return out, raw, {"render": rst, "features": fst, "denoise": dst, "rgb_half": half, "features_frame": feat}
 
-    def render_denoised_split(self, seed=42, feature_samples=4, refine=None, max_count=None, passes=8, **params):
+    def render_denoised_split(self, seed=42, feature_samples=4, refine=None, max_count=None, passes=8, budget=None, **params):
         """A frame whose direct and indirect light are filtered apart: (denoised, raw, info).  The components of the frame's spp samples come from
         render_components with their noise estimates, each goes through denoise_signal with the feature frame (demodulate=0: the states' noise is
         in rgb's domain) and the two results are added in FP32.  raw = direct_rgb + indirect_rgb.  params: denoise_params, but demodulate=1 is
@@ -1409,9 +1466,12 @@ class Scene:
         "direct" and "indirect", and their inputs "direct_rgb", "indirect_rgb", "noise_direct", "noise_indirect" and "features_frame".
         refine=TOL: the components come from Scene.refine on a new pair of states instead (tolerance TOL, at most max_count samples in a pixel --
         required -- and at most `passes` passes); "render" is then refine's info, info gains "refine" (that info with "counts", the int32 [H, W]
-        plane of samples held) and the features take min(feature_samples, the largest count) samples."""
+        plane of samples held) and the features take min(feature_samples, the largest count) samples.  budget: refine's frame-wide sample
+        budget (it needs refine)."""
         if refine is None and max_count is not None:
             raise ValueError("render_denoised_split: max_count needs refine")
+        if refine is None and budget is not None:
+            raise ValueError("render_denoised_split: budget needs refine")
         if refine is not None and max_count is None:
             raise ValueError("render_denoised_split: refine needs max_count")
         if params.get("demodulate", 0):
@@ -1424,7 +1484,7 @@ class Scene:
             spp = self.samples_per_pixel()
             d_rgb, i_rgb, _state, d_noise, i_noise, rst = self.render_components(spp, seed=seed, noise=True, stats=True)
         else:
-            d_rgb, i_rgb, state, d_noise, i_noise, rst = self.refine(None, refine, max_count, passes=passes, seed=seed, split=True)
+            d_rgb, i_rgb, state, d_noise, i_noise, rst = self.refine(None, refine, max_count, passes=passes, seed=seed, split=True, budget=budget)
             held = state[0].count_plane()
             spp = max(int(held.max()), 1)
             extra["refine"] = dict(rst, counts=held)

@@ -834,6 +834,42 @@ int  frayhip_sample_map_pair(int width, int height, const float* accum_direct, c
 int  frayhip_sample_map_pair_device(int width, int height, const float* d_accum_direct, const float* d_accum_indirect, const int32_t* d_count,
                                     struct frayhip_sample_map* p, int32_t* d_add, void* hip_stream, frayhip_stats* st);
 
+/* The map under a frame-wide sample budget (frayhip_sample_map_budget; samplemap_budget.hip; tests/sample_map_budget_ref.py restates it).
+ * Let A(tau)[p] be the add that frayhip_sample_map gives pixel p with tolerance = tau and every other parameter as passed
+ * (frayhip_sample_map_pair's add when accum_indirect is not NULL), S(tau) the sum of A(tau)[p] over all W*H pixels, tau0 = p->tolerance and
+ * taumax = FLT_MAX.  For a fixed pixel A(tau)[p] does not increase with tau: tolerance * ref, t * t, noise / (t * t), fn * (...) and ceilf are
+ * each correctly rounded and so monotone, the integer steps after them are non-decreasing in need, and a row whose need is NaN or infinite
+ * either asks for max_count at every tau or drops to a finite need once (fray_amd/csrc/samplemap_formula.hpp has the cases).  So S does not
+ * increase either, and for a budget of any value:
+ *   stage 0  S(tau0) <= budget:  add = A(tau0), frayhip_sample_map's plane bit for bit; tolerance_used = tau0, cap_used = -1.
+ *   stage 1  else, S(taumax) <= budget:  tolerance_used = the smallest float tau in (tau0, taumax] with S(tau) <= budget (positive floats are
+ *            ordered as their bit patterns); add = A(tolerance_used), cap_used = -1.  The one tolerance is raised until the frame can afford it:
+ *            the relative error aimed at stays equal across pixels, and the caller learns which error the budget buys.
+ *   stage 2  else -- the demand no tolerance removes (pixels below min_count, rows whose need is NaN or infinite) exceeds the budget:
+ *            tolerance_used = taumax, cap_used = the largest integer c in [0, max_add] with sum min(A(taumax)[p], c) <= budget,
+ *            add = min(A(taumax), cap_used).
+ * p->pixels and p->samples describe the final plane (samples <= budget always); demand = S(tau0).  What stage 1 or stage 2 leaves unspent is
+ * not handed out to other pixels: a stated limit.
+ * Device code: one pass reduces every row to {noise, ref} in a workspace of the call and sums S(tau0) and S(taumax); eight search launches
+ * evaluate 16 candidates each of the tolerance's bit pattern (stage 1) or of the cap (stage 2), each launch deriving its interval from the
+ * totals of those before it in a control block in device memory; a last pass writes add.  Stream order is the only ordering, the call
+ * synchronises once, whatever the data, and every total is an exact integer sum, so the answer depends on neither grid nor timing.
+ * FRAYHIP_E_ARG, before the device is touched: everything frayhip_sample_map (accum_indirect NULL) or frayhip_sample_map_pair refuses, in their
+ * order and words; a NULL b; b->reserved != 0.  Device pointers, the stream contract and *st as frayhip_sample_map_device. */
+struct frayhip_sample_budget {
+    uint64_t budget;          /* in:  the most samples the map may hand out, over all W*H pixels; any value        */
+    uint64_t demand;          /* out: S(tau0), what the tolerance asked for                                        */
+    float    tolerance_used;  /* out: the tolerance the plane was made with                                        */
+    int32_t  cap_used;        /* out: the per-pixel cap of stage 2; -1: none                                       */
+    int32_t  stage;           /* out: 0, 1, 2                                                                      */
+    int32_t  reserved;        /* in:  0                                                                            */
+};
+int  frayhip_sample_map_budget(int width, int height, const float* accum, const float* accum_indirect /* NULL: one state */, const int32_t* count,
+                               struct frayhip_sample_map* p, struct frayhip_sample_budget* b, int32_t* add, frayhip_stats* st);
+int  frayhip_sample_map_budget_device(int width, int height, const float* d_accum, const float* d_accum_indirect /* NULL: one state */,
+                                      const int32_t* d_count, struct frayhip_sample_map* p, struct frayhip_sample_budget* b, int32_t* d_add,
+                                      void* hip_stream, frayhip_stats* st);
+
 /* ---- feature frames (first-hit guides for a denoiser) ---------------------------------------------------------------------------------------
  * For every pixel of the call's buckets (frame.bucket_first / bucket_stride, as frayhip_render; other pixels untouched), the FP32 mean, in
  * sample order, of the first-hit features of the frame's own camera samples 0 .. n_samples - 1: sample i is the film position and the pinhole

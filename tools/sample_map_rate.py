@@ -19,7 +19,17 @@ after --warmup.  Every call adds its samples on top of a state of 4 samples per 
   pair_random_16, pair_tiles_16                    the pair maps of the same add: the same rays, a second row in the resolve and the finish
   sample_map, sample_map_pair                      frayhip_sample_map_device and frayhip_sample_map_pair_device alone
 
-    python tools/sample_map_rate.py [--split] [--rounds 7] [--warmup 2] [--out FILE]"""
+--budget measures the budgeted map instead (frayhip_sample_map_budget_device), on the state of 4 samples per pixel, beside the plain map in the same
+run; the calls alternate round after round.  D = the plain map's samples at the tolerance, F = its samples at tolerance FLT_MAX:
+
+  sample_map        frayhip_sample_map_device (tolerance 0.05, max_count 256)
+  budget_stage0     the budgeted entry with budget D: the prepare pass, eight search launches that return at once, the final pass
+  budget_stage1     budget (D + F) / 2: the search runs over the tolerance's bit pattern
+  budget_stage2     budget F8 / 2 with min_count 8, where F8 = 4 W H is what no tolerance removes (at min_count 4 a state of 4 samples has
+                    F = 0 and no budget reaches stage 2): the search runs over the cap
+  samples_1_over_16 one sixteenth of frayhip_render_samples_device's 16 samples: the sample per pixel the map is steering
+
+    python tools/sample_map_rate.py [--split | --budget] [--rounds 7] [--warmup 2] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -42,7 +52,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out")
     ap.add_argument("--split", action="store_true", help="measure the pair entries (component states under a map) beside the single-state ones")
+    ap.add_argument("--budget", action="store_true", help="measure the budgeted map (frayhip_sample_map_budget_device) at stage 0, 1 and 2 beside the plain map")
     a = ap.parse_args()
+    if a.budget and a.split:
+        ap.error("--budget and --split are separate measurements")
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import torch
@@ -103,6 +116,68 @@ def main():
         if rc:
             sys.exit("frayhip_sample_map_device: %s" % lib.frayhip_last_error().decode())
         return st.ms_kernels, st.ms_total
+
+    if a.budget:
+        import numpy as np
+        reset()
+
+        def plain(**kw):
+            p, st = fray_amd.sample_map_params(**dict(dict(tolerance=0.05, max_count=256), **kw)), abi.Stats()
+            rc = lib.frayhip_sample_map_device(W, H, acc.data_ptr(), count.data_ptr(), C.byref(p), out_add.data_ptr(), h, C.byref(st))
+            if rc:
+                sys.exit("frayhip_sample_map_device: %s" % lib.frayhip_last_error().decode())
+            return p, st
+
+        D = int(plain()[0].samples)
+        F = int(plain(tolerance=float(np.finfo(np.float32).max))[0].samples)
+        F8 = int(plain(tolerance=float(np.finfo(np.float32).max), min_count=8)[0].samples)
+        seen = {}
+
+        def budgeted(name, budget, stage, **kw):
+            def run():
+                p, st = fray_amd.sample_map_params(**dict(dict(tolerance=0.05, max_count=256), **kw)), abi.Stats()
+                b = abi.SampleBudget(budget=budget)
+                rc = lib.frayhip_sample_map_budget_device(W, H, acc.data_ptr(), None, count.data_ptr(), C.byref(p), C.byref(b), out_add.data_ptr(), h, C.byref(st))
+                if rc:
+                    sys.exit("frayhip_sample_map_budget_device: %s" % lib.frayhip_last_error().decode())
+                assert b.stage == stage and p.samples <= budget, (name, b.stage, p.samples, budget)
+                seen[name] = {"budget": budget, "demand": int(b.demand), "samples": int(p.samples), "pixels": int(p.pixels), "stage": int(b.stage),
+                              "tolerance_used": float(b.tolerance_used), "cap_used": int(b.cap_used)}
+                return st.ms_kernels, st.ms_total
+            return run
+
+        def plain_map():
+            _, st = plain()
+            return st.ms_kernels, st.ms_total
+
+        def samples_then_reset():
+            v = samples()
+            reset()
+            return v
+
+        calls = [("sample_map", plain_map), ("budget_stage0", budgeted("budget_stage0", D, 0)), ("budget_stage1", budgeted("budget_stage1", (D + F) // 2, 1)),
+                 ("budget_stage2", budgeted("budget_stage2", F8 // 2, 2, min_count=8)), ("samples_16", samples_then_reset)]
+        times = {k: [] for k, _ in calls}
+        for r in range(a.warmup + a.rounds):
+            for k, fn in calls:
+                v = fn()
+                if r >= a.warmup:
+                    times[k].append(v)
+        res = {k: med(v) for k, v in times.items()}
+        res["spread_kernels_ms"] = {k: [min(x[0] for x in v), max(x[0] for x in v)] for k, v in times.items()}
+        res["samples_1_over_16"] = {"kernels_ms": res["samples_16"]["kernels_ms"] / ADD}
+        res["maps"] = dict(seen, D=D, F=F, F8=F8)
+        one = res["samples_1_over_16"]["kernels_ms"]
+        res["ratios"] = {k + "_over_one_sample_per_pixel": res[k]["kernels_ms"] / one for k in ("sample_map", "budget_stage0", "budget_stage1", "budget_stage2")}
+        for k, _ in calls:
+            print("%-15s kernels %8.3f ms  call %8.3f ms" % (k, res[k]["kernels_ms"], res[k]["call_ms"]), flush=True)
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        s.close()
+        return
 
     if a.split:
         with torch.cuda.stream(stream):
