@@ -34,7 +34,7 @@ ST_OBJ   := $(foreach set,$(ST_SETS),$(foreach st,$(ST_WORDS),fray_amd/csrc/$(fi
 # render_contract.hip: the path tracer's bounce / shadow kernels once more per flag word, built with fused multiply-adds (option "fp_contract")
 CONTRACT_OBJ := $(foreach st,0 1 4 5 8 9,fray_amd/csrc/variantC$(st).o)
 HIP_OBJ  := fray_amd/csrc/capi.o fray_amd/csrc/capi_comm.o fray_amd/csrc/capi_query.o fray_amd/csrc/capi_shade.o fray_amd/csrc/capi_adaptive.o fray_amd/csrc/capi_samplemap.o \
-            fray_amd/csrc/capi_features.o fray_amd/csrc/denoise.o fray_amd/csrc/temporal.o fray_amd/csrc/temporal_split.o fray_amd/csrc/change.o fray_amd/csrc/accum.o fray_amd/csrc/samplemap.o fray_amd/csrc/samplemap_budget.o \
+            fray_amd/csrc/capi_features.o fray_amd/csrc/denoise.o fray_amd/csrc/temporal.o fray_amd/csrc/temporal_split.o fray_amd/csrc/change.o fray_amd/csrc/accum.o fray_amd/csrc/samplemap.o fray_amd/csrc/samplemap_budget.o fray_amd/csrc/history_map.o \
             $(filter fray_amd/csrc/variant%,$(ST_OBJ)) $(CONTRACT_OBJ) $(filter-out fray_amd/csrc/variant%,$(ST_OBJ))
 HIP_HDR  := $(wildcard fray_amd/csrc/*.h) $(wildcard fray_amd/csrc/*.hpp) include/frayhip.h
 
@@ -54,8 +54,8 @@ fray_amd/csrc/$(1)%.o: fray_amd/csrc/$(2).hip $$(HIP_HDR)
 endef
 $(foreach set,$(ST_SETS),$(eval $(call ST_RULE,$(firstword $(subst :, ,$(set))),$(lastword $(subst :, ,$(set))))))
 
-# the denoiser, the temporal stage, the change frame and the sample map (scene-free) and the resumable frames' resolves: FP32 without contraction whatever EXTRA_HIPFLAGS say (the last -ffp-contract on the command line wins)
-fray_amd/csrc/denoise.o fray_amd/csrc/temporal.o fray_amd/csrc/temporal_split.o fray_amd/csrc/change.o fray_amd/csrc/accum.o fray_amd/csrc/samplemap.o fray_amd/csrc/samplemap_budget.o: fray_amd/csrc/%.o: fray_amd/csrc/%.hip $(HIP_HDR)
+# the denoiser, the temporal stage, the change frame, the sample map and the history map (scene-free) and the resumable frames' resolves: FP32 without contraction whatever EXTRA_HIPFLAGS say (the last -ffp-contract on the command line wins)
+fray_amd/csrc/denoise.o fray_amd/csrc/temporal.o fray_amd/csrc/temporal_split.o fray_amd/csrc/change.o fray_amd/csrc/accum.o fray_amd/csrc/samplemap.o fray_amd/csrc/samplemap_budget.o fray_amd/csrc/history_map.o: fray_amd/csrc/%.o: fray_amd/csrc/%.hip $(HIP_HDR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -ffp-contract=off -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> fray_amd/csrc/$*.resources.txt || (cat fray_amd/csrc/$*.resources.txt; false)
 
 # (the last -ffp-contract on the command line wins)
@@ -85,7 +85,7 @@ tests/native/librccl_loopback.so: tests/native/rccl_loopback.cpp
 ref:
 	@if [ -d /root/reference/src ]; then $(MAKE) -C oracle -f Makefile.ref; else echo "reference tree absent: oracle/_ref not rebuilt"; fi
 
-resources: $(ST_OBJ) $(CONTRACT_OBJ) fray_amd/csrc/denoise.o fray_amd/csrc/temporal.o fray_amd/csrc/temporal_split.o fray_amd/csrc/change.o fray_amd/csrc/accum.o fray_amd/csrc/samplemap.o fray_amd/csrc/samplemap_budget.o
+resources: $(ST_OBJ) $(CONTRACT_OBJ) fray_amd/csrc/denoise.o fray_amd/csrc/temporal.o fray_amd/csrc/temporal_split.o fray_amd/csrc/change.o fray_amd/csrc/accum.o fray_amd/csrc/samplemap.o fray_amd/csrc/samplemap_budget.o fray_amd/csrc/history_map.o
 	python3 tools/kernel_resources.py $(foreach set,$(ST_SETS),fray_amd/csrc/$(firstword $(subst :, ,$(set)))*.resources.txt) fray_amd/csrc/denoise.resources.txt fray_amd/csrc/temporal.resources.txt fray_amd/csrc/temporal_split.resources.txt fray_amd/csrc/change.resources.txt fray_amd/csrc/accum.resources.txt
 
 clean:

@@ -107,6 +107,12 @@ def build_parser():
     ap.add_argument("--sample-budget", type=int, metavar="N",
                     help="with --refine: the most samples the passes may add over the whole frame (Scene.refine(budget=N)): the tolerance is raised until "
                          "the frame can afford it; the JSON line gains budget, tolerance_reached and stage")
+    ap.add_argument("--boost", type=int, metavar="T",
+                    help="with --denoise --frames N: spend samples where the reprojected history is short (Scene.render_sequence(boost=...)): a pixel "
+                         "whose history holds fewer than T units of --spp samples gets the missing whole units this frame, at most --boost-max of them; "
+                         "--sample-budget N caps the samples of one frame (the target is lowered until the frame fits).  Path-traced mono frames; not "
+                         "with --split or --refine.  The per-frame line gains target_used, samples and boosted")
+    ap.add_argument("--boost-max", type=int, metavar="U", help="with --boost: the most units one frame gives a pixel (default 8)")
     ap.add_argument("--components-out", metavar="FILE.npz",
                     help="component frame (Scene.render_components; path-traced mono frames): render the frame's samples with direct and indirect light "
                          "kept apart and save direct, indirect, noise_direct, noise_indirect, samples and seed; the picture is their sum")
@@ -161,8 +167,21 @@ def check_args(ap, a):
             ap.error("--sample-budget must be >= 0")
     elif a.max_spp is not None:
         ap.error("--max-spp needs --refine")
-    elif a.sample_budget is not None:
+    elif a.sample_budget is not None and a.boost is None:
         ap.error("--sample-budget needs --refine")
+    if a.boost is not None:
+        if a.refine is not None or a.split:
+            ap.error("--boost cannot be combined with --refine or --split")
+        if not (a.denoise and a.frames is not None):
+            ap.error("--boost needs --denoise --frames N")
+        if a.boost < 1:
+            ap.error("--boost: T must be >= 1")
+        if a.boost_max is not None and a.boost_max < 1:
+            ap.error("--boost-max must be >= 1")
+        if a.sample_budget is not None and a.sample_budget < 0:
+            ap.error("--sample-budget must be >= 0")
+    elif a.boost_max is not None:
+        ap.error("--boost-max needs --boost")
     if a.frames is not None and not a.denoise and not a.move:
         ap.error("--frames needs --denoise: a sequence is rendered with temporal accumulation and the filter")
     if a.move and a.frames is None:
@@ -314,8 +333,11 @@ def main(argv=None):
     if a.frames is not None:
         start = abi.Camera.from_buffer_copy(s.camera)
         edit = (lambda _k, scene: move_nodes(scene, a.move)) if a.motion_vectors else None
+        boost = None
+        if a.boost is not None:
+            boost = dict(target=a.boost, max_units=8 if a.boost_max is None else a.boost_max, budget=a.sample_budget)
         for k, (img, _raw, info) in enumerate(s.render_sequence(orbit(start, a.frames, a.yaw_step), seed=a.seed, feature_samples=a.feature_samples,
-                                                                edit=edit, split=a.split, change_samples=a.change_samples)):
+                                                                edit=edit, split=a.split, change_samples=a.change_samples, boost=boost)):
             path = sequence_path(a.output, k)
             img = img.cpu().numpy()
             if lib.frayhip_save_bmp(path.encode(), img.ctypes.data, img.shape[1], img.shape[0]):
@@ -325,6 +347,9 @@ def main(argv=None):
             print("frame %d: yaw %+.2f, frame %.1f ms, features %.1f ms, accumulation %.2f ms, filter %.2f ms (kernels); wrote %s"
                   % (k, k * a.yaw_step, info["render"]["ms_kernels"], info["features"]["ms_kernels"], info["temporal"]["ms_kernels"],
                      filter_ms, path), flush=True)
+            if boost is not None:
+                b = info["boost"]
+                print("frame %d: boost target_used %d, samples %d, boosted %d" % (k, b["target_used"], b["samples"], b["boosted"]), flush=True)
             if a.move and not a.motion_vectors and k + 1 < a.frames:
                 move_nodes(s, a.move)           # the generator renders the next frame when it is asked for it: after this edit
         print("Rendered %d frames in %.2fs" % (a.frames, time.time() - t0))

@@ -224,6 +224,13 @@ class Change(C.Structure):
     _fields_ = [("radius", i32), ("gain", C.c_float)]
 
 
+# struct frayhip_history_map (a struct tag without a typedef, as frayhip_denoise: the name is also the entry point's)
+class HistoryMap(C.Structure):
+    _fields_ = [("base", i32), ("target", i32), ("max_units", i32), ("reserved", i32), ("budget", u64), ("samples", u64), ("boosted", u64),
+                ("target_used", i32), ("pad", i32)]
+
+
+NO_BUDGET = (1 << 64) - 1   # frayhip_history_map.budget: none (UINT64_MAX)
 HISTORY_CHANNELS = 12   # FRAYHIP_HISTORY_CHANNELS: {acc.rgb, N}, {P.xyz, m1}, {n.xyz, m2}
 HISTORY_SPLIT_CHANNELS = 20   # FRAYHIP_HISTORY_SPLIT_CHANNELS: {accD.rgb, N_D}, {P.xyz, m1_D}, {n.xyz, m2_D}, {accI.rgb, N_I}, {m1_I, m2_I, 0, 0}
 
@@ -309,6 +316,12 @@ SYMBOLS = {
                                                              VP, P(Stats)]),
     "frayhip_temporal_accumulate_split_adaptive_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, VP, VP, VP, P(View), VP, P(Temporal), P(Temporal), VP, VP,
                                                                     VP, VP, VP, VP, P(Stats)]),
+    "frayhip_temporal_accumulate_weighted": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, VP, VP, P(View), VP, VP, P(Temporal), VP, VP, VP, VP, P(Stats)]),
+    "frayhip_temporal_accumulate_weighted_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, VP, VP, P(View), VP, VP, P(Temporal), VP, VP, VP, VP, VP,
+                                                              P(Stats)]),
+    "frayhip_history_map_defaults": (C.c_int, [P(HistoryMap)]),
+    "frayhip_history_map": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(View), VP, VP, P(Temporal), P(HistoryMap), VP, VP, VP, P(Stats)]),
+    "frayhip_history_map_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(View), VP, VP, P(Temporal), P(HistoryMap), VP, VP, VP, VP, P(Stats)]),
     "frayhip_camera_rays": (C.c_int, [VP, i64, VP, C.c_int, VP, VP]),
     "frayhip_camera_rays_device": (C.c_int, [VP, i64, VP, C.c_int, VP, VP, VP]),
     "frayhip_trace_rays": (C.c_int, [VP, i64, VP, VP, C.c_int, VP, VP, VP, P(Stats)]),

@@ -122,6 +122,7 @@ int frayhip_sizeof(const char* n)
     if (!strcmp(n, "frayhip_change")) return (int)sizeof(struct frayhip_change);
     if (!strcmp(n, "frayhip_sample_map")) return (int)sizeof(struct frayhip_sample_map);
     if (!strcmp(n, "frayhip_sample_budget")) return (int)sizeof(struct frayhip_sample_budget);
+    if (!strcmp(n, "frayhip_history_map")) return (int)sizeof(struct frayhip_history_map);
 #undef FRAYHIP_SZ
     return -1;
 }

@@ -10,8 +10,14 @@
 //                    the surface the taps are tested against are the motion frame's P' and n' (two float4 rows) instead of the feature frame's
 //                    position and normal; <false> is the kernel as it was.  <MOTION, ADAPTIVE>: a change frame (change.hip) shortens the history per
 //                    pixel -- none where change >= 1, a blend factor raised towards 1 where it is > 0, the arithmetic as it was where it is 0;
-//                    <MOTION, false> are the two kernels as they were
-//   k_tp_variance    per pixel with N < variance_history: the 7x7 window of the finished history (rows 1 and 2: position, normal, m1, m2),
+//                    <MOTION, false> are the two kernels as they were.  <MOTION, ADAPTIVE, WEIGHTED> (frayhip_temporal_accumulate_weighted): the
+//                    frame weighs w units and the history the hu units fetched from a units plane beside it, so the blend factor is w / U with
+//                    U = min(hu + w, max_history) where the unweighted kernels have 1 / N; N, which k_tp_variance reads, still counts frames.
+//                    With w = 1 and a units plane equal to the history's N channel bit for bit, hu is hn (the same products summed in the same
+//                    order), so U is N and w / U is 1.0f / N on the same operands: every output bit is the <MOTION, ADAPTIVE, false> kernel's
+//                    and units_out is hist_out's N.  <.., .., false> compiles the arithmetic as it was: every WEIGHTED branch is if constexpr
+//                    Steps 1 and 2 (tp_surface, tp_fetch) are temporal_common.hpp's, shared with k_hm_held (history_map.hip)
+//   k_tp_variance   per pixel with N < variance_history: the 7x7 window of the finished history (rows 1 and 2: position, normal, m1, m2),
 //                    taken from an LDS tile that the 16x16 block stages first; a block without such a pixel stages nothing
 // k_tp_accumulate's taps are read through L1 / L2, as the filter's.  k_tp_variance with the same direct reads took 0.214 ms at 1080p where
 // every pixel takes the window, against 0.074 ms from the tile ("Temporal accumulation").
@@ -38,80 +44,35 @@ struct TemporalCall {
     int demodulate, varianceHistory;
     float maxHistory, alphaMin, filmOffset, planeTolerance, normalMinDot;
     const float* change;        // k_tp_accumulate<MOTION, true> only: one float a pixel
+    const float* weight;        // k_tp_accumulate<MOTION, ADAPTIVE, true> only: the frame's sample weight, one float a pixel
+    const float* unitsIn;       // and the units plane beside histIn (null with it)
+    float* unitsOut;            // and the one beside histOut
 };
 
-template <bool MOTION, bool ADAPTIVE>
+template <bool MOTION, bool ADAPTIVE, bool WEIGHTED = false>
 static __global__ __launch_bounds__(256) void k_tp_accumulate(TemporalCall T)
 {
     const int W = T.W, H = T.H;
     const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= (size_t)W * H) return;
     const float* f = T.feat + p * FRAYHIP_FEAT_CHANNELS;
-    const float Px = f[0], Py = f[1], Pz = f[2];
-    float nx = f[3], ny = f[4], nz = f[5];
-    const float nn = nx * nx + ny * ny + nz * nz;
-    if (nn > 0.0f) {                       // k_dn_prepare's unit normal
-        const float s = sqrtf(nn);
-        nx = nx / s; ny = ny / s; nz = nz / s;
-    }
+    const TpSurface S = tp_surface<MOTION>(f, T.motion, p);
     const float* c = T.rgb + 3 * p;
     float cr = c[0], cg = c[1], cb = c[2];
     if (T.demodulate) { cr = cr / fmaxf(f[6], 1e-3f); cg = cg / fmaxf(f[7], 1e-3f); cb = cb / fmaxf(f[8], 1e-3f); }
     const float l = tp_lum(cr, cg, cb);
     const float l2 = l * l;
 
-    float sb = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hn = 0.0f, h1 = 0.0f, h2 = 0.0f;
-    bool miss = nx == 0.0f && ny == 0.0f && nz == 0.0f;
-    // what is carried into the previous view: the pixel's own position and unit normal, or where they were (P', n' scaled as the normal is)
-    float Qx = Px, Qy = Py, Qz = Pz, mx = nx, my = ny, mz = nz;
-    if constexpr (MOTION) {
-        const float4 r0 = T.motion[2 * p], r1 = T.motion[2 * p + 1];
-        Qx = r0.x; Qy = r0.y; Qz = r0.z;
-        mx = r1.x; my = r1.y; mz = r1.z;
-        const float mm = mx * mx + my * my + mz * mz;
-        if (mm > 0.0f) {
-            const float s = sqrtf(mm);
-            mx = mx / s; my = my / s; mz = mz / s;
-        }
-        miss = miss || (mx == 0.0f && my == 0.0f && mz == 0.0f);
+    const TpFetch h = tp_fetch<WEIGHTED>(S, W, H, T.histIn, T.unitsIn, T.view, T.filmOffset, T.planeTolerance, T.normalMinDot);
+    const float sb = h.sb;
+    float hr = h.hr, hg = h.hg, hb = h.hb, hn = h.hn, h1 = h.h1, h2 = h.h2, hu = h.hu;
+    float w = 1.0f;                        // the frame's sample weight in this pixel: NaN, 0 and negatives count as 1
+    if constexpr (WEIGHTED) {
+        w = T.weight[p];
+        if (!(w >= 1.0f)) w = 1.0f;
+        w = fminf(w, T.maxHistory);
     }
-    if (T.histIn && !miss) {
-        const frayhip_view& V = T.view;
-        const float dx = Qx - V.pos[0], dy = Qy - V.pos[1], dz = Qz - V.pos[2];
-        const float zc = tp_dot(dx, dy, dz, V.front[0], V.front[1], V.front[2]);
-        if (zc > 0.0f) {
-            const float xc = tp_dot(dx, dy, dz, V.right[0], V.right[1], V.right[2]);
-            const float yc = tp_dot(dx, dy, dz, V.up[0], V.up[1], V.up[2]);
-            const float fx = ((xc / zc / V.tan_x + 1.0f) * 0.5f) * (float)W;
-            const float fy = ((1.0f - yc / zc / V.tan_y) * 0.5f) * (float)H;
-            const float u = fx - T.filmOffset, v = fy - T.filmOffset;
-            const float x0f = floorf(u), y0f = floorf(v);
-            // a footprint that touches the image (the comparisons are false for a NaN): only then do the floats fit an int
-            if (x0f >= -1.0f && x0f <= (float)(W - 1) && y0f >= -1.0f && y0f <= (float)(H - 1)) {
-                const int x0 = (int)x0f, y0 = (int)y0f;
-                const float tx = u - x0f, ty = v - y0f;
-                const float tol = T.planeTolerance * sqrtf(tp_dot(dx, dy, dz, dx, dy, dz));
-                for (int j = 0; j < 2; j++) {
-                    const int yq = y0 + j;
-                    if (yq < 0 || yq >= H) continue;
-                    for (int i = 0; i < 2; i++) {
-                        const int xq = x0 + i;
-                        if (xq < 0 || xq >= W) continue;
-                        const float4* hq = T.histIn + ((size_t)yq * W + xq) * 3;
-                        const float4 q0 = hq[0], q1 = hq[1], q2 = hq[2];
-                        if (q2.x == 0.0f && q2.y == 0.0f && q2.z == 0.0f) continue;
-                        if (!(tp_dot(mx, my, mz, q2.x, q2.y, q2.z) >= T.normalMinDot)) continue;
-                        if (!(fabsf(tp_dot(q1.x - Qx, q1.y - Qy, q1.z - Qz, mx, my, mz)) <= tol)) continue;
-                        const float b = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty);
-                        sb += b;
-                        hr += b * q0.x; hg += b * q0.y; hb += b * q0.z; hn += b * q0.w;
-                        h1 += b * q1.w; h2 += b * q2.w;
-                    }
-                }
-            }
-        }
-    }
-    float ar = cr, ag = cg, ab = cb, m1 = l, m2 = l2, N = 1.0f;
+    float ar = cr, ag = cg, ab = cb, m1 = l, m2 = l2, N = 1.0f, U = w;
     float g = 0.0f;                        // the pixel's change, read only where a history was fetched
     if constexpr (ADAPTIVE) {
         if (sb > 0.0f) g = T.change[p];
@@ -121,26 +82,42 @@ static __global__ __launch_bounds__(256) void k_tp_accumulate(TemporalCall T)
     } else if (ADAPTIVE && g > 0.0f) {
         hr = hr / sb; hg = hg / sb; hb = hb / sb; hn = hn / sb; h1 = h1 / sb; h2 = h2 / sb;
         const float N0 = fminf(hn + 1.0f, T.maxHistory);
-        const float a0 = fmaxf(T.alphaMin, 1.0f / N0);
+        float a0, U0 = 0.0f;
+        if constexpr (WEIGHTED) {
+            hu = hu / sb;
+            U0 = fminf(hu + w, T.maxHistory);
+            a0 = fmaxf(T.alphaMin, w / U0);
+        } else {
+            a0 = fmaxf(T.alphaMin, 1.0f / N0);
+        }
         const float alpha = a0 + g * (1.0f - a0);
         N = fminf(N0, 1.0f / alpha);
+        if constexpr (WEIGHTED) U = fminf(U0, w / alpha);
         ar = hr + alpha * (cr - hr); ag = hg + alpha * (cg - hg); ab = hb + alpha * (cb - hb);
         m1 = h1 + alpha * (l - h1);
         m2 = h2 + alpha * (l2 - h2);
     } else if (sb > 0.0f) {
         hr = hr / sb; hg = hg / sb; hb = hb / sb; hn = hn / sb; h1 = h1 / sb; h2 = h2 / sb;
         N = fminf(hn + 1.0f, T.maxHistory);
-        const float alpha = fmaxf(T.alphaMin, 1.0f / N);
+        float alpha;
+        if constexpr (WEIGHTED) {
+            hu = hu / sb;
+            U = fminf(hu + w, T.maxHistory);
+            alpha = fmaxf(T.alphaMin, w / U);
+        } else {
+            alpha = fmaxf(T.alphaMin, 1.0f / N);
+        }
         ar = hr + alpha * (cr - hr); ag = hg + alpha * (cg - hg); ab = hb + alpha * (cb - hb);
         m1 = h1 + alpha * (l - h1);
         m2 = h2 + alpha * (l2 - h2);
     }
     float4* ho = T.histOut + p * 3;
     ho[0] = make_float4(ar, ag, ab, N);
-    ho[1] = make_float4(Px, Py, Pz, m1);
-    ho[2] = make_float4(nx, ny, nz, m2);
+    ho[1] = make_float4(S.Px, S.Py, S.Pz, m1);
+    ho[2] = make_float4(S.nx, S.ny, S.nz, m2);
     float* s = T.signal + 3 * p;
     s[0] = ar; s[1] = ag; s[2] = ab;
+    if constexpr (WEIGHTED) T.unitsOut[p] = U;
     if (N >= (float)T.varianceHistory) T.variance[p] = fmaxf(0.0f, m2 - m1 * m1);
 }
 
@@ -249,7 +226,7 @@ int check(const char* who, int W, int H, const float* rgb, const float* feat, co
 // motion: the motion frame of the _motion and _adaptive entries, or null; change: the change frame of the _adaptive entries, or null
 int run(int W, int H, const float* rgb, const float* feat, const frayhip_view* view, const float* histIn, const struct frayhip_temporal* prm, float* histOut,
         float* signal, float* variance, hipStream_t stream, frayhip_stats* st, std::chrono::steady_clock::time_point t0, const float* motion = nullptr,
-        const float* change = nullptr)
+        const float* change = nullptr, const float* weight = nullptr, const float* unitsIn = nullptr, float* unitsOut = nullptr)
 {
     const size_t n = (size_t)W * H;
     TemporalCall T{};
@@ -257,6 +234,7 @@ int run(int W, int H, const float* rgb, const float* feat, const frayhip_view* v
     T.rgb = rgb; T.feat = feat; T.motion = (const float4*)motion;
     T.histIn = (const float4*)histIn; T.histOut = (float4*)histOut;
     T.signal = signal; T.variance = variance; T.change = change;
+    T.weight = weight; T.unitsIn = unitsIn; T.unitsOut = unitsOut;
     if (view) T.view = *view;
     T.demodulate = prm->demodulate; T.varianceHistory = prm->variance_history;
     T.maxHistory = (float)prm->max_history; T.alphaMin = prm->alpha_min; T.filmOffset = prm->film_offset;
@@ -267,7 +245,11 @@ int run(int W, int H, const float* rgb, const float* feat, const frayhip_view* v
     struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{stream};
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     HIP_TRY(hipEventRecord(E.a, stream));
-    if (change && motion) hipLaunchKernelGGL((k_tp_accumulate<true, true>), grid, block, 0, stream, T);
+    if (weight && change && motion) hipLaunchKernelGGL((k_tp_accumulate<true, true, true>), grid, block, 0, stream, T);
+    else if (weight && change) hipLaunchKernelGGL((k_tp_accumulate<false, true, true>), grid, block, 0, stream, T);
+    else if (weight && motion) hipLaunchKernelGGL((k_tp_accumulate<true, false, true>), grid, block, 0, stream, T);
+    else if (weight) hipLaunchKernelGGL((k_tp_accumulate<false, false, true>), grid, block, 0, stream, T);
+    else if (change && motion) hipLaunchKernelGGL((k_tp_accumulate<true, true>), grid, block, 0, stream, T);
     else if (change) hipLaunchKernelGGL((k_tp_accumulate<false, true>), grid, block, 0, stream, T);
     else if (motion) hipLaunchKernelGGL((k_tp_accumulate<true, false>), grid, block, 0, stream, T);
     else hipLaunchKernelGGL((k_tp_accumulate<false, false>), grid, block, 0, stream, T);
@@ -287,6 +269,36 @@ int run(int W, int H, const float* rgb, const float* feat, const frayhip_view* v
         o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         *st = o;
     }
+    return FRAYHIP_OK;
+}
+
+// The weighted entries' checks: the adaptive entry's list with motion and change both optional, then the weight plane and the two units planes
+int check_weighted(const char* who, int W, int H, const float* rgb, const float* feat, const float* motion, const float* change, const float* weight,
+                   const frayhip_view* view, const float* histIn, const float* unitsIn, const struct frayhip_temporal* p, const float* histOut,
+                   const float* unitsOut, const float* signal, const float* variance, bool device)
+{
+    if (const int rc = check(who, W, H, rgb, feat, view, histIn, p, histOut, signal, variance, device, MAY_MOTION, motion, false, change)) return rc;
+    if (!weight) return bad(who, "null weight");
+    if (!unitsOut) return bad(who, "null units_out");
+    if (!histIn != !unitsIn) return bad(who, "hist_in and units_in must both be given or both be null");
+    if (device) {
+        for (const void* q : {(const void*)weight, (const void*)unitsIn, (const void*)unitsOut})
+            if (misaligned(q, 4)) return bad(who, "device pointer to floats not 4-byte aligned");
+    }
+    const size_t n = (size_t)W * H;
+    const struct { const void* q; size_t bytes; const char* name; } ins[7] = {{rgb, 12 * n, "rgb"}, {feat, 4 * FRAYHIP_FEAT_CHANNELS * n, "feat"},
+                                                                              {histIn, 4 * FRAYHIP_HISTORY_CHANNELS * n, "hist_in"},
+                                                                              {motion, 4 * FRAYHIP_MOTION_CHANNELS * n, "motion"}, {change, 4 * n, "change"},
+                                                                              {weight, 4 * n, "weight"}, {unitsIn, 4 * n, "units_in"}};
+    const struct { const void* q; size_t bytes; const char* name; } outs[3] = {{histOut, 4 * FRAYHIP_HISTORY_CHANNELS * n, "hist_out"}, {signal, 12 * n, "signal"},
+                                                                                 {variance, 4 * n, "variance"}};
+    for (const auto& o : outs) {
+        for (int k = 5; k < 7; k++)
+            if (overlaps(o.q, o.bytes, ins[k].q, ins[k].bytes)) return bad(who, std::string(o.name) + " must not overlap " + ins[k].name);
+        if (overlaps(unitsOut, 4 * n, o.q, o.bytes)) return bad(who, std::string("units_out must not overlap ") + o.name);
+    }
+    for (const auto& in : ins)
+        if (overlaps(unitsOut, 4 * n, in.q, in.bytes)) return bad(who, "units_out must not overlap an input");
     return FRAYHIP_OK;
 }
 
@@ -457,6 +469,67 @@ int frayhip_temporal_accumulate_adaptive(int width, int height, const float* rgb
     if (d_hin) HIP_TRY(hipMemcpy(d_hin, hist_in, n * 4 * HC, hipMemcpyHostToDevice));
     if (const int rc = run(width, height, d_rgb, d_feat, prev_view, d_hin, p, d_hout, d_signal, d_var, nullptr, st, t0, d_motion, d_change)) return rc;
     HIP_TRY(hipMemcpy(hist_out, d_hout, n * 4 * HC, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(signal, d_signal, n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(variance, d_var, n * 4, hipMemcpyDeviceToHost));
+    if (st) st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return FRAYHIP_OK;
+}
+
+int frayhip_temporal_accumulate_weighted_device(int width, int height, const float* d_rgb, const float* d_feat, const float* d_motion, const float* d_change,
+                                                const float* d_weight, const frayhip_view* prev_view, const float* d_hist_in, const float* d_units_in,
+                                                const struct frayhip_temporal* p, float* d_hist_out, float* d_units_out, float* d_signal, float* d_variance,
+                                                void* hip_stream, frayhip_stats* st)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (const int rc = check_weighted("frayhip_temporal_accumulate_weighted_device", width, height, d_rgb, d_feat, d_motion, d_change, d_weight, prev_view, d_hist_in,
+                                      d_units_in, p, d_hist_out, d_units_out, d_signal, d_variance, true))
+        return rc;
+    return run(width, height, d_rgb, d_feat, prev_view, d_hist_in, p, d_hist_out, d_signal, d_variance, (hipStream_t)hip_stream, st, t0, d_motion, d_change, d_weight,
+               d_units_in, d_units_out);
+}
+
+int frayhip_temporal_accumulate_weighted(int width, int height, const float* rgb, const float* feat, const float* motion, const float* change, const float* weight,
+                                         const frayhip_view* prev_view, const float* hist_in, const float* units_in, const struct frayhip_temporal* p,
+                                         float* hist_out, float* units_out, float* signal, float* variance, frayhip_stats* st)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const char* who = "frayhip_temporal_accumulate_weighted";
+    if (const int rc = check_weighted(who, width, height, rgb, feat, motion, change, weight, prev_view, hist_in, units_in, p, hist_out, units_out, signal, variance, false))
+        return rc;
+    const size_t n = (size_t)width * height;
+    const size_t HC = FRAYHIP_HISTORY_CHANNELS, MC = FRAYHIP_MOTION_CHANNELS;
+    // one allocation, the 16-byte rows first: hist_out, hist_in and motion when given, then rgb, feat, weight, units_out, signal, variance, and
+    // change and units_in when given
+    DeviceArrays B(std::string(who) + ": out of device memory");
+    float* d_hout;
+    if (const int rc = B.alloc(d_hout, n * (HC + (hist_in ? HC + 1 : 0) + (motion ? MC : 0) + 3 + FRAYHIP_FEAT_CHANNELS + 1 + 1 + 3 + 1 + (change ? 1 : 0)))) return rc;
+    float* q = d_hout + HC * n;
+    float* d_hin = nullptr;
+    float* d_motion = nullptr;
+    float* d_change = nullptr;
+    float* d_uin = nullptr;
+    if (hist_in) { d_hin = q; q += HC * n; }
+    if (motion) { d_motion = q; q += MC * n; }
+    float* d_rgb = q;
+    float* d_feat = d_rgb + 3 * n;
+    float* d_weight = d_feat + FRAYHIP_FEAT_CHANNELS * n;
+    float* d_uout = d_weight + n;
+    float* d_signal = d_uout + n;
+    float* d_var = d_signal + 3 * n;
+    q = d_var + n;
+    if (change) { d_change = q; q += n; }
+    if (hist_in) { d_uin = q; q += n; }
+    HIP_TRY(hipMemcpy(d_rgb, rgb, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_feat, feat, n * 4 * FRAYHIP_FEAT_CHANNELS, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_weight, weight, n * 4, hipMemcpyHostToDevice));
+    if (d_change) HIP_TRY(hipMemcpy(d_change, change, n * 4, hipMemcpyHostToDevice));
+    if (d_motion) HIP_TRY(hipMemcpy(d_motion, motion, n * 4 * MC, hipMemcpyHostToDevice));
+    if (d_hin) HIP_TRY(hipMemcpy(d_hin, hist_in, n * 4 * HC, hipMemcpyHostToDevice));
+    if (d_uin) HIP_TRY(hipMemcpy(d_uin, units_in, n * 4, hipMemcpyHostToDevice));
+    if (const int rc = run(width, height, d_rgb, d_feat, prev_view, d_hin, p, d_hout, d_signal, d_var, nullptr, st, t0, d_motion, d_change, d_weight, d_uin, d_uout))
+        return rc;
+    HIP_TRY(hipMemcpy(hist_out, d_hout, n * 4 * HC, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(units_out, d_uout, n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(signal, d_signal, n * 12, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(variance, d_var, n * 4, hipMemcpyDeviceToHost));
     if (st) st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -448,7 +448,8 @@ def _sample_map_pair(who, state, stats, stream, params, budget=None):
     return add, info
 
 
-def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, stream=None, motion=None, change=None, **params):
+def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, stream=None, motion=None, change=None, weight=None, units_in=None,
+                        **params):
     """The temporal stage of include/frayhip.h (frayhip_temporal_accumulate): rgb [H, W, 3] and feat [H, W, 10] of the current frame, prev_view
     (view_from_camera of the previous frame's camera) and hist_in [H, W, 12] (the previous call's history), both None for the first frame;
     float32.  numpy arrays go through the host entry; torch tensors on the GPU through the device entry, on `stream` (None: the current
@@ -459,23 +460,51 @@ def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, st
     above.
     change: a change frame [H, W] of the inputs' kind (change_frame): the history is shortened per pixel -- dropped where change >= 1, blended
     with a larger factor where it is > 0, taken as it is where it is 0 (frayhip_temporal_accumulate_adaptive, with or without motion).  None:
-    exactly the calls above."""
+    exactly the calls above.
+    weight: a weight plane [H, W] of the inputs' kind -- the units of the sequence's base sample count this frame gave each pixel (history_map) --
+    with units_in [H, W], the previous call's units plane, given exactly when hist_in is (frayhip_temporal_accumulate_weighted, with or without
+    motion and change): the blend factor comes from sample weight, w / U, while N keeps counting frames.  The call then returns (hist_out, units_out
+    [H, W], signal, variance[, stats]).  None: exactly the calls and returns above."""
     p = temporal_params(**params)
     if (prev_view is None) != (hist_in is None):
         raise ValueError("temporal_accumulate: prev_view and hist_in must both be given or both be None")
     if prev_view is not None and not isinstance(prev_view, abi.View):
         raise TypeError("temporal_accumulate: prev_view must be an abi.View (view_from_camera), got %s" % type(prev_view).__name__)
+    if weight is None and units_in is not None:
+        raise ValueError("temporal_accumulate: units_in needs weight=")
+    if weight is not None and (units_in is None) != (hist_in is None):
+        raise ValueError("temporal_accumulate: with weight=, units_in and hist_in must both be given or both be None")
     named = [("rgb", rgb, 3), ("feat", feat, abi.FEAT_CHANNELS)] + ([("hist_in", hist_in, abi.HISTORY_CHANNELS)] if hist_in is not None else [])
     if motion is not None:
         named.append(("motion", motion, abi.MOTION_CHANNELS))
     if change is not None:
         named.append(("change", change, 0))
+    if weight is not None:
+        named.append(("weight", weight, 0))
+        if units_in is not None:
+            named.append(("units_in", units_in, 0))
     ins, (H, W), tensors = _frame_inputs("temporal_accumulate", named)
     hin = ins[2] if hist_in is not None else None
+    uin = ins.pop() if units_in is not None else None
+    wgt = ins.pop() if weight is not None else None
     chg = ins.pop() if change is not None else None
     mot = ins[-1] if motion is not None else None
     view = C.byref(prev_view) if prev_view is not None else None
     st = abi.Stats()
+    if wgt is not None:
+        if not tensors:
+            hist, units, signal, var = (np.empty((H, W, abi.HISTORY_CHANNELS), np.float32), np.empty((H, W), np.float32), np.empty((H, W, 3), np.float32),
+                                        np.empty((H, W), np.float32))
+            _check(lib.frayhip_temporal_accumulate_weighted(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(mot), _ptr(chg), _ptr(wgt), view, _ptr(hin), _ptr(uin),
+                                                            C.byref(p), _ptr(hist), _ptr(units), _ptr(signal), _ptr(var), C.byref(st)))
+        else:
+            with _DeviceCall(ins[0].device, stream) as call:
+                new = lambda *shape: call.torch.empty(shape, dtype=call.torch.float32, device=ins[0].device)
+                hist, units, signal, var = new(H, W, abi.HISTORY_CHANNELS), new(H, W), new(H, W, 3), new(H, W)
+                _check(lib.frayhip_temporal_accumulate_weighted_device(W, H, _ptr(ins[0]), _ptr(ins[1]), _ptr(mot), _ptr(chg), _ptr(wgt), view, _ptr(hin),
+                                                                       _ptr(uin), C.byref(p), _ptr(hist), _ptr(units), _ptr(signal), _ptr(var), call.handle,
+                                                                       C.byref(st)))
+        return (hist, units, signal, var, st.as_dict()) if stats else (hist, units, signal, var)
     if not tensors:
         hist, signal, var = (np.empty((H, W, abi.HISTORY_CHANNELS), np.float32), np.empty((H, W, 3), np.float32), np.empty((H, W), np.float32))
         if chg is not None:
@@ -501,6 +530,66 @@ def temporal_accumulate(rgb, feat, prev_view=None, hist_in=None, stats=False, st
                 _check(lib.frayhip_temporal_accumulate_device(W, H, _ptr(ins[0]), _ptr(ins[1]), view, _ptr(hin), C.byref(p), hist.data_ptr(),
                                                               signal.data_ptr(), var.data_ptr(), call.handle, C.byref(st)))
     return (hist, signal, var, st.as_dict()) if stats else (hist, signal, var)
+
+
+def history_map(feat, prev_view=None, hist_in=None, units_in=None, motion=None, change=None, base=None, target=8, max_units=8, budget=None,
+                held=False, stats=False, stream=None, **temporal_params_):
+    """The history map of include/frayhip.h (frayhip_history_map): from the history that temporal_accumulate(weight=) will fetch for this view,
+    how many samples each pixel gets this frame.  feat [H, W, 10]; prev_view, hist_in [H, W, 12] and units_in [H, W] all None (first frame) or
+    all given; motion [H, W, 8] and change [H, W] or None, as temporal_accumulate takes them; float32, numpy arrays (host entry) or GPU torch
+    tensors (device entry, on `stream`).  base: the samples a pixel with a full history gets (required); target: the units a pixel's history
+    should amount to after this frame; max_units: the most units one frame gives a pixel; budget: None, or the most samples the plane may hold
+    (an int >= base * W * H; the target is lowered until the plane fits).  **temporal_params_: the temporal_params fields of the accumulation
+    that follows -- the map fetches with its tap tests and counts against its max_history.
+    Returns (add, weight, info): add int32 [H, W] -- what Scene.render_samples_map takes -- weight float32 [H, W] -- what
+    temporal_accumulate(weight=) takes -- and info {"target_used", "samples", "boosted", "budget"}, with "held" (the units each pixel's
+    reprojected history holds, float32 [H, W]) when held=True and "stats" (ms_total, ms_kernels) when stats=True."""
+    who = "history_map"
+    p = temporal_params(**temporal_params_)
+    if base is None:
+        raise ValueError("%s: base must be given (it has no default)" % who)
+    budget = _budget_of(who, budget)
+    given = [x is not None for x in (prev_view, hist_in, units_in)]
+    if any(given) and not all(given):
+        raise ValueError("%s: prev_view, hist_in and units_in must all be given or all be None" % who)
+    if prev_view is not None and not isinstance(prev_view, abi.View):
+        raise TypeError("%s: prev_view must be an abi.View (view_from_camera), got %s" % (who, type(prev_view).__name__))
+    named = [("feat", feat, abi.FEAT_CHANNELS)]
+    if hist_in is not None:
+        named += [("hist_in", hist_in, abi.HISTORY_CHANNELS), ("units_in", units_in, 0)]
+    if motion is not None:
+        named.append(("motion", motion, abi.MOTION_CHANNELS))
+    if change is not None:
+        named.append(("change", change, 0))
+    ins, (H, W), tensors = _frame_inputs(who, named)
+    chg = ins.pop() if change is not None else None
+    mot = ins.pop() if motion is not None else None
+    hin, uin = (ins[1], ins[2]) if hist_in is not None else (None, None)
+    view = C.byref(prev_view) if prev_view is not None else None
+    m = abi.HistoryMap()
+    _check(lib.frayhip_history_map_defaults(C.byref(m)))
+    m.base, m.target, m.max_units = int(base), int(target), int(max_units)
+    if budget is not None:
+        m.budget = budget
+    st = abi.Stats()
+    if not tensors:
+        add, weight = np.zeros((H, W), np.int32), np.zeros((H, W), np.float32)
+        hld = np.zeros((H, W), np.float32) if held else None
+        _check(lib.frayhip_history_map(W, H, _ptr(ins[0]), _ptr(mot), _ptr(chg), view, _ptr(hin), _ptr(uin), C.byref(p), C.byref(m), _ptr(add), _ptr(weight),
+                                       _ptr(hld), C.byref(st)))
+    else:
+        with _DeviceCall(ins[0].device, stream) as call:
+            add = call.torch.zeros((H, W), dtype=call.torch.int32, device=ins[0].device)
+            weight = call.torch.zeros((H, W), dtype=call.torch.float32, device=ins[0].device)
+            hld = call.torch.zeros((H, W), dtype=call.torch.float32, device=ins[0].device) if held else None
+            _check(lib.frayhip_history_map_device(W, H, _ptr(ins[0]), _ptr(mot), _ptr(chg), view, _ptr(hin), _ptr(uin), C.byref(p), C.byref(m), _ptr(add),
+                                                  _ptr(weight), _ptr(hld), call.handle, C.byref(st)))
+    info = {"target_used": int(m.target_used), "samples": int(m.samples), "boosted": int(m.boosted), "budget": budget}
+    if held:
+        info["held"] = hld
+    if stats:
+        info["stats"] = st.as_dict()
+    return add, weight, info
 
 
 _TEMPORAL_SHARED = ("demodulate", "film_offset", "plane_tolerance", "normal_min_dot")     # the fields that decide which taps count
@@ -1518,8 +1607,24 @@ class Scene:
             a.samples_done = req.samples_done
         return (tuple(rgb) if pair else rgb[0]), st.as_dict()
 
+    def _sequence_samples_map(self, fr, add, state, stream):
+        """render_sequence's own call of frayhip_render_samples_map_device: add[y, x] more samples of frame record `fr` on the device state
+        `state`, without the counting kernels that stats=True asks for: (rgb, stats dict)."""
+        import torch
+        W, H = self.frame_size
+        st = abi.Stats()
+        req = abi.SamplesMap()
+        with torch.cuda.stream(stream):
+            count = state.count_plane()
+            rgb = torch.zeros((H, W, 3), dtype=torch.float32, device="cuda")
+        _check(lib.frayhip_render_samples_map_device(self._dev, C.byref(fr), C.byref(req), _ptr(state.state), _ptr(count), _ptr(add), _ptr(rgb), None,
+                                                     C.c_void_p(stream.cuda_stream), C.byref(st)))
+        state.samples_done = req.count_min
+        state.counts = None if req.count_min == req.count_max else count
+        return rgb, st.as_dict()
+
     def render_sequence(self, cameras, seed=42, feature_samples=4, temporal=None, edit=None, split=False, temporal_direct=None, temporal_indirect=None,
-                        change_samples=0, change=None, **denoise_params):
+                        change_samples=0, change=None, boost=None, **denoise_params):
         """A generator over a fly-through of a static scene with temporal accumulation (include/frayhip.h "temporal accumulation"): for the k-th
         abi.Camera of `cameras` it sets the view, renders the feature frame and the frame with seed + k (equal seeds would accumulate the same
         noise every frame), accumulates onto the previous frame's history reprojected into this view, runs the a-trous levels on the accumulated
@@ -1560,11 +1665,35 @@ class Scene:
         per component, from that component's pair of states, and frames k >= 1 make one temporal_accumulate_split(change_direct=,
         change_indirect=) on the 20-channel history, whose outputs are those two temporal_accumulate(change=) calls' bit for bit.  info then also
         holds "change" (or "change_direct" and "change_indirect") and the "probe" stats dict; they are None in frame 0.
-        change: a dict of change_frame's radius and gain (needs change_samples > 0).  radius 3 and gain 1 are a choice, not a measurement."""
+        change: a dict of change_frame's radius and gain (needs change_samples > 0).  radius 3 and gain 1 are a choice, not a measurement.
+        boost: None runs exactly the launches above.  A dict of history_map's target (default 8), max_units (8) and budget (None) spends samples
+        where the reprojected history is short (include/frayhip.h "weighted accumulation and history maps"): mono path-traced frames only (a
+        Whitted or stereo frame and a long generator are refused with FrayError before anything is rendered; with split=True it is a ValueError:
+        not offered yet; unknown keys are a TypeError).  Frame k then runs the feature (and motion) pass as above; with change_samples, after
+        the edit the frame's first n samples go into a fresh device state, which is cloned for change_frame; history_map(feat, view, history,
+        units, motion, change, base=spp, ...) with the sequence's temporal parameters gives add and weight; render_samples_map renders add (add - n
+        on the state that holds n; n <= spp <= add always), so that every pixel of raw is that pixel of render(seed + k) at add[pixel] samples bit for
+        bit; temporal_accumulate(weight=, units_in=) accumulates raw.  info gains "counts" (int32 [H, W]: the samples each pixel of raw holds),
+        "weight", "units" (the units plane that goes with "history") and "boost" (history_map's info).  target=1, max_units=1 gives every output bit
+        of the boost=None sequence.  target 8 and max_units 8 are a choice, not a measurement."""
+        bparams = None
+        if boost is not None:                   # what the arguments alone decide, before the device is asked for
+            if split:
+                raise ValueError("render_sequence: boost with split=True is not offered yet")
+            bparams = dict(boost)
+            if set(bparams) - {"target", "max_units", "budget"}:
+                raise TypeError("render_sequence: boost= takes target, max_units and budget, got %s" % ", ".join(sorted(set(bparams) - {"target", "max_units", "budget"})))
         self._need_dev()
         import torch
         W, H = self.frame_size
         spp = self.samples_per_pixel()
+        if boost is not None:
+            if not self.settings.gi:
+                raise FrayError(abi.E_UNSUPPORTED, "render_sequence: boost needs a path-traced frame (settings.gi): sample maps are not offered for Whitted frames")
+            if self.camera.stereoSeparation > 0:
+                raise FrayError(abi.E_UNSUPPORTED, "render_sequence: boost is not offered for stereo frames")
+            if 8 + 10 * (int(self.settings.maxTraceDepth) + 2) > 227:
+                raise FrayError(abi.E_UNSUPPORTED, "render_sequence: boost is not offered for long generators (maxTraceDepth %d)" % self.settings.maxTraceDepth)
         change_samples = int(change_samples)
         if change_samples < 0:
             raise ValueError("render_sequence: change_samples must be >= 0, got %d" % change_samples)
@@ -1607,7 +1736,7 @@ class Scene:
         saved = abi.Camera.from_buffer_copy(self.desc.camera)
         stream = torch.cuda.current_stream()
         handle = C.c_void_p(stream.cuda_stream)
-        hist, view = None, None
+        hist, view, units = None, None, None
         try:
             for k, cam in enumerate(cameras):
                 if not isinstance(cam, abi.Camera):
@@ -1664,6 +1793,29 @@ class Scene:
                     yield d_out + i_out, d_rgb + i_rgb, info
                     continue
                 chg = None
+                if bparams is not None:
+                    state = fresh()
+                    rdict = None
+                    if probing:
+                        _, rdict = self._sequence_samples(fr, n_probe, state, stream)
+                        chg = change_frame(probe, state.state.clone(), motion, stream=stream, **cparams)
+                    add, weight, binfo = history_map(feat, view, hist, units, motion=motion, change=chg, base=spp, stream=stream,
+                                                     **dict(bparams, **tparams))
+                    raw, rdict2 = self._sequence_samples_map(fr, add - n_probe if probing else add, state, stream)
+                    rdict = _sum_stats(rdict, rdict2) if rdict else rdict2
+                    hist, units, signal, var, tst = temporal_accumulate(raw, feat, view, hist, stats=True, stream=stream, motion=motion, change=chg,
+                                                                        weight=weight, units_in=units, **tparams)
+                    out, dst = denoise_signal(signal, var, feat, stats=True, stream=stream, **denoise_params)
+                    view = view_from_camera(self.desc.camera, W, H)
+                    info = {"features_frame": feat, "history": hist, "signal": signal, "variance": var, "view": view,
+                            "film_offset": tparams["film_offset"], "render": rdict, "features": fst.as_dict(), "temporal": tst,
+                            "denoise": dst, "counts": add, "weight": weight, "units": units, "boost": binfo}
+                    if edit is not None:
+                        info["motion"] = motion
+                    if n_probe > 0:
+                        info.update(change=chg, probe=pst)
+                    yield out, raw, info
+                    continue
                 if probing:
                     state = fresh()
                     raw, rdict = self._sequence_samples(fr, n_probe, state, stream)

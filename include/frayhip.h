@@ -1179,6 +1179,90 @@ int  frayhip_temporal_accumulate_split_adaptive_device(int width, int height, co
                                                        float* d_hist_out, float* d_signal_direct, float* d_signal_indirect,
                                                        float* d_variance_direct, float* d_variance_indirect, void* hip_stream,
                                                        frayhip_stats* st);
+
+/* ---- weighted accumulation and history maps (samples spent where the reprojected history is short, scene-free) --------------------------------
+ * A sequence may give its pixels different numbers of samples per frame (frayhip_render_samples_map renders any count plane).  Two pieces make
+ * the temporal stage follow: an accumulation whose blend factor comes from sample weight instead of a frame count, and a map that says, from
+ * the history reprojected into this view, how many samples each pixel gets this frame.
+ *
+ * Units plane: W*H floats beside the 12-channel history (whose layout is unchanged), ping-ponged by the caller as the history is: the sample
+ * weight a pixel's history holds, in units of the sequence's base sample count.  N (row 0 of the history) keeps counting FRAMES: the variance
+ * rules (variance_history, k_tp_variance) ask how many observations the luminance moments have seen, and a pixel that received eight units in
+ * its first frame has still seen one.  Units count WEIGHT: if a pixel gets 8x the samples in its first frame and 1x in its second, a blend by
+ * 1 / N would weigh the two equally and leave the pixel noisier than the first frame left it.
+ *
+ * frayhip_temporal_accumulate_weighted: frayhip_temporal_accumulate with a weight plane (W*H floats: the units this frame gives each pixel) and
+ * the two units planes.  motion NULL or a motion frame (the arithmetic of the _motion entry), change NULL or a change frame (the arithmetic of
+ * the _adaptive entry), or both.  hist_in, units_in and prev_view are all NULL (first frame) or all given.  Per pixel, with the steps of
+ * "temporal accumulation":
+ *   weight   w = weight_p; if (!(w >= 1.0f)) w = 1.0f; w = fminf(w, max_history).  NaN, 0 and negatives count as 1.
+ *   step 2   the same taps, tests and weights b; the counted taps also sum hu += b * units_in[q], in tap order beside N's sum, and hu = hu / sum(b)
+ *            where the others are divided.
+ *   step 3   no history (sum(b) == 0, a miss, or a change frame with !(g < 1)):  acc = c, m1 = l, m2 = l * l, N = 1, U = w.
+ *            plain (no change frame, or !(g > 0)):  N = fminf(N_hist + 1, max_history); U = fminf(hu + w, max_history);
+ *              alpha = fmaxf(alpha_min, w / U); the blends of step 3 with this alpha.
+ *            0 < g < 1:  N0 = fminf(N_hist + 1, max_history); U0 = fminf(hu + w, max_history); a0 = fmaxf(alpha_min, w / U0);
+ *              alpha = a0 + g * (1.0f - a0); U = fminf(U0, w / alpha); N = fminf(N0, 1.0f / alpha); the blends with this alpha.
+ *   outputs  row 0 .w of hist_out stores N; units_out[p] = U.
+ *   step 4   unchanged, on N: a boosted pixel in its first frame has N = 1 and takes the spatial estimate.
+ * The contract.  With a weight plane of 1.0f everywhere and units_in equal to hist_in's N channel bit for bit (or on the first frame), hist_out,
+ * signal and variance are the matching existing entry's (plain, _motion or _adaptive) bit for bit, and units_out equals hist_out's N channel bit
+ * for bit: hu is then the sum that N_hist is, so U is N, and w / U is 1.0f / N on the same operands.
+ * Kernels: k_tp_accumulate<MOTION, ADAPTIVE, true>, then k_tp_variance as above; the other entries keep their instantiations.  No work buffers.
+ *   Device pointers, the stream contract and *st as frayhip_temporal_accumulate_device (weight and the units planes 4-byte aligned).
+ * FRAYHIP_E_ARG, before the device is touched: the adaptive entry's list (motion and change may each be NULL); a NULL, misaligned or
+ *   output-overlapping weight or units_in; a NULL units_out or one that overlaps any other buffer; units_in without hist_in or the reverse.
+ *
+ * frayhip_history_map: per pixel,
+ *   held   0 on the first frame, where step 2 fetches no history (a miss, zc <= 0, the footprint off the image, no counted tap) and where a
+ *          change frame has !(g < 1); otherwise hu, exactly the hu of the weighted entry's step 2 (one device function serves both kernels);
+ *          with 0 < g < 1 it is hu * (1.0f - g).  Then if (!(held >= 0)) held = 0.
+ *   k      (int)floorf(fminf(held, (float)p->max_history)): the whole units the pixel already holds.
+ *   units  for a target t: units(t) = min(max(t - k, 1), max_units); add = base * units, weight = (float)units.  Whole units, so that add is a
+ *          multiple of base and the weight plane says exactly what was rendered.
+ *   S(t) = base * the sum over all pixels of units(t), an exact 64-bit integer that does not decrease with t; target_used is the largest t in
+ *   [1, target] with S(t) <= budget.  The unspent rest is not handed out: a stated limit, as in the budgeted sample map.  A budget below
+ *   base * W * H makes even S(1) unaffordable: FRAYHIP_E_ARG, found from the arguments alone.
+ * target 8 and max_units 8 are a maintainer's choice, not a measurement.
+ * Kernels: k_hm_held (the fetch; held into a workspace of the call and into the caller's plane when given; k counted into max_history + 1 bins,
+ *   per block in LDS, flushed with integer atomics), k_hm_select (one block: S(t) for every t from the bins' prefix sums; target_used, samples
+ *   and boosted into a control record in device memory), k_hm_map (add and weight at the record's target).  Three launches on one stream and
+ *   one synchronisation per call, whatever the data; every total is an exact integer sum, so the answer depends on neither grid nor timing.
+ *   Device pointers: the history and the motion frame 16-byte aligned, the rest 4-byte; prev_view, p and m stay HOST pointers; the stream
+ *   contract and *st as frayhip_temporal_accumulate_device.
+ * FRAYHIP_E_ARG, before the device is touched: width or height < 1 or W*H > 2^30; a NULL feat, p, m, add or weight; hist_in, units_in and
+ *   prev_view not all given or all NULL; a bad view or temporal parameter as the accumulation refuses it; base < 1; target outside
+ *   1..p->max_history; max_units < 1; base * max_units > 2^24; reserved != 0; budget < base * W * H; an output overlapping an input or another
+ *   output; a misaligned device pointer. */
+int  frayhip_temporal_accumulate_weighted(int width, int height, const float* rgb, const float* feat, const float* motion /* NULL ok */,
+                                          const float* change /* NULL ok */, const float* weight, const frayhip_view* prev_view, const float* hist_in,
+                                          const float* units_in, const struct frayhip_temporal* p, float* hist_out, float* units_out, float* signal,
+                                          float* variance, frayhip_stats* st);
+int  frayhip_temporal_accumulate_weighted_device(int width, int height, const float* d_rgb, const float* d_feat, const float* d_motion /* NULL ok */,
+                                                 const float* d_change /* NULL ok */, const float* d_weight, const frayhip_view* prev_view,
+                                                 const float* d_hist_in, const float* d_units_in, const struct frayhip_temporal* p, float* d_hist_out,
+                                                 float* d_units_out, float* d_signal, float* d_variance, void* hip_stream, frayhip_stats* st);
+/* A struct tag without a typedef, as frayhip_denoise. */
+struct frayhip_history_map {
+    int32_t  base;          /* in:  samples a pixel with a full history gets; >= 1; no default (0): the caller sets it               */
+    int32_t  target;        /* in:  units a pixel's history should amount to after this frame; 1..p->max_history, default 8           */
+    int32_t  max_units;     /* in:  the most units one frame gives a pixel; >= 1, base * max_units <= 2^24, default 8                 */
+    int32_t  reserved;      /* in:  0                                                                                                 */
+    uint64_t budget;        /* in:  the most samples the plane may hold; UINT64_MAX (the default): none                               */
+    uint64_t samples;       /* out: the sum of add                                                                                    */
+    uint64_t boosted;       /* out: pixels with more than one unit                                                                    */
+    int32_t  target_used;   /* out: the t the plane was made with                                                                     */
+    int32_t  pad;
+};
+int  frayhip_history_map_defaults(struct frayhip_history_map* m);
+int  frayhip_history_map(int width, int height, const float* feat, const float* motion /* NULL ok */, const float* change /* NULL ok */,
+                         const frayhip_view* prev_view, const float* hist_in, const float* units_in, const struct frayhip_temporal* p,
+                         struct frayhip_history_map* m, int32_t* add, float* weight, float* held /* NULL ok */, frayhip_stats* st);
+int  frayhip_history_map_device(int width, int height, const float* d_feat, const float* d_motion /* NULL ok */, const float* d_change /* NULL ok */,
+                                const frayhip_view* prev_view, const float* d_hist_in, const float* d_units_in, const struct frayhip_temporal* p,
+                                struct frayhip_history_map* m, int32_t* d_add, float* d_weight, float* d_held /* NULL ok */, void* hip_stream,
+                                frayhip_stats* st);
+
 /* Not covered: SVGF's wider 3 x 3 retry when no bilinear tap counts, feeding a filtered level back into the history, moved lights and the
  * shadows and reflections of moved objects (only a pixel's own first hit is carried back: frayhip_render_features_motion), motion blur,
  * specular motion vectors (what a mirror shows moves with the camera while its first hit does not), learned
@@ -1186,7 +1270,9 @@ int  frayhip_temporal_accumulate_split_adaptive_device(int width, int height, co
  * and denoising across ranks (gather the frame and its features first: frayhip_gather_buckets takes a
  * channel count).  With a change frame the accumulation does shorten the history under a moved light and under the shadows and reflections of
  * moved objects (the history is dropped or faded there, not carried to where the shadow went).  Still not covered with it: a moved node's own pixels entering changed light (their difference is masked: they are the motion frame's
- * business), view-dependent change under camera motion, and any tuning beyond gain. */
+ * business), view-dependent change under camera motion, and any tuning beyond gain.  Not covered by the weighted accumulation and the history
+ * map: split (20-channel) histories, handing the budget's unspent rest to other pixels, and a noise-driven map (frayhip_sample_map) inside a
+ * sequence. */
 
 /* Multi-GPU tile exchange helpers.  pack: gathers this rank's buckets from a
  * full-frame device buffer into a compact bucket-major buffer of
