@@ -267,6 +267,7 @@ SYMBOLS = {
     "frayhip_scene_get_option": (C.c_int, [VP, C.c_char_p, P(i64)]),
     "frayhip_scene_tight_gates": (C.c_int, [VP, C.c_int, P(i64), P(i64)]),
     "frayhip_scene_camera_skip": (C.c_int, [VP, C.c_int, P(i64), P(i64), P(i64), P(i64)]),
+    "frayhip_scene_camera_tiles": (C.c_int, [VP, C.c_int, P(i64)]),
     "frayhip_scene_shade_shortcuts": (C.c_int, [VP, C.c_int, P(i64), P(i64)]),
     "frayhip_render": (C.c_int, [VP, P(Frame), VP, VP, VP, P(Stats)]),
     "frayhip_render_device": (C.c_int, [VP, P(Frame), VP, VP, VP, VP, P(Stats)]),

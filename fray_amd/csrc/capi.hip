@@ -641,6 +641,7 @@ int frayhip_scene_create(const frayhip_scene_desc* desc, frayhip_scene** out)
     if (const char* e = getenv("FRAYHIP_CERTIFIED_SEGMENTS")) sc->certifiedSegments = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_TIGHT_GATES")) sc->tightGates = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_CAMERA_SKIP")) sc->cameraSkip = atol(e) != 0;
+    if (const char* e = getenv("FRAYHIP_CAMERA_TILES")) sc->cameraTiles = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_SHADE_SHORTCUTS")) sc->shadeShortcuts = atol(e) != 0;
     if (const char* e = getenv("FRAYHIP_FUSED_WHITTED_MAX")) { long v = atol(e); if (v >= 0 && v <= 1024) sc->fusedWhittedMax = (int)v; }
     if (const char* e = getenv("FRAYHIP_CSG_LANES")) { long v = atol(e); if (v >= 1 && v <= FRAY_PT_LANES) sc->csgLanes = (int)v; }
@@ -748,6 +749,16 @@ int frayhip_scene_camera_skip(frayhip_scene* s, int enable, int64_t* enabled, in
     if (eligible) *eligible = s->edit->F.nCamSkip;
     if (skipped) *skipped = s->lastCameraSkipped;
     if (waves) *waves = s->lastCameraWaves;
+    return FRAYHIP_OK;
+}
+
+int frayhip_scene_camera_tiles(frayhip_scene* s, int enable, int64_t* enabled)
+{
+    if (!s) { set_error("frayhip_scene_camera_tiles: null scene"); return FRAYHIP_E_ARG; }
+    if (enable < -1 || enable > 1) { set_error("frayhip_scene_camera_tiles: enable must be -1, 0 or 1"); return FRAYHIP_E_ARG; }
+    if (enable >= 0 && s->rendering) { set_error("frayhip_scene_camera_tiles: the scene is rendering a frame"); return FRAYHIP_E_ARG; }
+    if (enable >= 0) s->cameraTiles = enable != 0;
+    if (enabled) *enabled = s->cameraTiles ? 1 : 0;
     return FRAYHIP_OK;
 }
 

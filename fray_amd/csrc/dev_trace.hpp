@@ -1171,6 +1171,25 @@ FD uint32_t camera_skip_nodes(const DScene& S, V3 o, V3 d, bool live)
     return skipNodes;
 }
 
+// The same for a wave whose tile decided the box part already (dev_camtile.hpp "Asked nodes"; the frame's tile table): the per-ray form's guard and bounds on the
+// ray for the records of the nodes in `ask`; a node is returned when every live lane passes.
+FD uint32_t camera_guard_nodes(const DScene& S, V3 o, V3 d, bool live, uint32_t ask)
+{
+    const int nR = S.nCamSkip;
+    const float dx = (float)d.x, dy = (float)d.y, dz = (float)d.z;
+    const float dsum = fabsf(dx) + fabsf(dy) + fabsf(dz);
+    const float ox = (float)o.x, oy = (float)o.y, oz = (float)o.z;
+    const bool range = gate_ray_range(dsum, fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz)), ox + oy + oz);
+    const lanes_t all = lanes(true);
+    uint32_t nodes = 0;
+    for (int r = 0; r < nR; r++) {
+        const FRAY_RO DCamSkip& R = S.camSkip[r];
+        if (!((ask >> R.node) & 1u)) continue;          // (wave-uniform)
+        if (lanes(!live || (gate_guard_f32(R, dx, dy, dz, dsum) & range)) == all) nodes |= 1u << R.node;
+    }
+    return nodes;
+}
+
 // Which end of its wave's queue segment a ray goes to (QMeta, dev_queues.hpp; kernels.hpp): true = it may enter one of the scene's gates (DGate: the boxes
 // of the meshes with long brute-force triangle loops).  A slab test in FP32 on the world-space box -- a scheduling hint, nothing else.
 // Round 5: when every gate of the scene is EXACT (DGate::exact: untransformed nodes) the test is dev_misscert.hpp's FP32 certificate instead, "gate-free" is

@@ -22,6 +22,7 @@
 #include "dev_shade.hpp"
 #include "dev_whitted.hpp"
 #include "dev_queues.hpp"
+#include "dev_camtile.hpp"
 #include <type_traits>
 
 #ifndef FRAY_PRIMARY_WAVES
@@ -90,19 +91,8 @@ template <class A> FD const FRAY_RO A* kernel_args()
 #define KARG(A, P, f) (*(const decltype(A::f)*)(&(P)->f))
 
 // ---- work item -> pixel ------------------------------------------------------------------------
-// Inside a 48x48 bucket the items run over 8x8 pixel tiles (6x6 of them), so the 64 lanes of a wave
-// hold a square of neighbouring pixels: their camera rays walk the same part of a KD-tree.  Every
-// (pixel, sample) is independent, so the order has no effect on the picture.
-FD bool item_pixel(const DFrame& F, int item, int& x, int& y)
-{
-    int k = item / 2304, local = item - k * 2304;
-    int b = F.bucketFirst + k * F.bucketStride;
-    int by = b / F.BW, bx = (b - by * F.BW + FRAYHIP_BUCKET_SKEW * by) % F.BW;      // frayhip_bucket_xy (include/frayhip.h)
-    int tile = local >> 6, in = local & 63;
-    x = bx * 48 + (tile % 6) * 8 + (in & 7);
-    y = by * 48 + (tile / 6) * 8 + (in >> 3);
-    return x < F.W && y < F.H;
-}
+// (dev_camtile.hpp frame_item_pixel, where the host harness of the first bounce's tile table compiles it too)
+FD bool item_pixel(const DFrame& F, int item, int& x, int& y) { return frame_item_pixel(F, item, x, y); }
 // Persistent waves.  The work items of a frame form nItems / 64 tiles (one 8x8 pixel tile = one wave's
 // worth; nItems is a multiple of 2304, hence of 64), split into 8 contiguous ranges with one cursor
 // each (DCursors: one 128-byte line per cursor, zeroed by the host with the counters).  A wave claims
@@ -1195,11 +1185,41 @@ FD void path_shade(const DScene& S, PathStateT<G>& ps, const HitT<ST>& h, const 
 struct LongRng { uint32_t* cols; uint32_t nPaths; DFrame F; int nItems, s0; };
 // FIRST: the batch's first bounce makes its own camera rays (what k_pt_init does for the other cases: stereo, long generators) instead of
 // reading them from a queue -- no 92-byte path record written and read back per camera sample, one launch less per batch.
-struct FirstArgs { DCamera C; DFrame F; int nItems, s0; uint32_t n; const uint32_t* x397; unsigned short* termCount; };
+// tiles (may be null: the camera sample's pixel and the skipped nodes are then computed per lane, as they always were): the frame's tile table (dev_camtile.hpp
+// DCamTile, k_cam_tiles below; frayhip_scene_camera_tiles), one entry per 64-item tile -- a first-bounce wave iteration is one of them at one sample index
+// tileAsk: per tile, the nodes whose box part the tile's corners decided and whose guard they could not (dev_camtile.hpp "Asked nodes"): the wave's own rays decide it
+struct FirstArgs { DCamera C; DFrame F; int nItems, s0; uint32_t n; const uint32_t* x397; unsigned short* termCount; const FRAY_RO DCamTile* tiles; const FRAY_RO uint32_t* tileAsk; };
 // segCertified (may be null): the batch lane's count of next-event segments path_shade certified instead of queueing (render_state.hpp kSegCertifiedOffset), one atomic per wave
 // camSkipped (may be null): two words of the batch lane (render_state.hpp kCamSkippedOffset) -- the (wave, node) pairs the first bounce skipped by its miss records
 // (dev_trace.hpp camera_skip_nodes) and the wave iterations that evaluated them, one atomic each per wave
 struct BounceArgs { DScene S; PathQueue Qin, Qout; ShadowQueue SQ; QMetaRO metaIn; QMeta* metaOut; QMeta* metaShadow; TermBuf TB; StereoBuf SB; LongRng LR; DStats* st; FirstArgs FA; unsigned long long* segCertified; unsigned long long* camSkipped; };
+// The first bounce's tile table (dev_camtile.hpp DCamTile; FirstArgs::tiles above; render_impl.hpp launches it), one thread per 64-item tile of the frame's items: the tile's pixel origin
+// -- item_pixel of its item 0 -- and, with `certify`, the nodes of the miss records whose meshes no camera ray of the tile can hit (tile_surely_misses_mesh, FP64).
+// Filled anew by every frame that uses it: a table that is never kept is never stale.
+// (The record table travels inside the by-value struct, as QMetaRO's pointer does: no kernel of this library takes a bare constant-address-space pointer as an argument.)
+struct CamTileArgs { const FRAY_RO DCamSkip* recs; int nRecs; DCamera C; DFrame F; int nTiles, certify; DCamTile* out; uint32_t* ask; };
+template <int ST>      // (a template so that only render_impl's translation units hold it)
+static __global__ __launch_bounds__(256) void k_cam_tiles(CamTileArgs A)
+{
+    const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (t >= A.nTiles) return;
+    int x0, y0;
+    item_pixel(A.F, t * 64, x0, y0);
+    uint32_t skip = 0, ask = 0;
+    if (A.certify) {
+        const CamTileView V = cam_tile_view(A.C);
+        const CamTileRays R = cam_tile_rays(V, x0, y0);
+        for (int r = 0; r < A.nRecs; r++) {
+            if (!tile_surely_misses_box(A.recs[r], V, R)) continue;
+            if (tile_surely_guarded(A.recs[r], R)) skip |= 1u << A.recs[r].node; else ask |= 1u << A.recs[r].node;
+        }
+    }
+    DCamTile e;
+    e.skip = skip; e.x0 = (uint16_t)x0; e.y0 = (uint16_t)y0;
+    A.out[t] = e;
+    A.ask[t] = ask;
+}
+
 // ARITH: how the translation unit was compiled -- 0 = the reference's arithmetic (-ffp-contract=off: every hit record and every colour is the CPU reference build's, bit
 // for bit), 1 = -ffp-contract=fast (render_contract.hip: multiply-add pairs fused; only for rays AFTER a sample's first closest hit, i.e. colour within
 // north_star's 1e-4 RMS, option "fp_contract").  The parameter only names the kernel apart in profiles; the code is the same source.
@@ -1263,14 +1283,36 @@ static __global__ __launch_bounds__(256, waves_for(ST, kd_variant(ST) ? FRAY_BOU
         if constexpr (CAMSKIP) { ps.o = v3(0, 0, 0); ps.d = v3(0, 0, 0); }               // (every lane's ray is read below, a dead lane's too)
         bool live = di < b1;
         uint32_t i = di, seed0 = 0;
+        bool tabled = false;                                                              // (wave-uniform, like tileSkip)
+        uint32_t tileSkip = 0, tileAsk = 0;
         if constexpr (FIRST) {
             // the camera sample of slot di (k_pt_init's arithmetic): generators seeded by the contract seed, two jitter words, the lens sample
+            int px = 0, py = 0;
+            uint32_t smp = 0;
+            if (live) FA.termCount[di] = 0;                                               // (every slot of the share, those outside the frame too)
+            if constexpr (CAMSKIP) {
+                // With the frame's tile table the wave reads what is a property of its tile -- the pixel origin, the nodes no camera ray of the tile can hit -- instead
+                // of computing it per lane and per sample.  `base` is wave-uniform (a wave's share and its steps are multiples of 64, and so is nItems): said so
+                // to the compiler, the index, the load and the sample index stay on the scalar path.
+                const FRAY_RO DCamTile* const tiles = FA.tiles;
+                if (tiles) {
+                    tabled = true;
+                    const uint32_t ub = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+                    smp = ub / (uint32_t)FA.nItems;
+                    const FRAY_RO DCamTile& T = tiles[(ub - smp * (uint32_t)FA.nItems) >> 6];
+                    tileSkip = T.skip;
+                    tileAsk = FA.tileAsk[(ub - smp * (uint32_t)FA.nItems) >> 6];
+                    px = (int)T.x0 + (int)(lane & 7u); py = (int)T.y0 + (int)(lane >> 3);
+                    live = live && px < FA.F.W && py < FA.F.H;
+                }
+            }
             if (live) {
-                FA.termCount[di] = 0;
-                int px, py;
-                live = item_pixel(FA.F, (int)(di % (uint32_t)FA.nItems), px, py);      // slots of a ragged edge bucket outside the frame: no path
+                if (!tabled) {
+                    live = item_pixel(FA.F, (int)(di % (uint32_t)FA.nItems), px, py);      // slots of a ragged edge bucket outside the frame: no path
+                    smp = di / (uint32_t)FA.nItems;
+                }
                 if (live) {
-                    seed0 = sample_seed(FA.F.seed, (uint32_t)py * (uint32_t)FA.F.W + (uint32_t)px, (uint32_t)(FA.s0 + (int)(di / (uint32_t)FA.nItems)));
+                    seed0 = sample_seed(FA.F.seed, (uint32_t)py * (uint32_t)FA.F.W + (uint32_t)px, (uint32_t)(FA.s0 + (int)smp));
                     Mt rnd = mt_seed_with(seed0, FA.x397[di]), tab = rnd;
                     const float ox = rng_float(rnd), oy = rng_float(rnd);                  // gi: always jittered (main.cpp:351-353)
                     const double fx = (double)((float)px + ox), fy = (double)((float)py + oy);
@@ -1290,7 +1332,12 @@ static __global__ __launch_bounds__(256, waves_for(ST, kd_variant(ST) ? FRAY_BOU
         uint32_t skipNodes = 0;                                                           // (wave-uniform)
         if constexpr (CAMSKIP) {
             if (S.nCamSkip > 0 && lanes(live) != 0) {
-                skipNodes = camera_skip_nodes(S, ps.o, ps.d, live);
+                // the tile's word (dev_camtile.hpp: decided once per frame from the tile's corner directions); per-lane starts (`dof`) and a frame without the table
+                // ask the wave's own rays
+                if (tabled && !FA.C.dof) {
+                    skipNodes = tileSkip;
+                    if (tileAsk) skipNodes |= camera_guard_nodes(S, ps.o, ps.d, live, tileAsk);      // (the headline frame: about two tiles in a hundred)
+                } else skipNodes = camera_skip_nodes(S, ps.o, ps.d, live);
                 camSkipped += (uint32_t)__builtin_popcount(skipNodes);
                 camWaves++;
             }

@@ -521,7 +521,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                 nQueue = nPaths + (size_t)bounce_grid(nPaths, (ST & 2) != 0 && maxLanes == 1) * 4 * 128;
                 laneBytes = 2 * queue_bytes(nQueue) + shadow_bytes(nQueue) + nPaths * 12 + (tabled ? 0 : nPaths * 4) + 4096 + nPaths * termBytes + 512 + (longRng ? nPaths * 2 * 624 * sizeof(uint32_t) + 256 : 0) +
                             (stereo ? nPaths * (12 + 6 * 8 + 6 * 4) + 16 * 256 : 0);
-                const int rc = ensure_work_or_shrink(sc, (size_t)nLanes * laneBytes + (size_t)nItems * 12 + 4096, f->spp_chunk <= 0 && (chunk > 1 || nLanes > 1));
+                const int rc = ensure_work_or_shrink(sc, (size_t)nLanes * laneBytes + (size_t)nItems * 12 + 4096 + r256((size_t)(nItems >> 6) * sizeof(DCamTile)) + r256((size_t)(nItems >> 6) * sizeof(uint32_t)), f->spp_chunk <= 0 && (chunk > 1 || nLanes > 1));
                 if (rc == FRAYHIP_RETRY_SMALLER) { if (chunk == 1 && maxLanes > 1) maxLanes--; continue; }
                 if (rc) return rc;
                 if (tabled && !sc->seedTab.serving) continue;          // the workspace took the table's memory: plan again with the per-batch seed words
@@ -546,6 +546,8 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
             } lane[FRAY_PT_LANES];
             unsigned char* p = (unsigned char*)sc->d_work;
             float* sum = (float*)p; p += ((size_t)nItems * 12 + 255) / 256 * 256;
+            DCamTile* const tileTable = (DCamTile*)p; p += r256((size_t)(nItems >> 6) * sizeof(DCamTile));
+            uint32_t* const tileAsk = (uint32_t*)p; p += r256((size_t)(nItems >> 6) * sizeof(uint32_t));
             for (int k = 0; k < nLanes; k++) {
                 Lane& L = lane[k];
                 L.stream = k == 0 ? stream : sc->laneStream[k];
@@ -574,6 +576,15 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
             }
             const StereoBuf SBnone{};
             const int nBounce = set.maxTraceDepth + 2;
+            // frayhip_scene_camera_tiles: the fused mono path's first bounces read their tiles' pixel origins and skipped nodes from a table made here, on the
+            // caller's stream, before any lane starts (the skip words are zero for per-lane starts, `dof`, and while frayhip_scene_camera_skip is off)
+            const DCamTile* tiles = nullptr;
+            if (sc->cameraTiles && !stereo && !longRng && F.BW * 48 <= FRAY_CAMTILE_MAX_COORD && F.BH * 48 <= FRAY_CAMTILE_MAX_COORD) {
+                const int nTiles = nItems >> 6;
+                const CamTileArgs TA{S.camSkip, S.nCamSkip, C, F, nTiles, (S.nCamSkip > 0 && !C.dof) ? 1 : 0, tileTable, tileAsk};
+                hipLaunchKernelGGL(k_cam_tiles<ST>, dim3((nTiles + 255) / 256), dim3(256), 0, stream, TA);
+                tiles = tileTable;
+            }
             HIP_TRY(hipEventRecord(sc->evLaneStart, stream));               // the side lanes start after whatever precedes this frame on the caller's stream
             for (int k = 1; k < nLanes; k++) HIP_TRY(hipStreamWaitEvent(sc->laneStream[k], sc->evLaneStart, 0));
             auto trace = [&](int batch) -> int {
@@ -604,7 +615,7 @@ int render_impl(frayhip_scene* sc, const frayhip_frame* f, float* d_rgb, int32_t
                         HIP_TRY(hipEventRecord(ea, ls));
                         const LongRng LR{L.mtCols, (uint32_t)nPaths, F, nItems, s0};
                         const TermBuf TB{L.terms, L.termCount, (uint32_t)nPaths, b};
-                        const FirstArgs FA{C, F, nItems, s0, (uint32_t)((size_t)nItems * cn), x397, L.termCount};
+                        const FirstArgs FA{C, F, nItems, s0, (uint32_t)((size_t)nItems * cn), x397, L.termCount, (const FRAY_RO DCamTile*)tiles, (const FRAY_RO uint32_t*)(tiles ? tileAsk : nullptr)};
                         const BounceArgs BA{S, L.Q[b & 1], L.Q[(b + 1) & 1], L.SQ, mIn, L.meta + ((b + 1) & 1), L.meta + 2, TB, save, LR, sc->d_stats, FA, L.segCertified, L.camSkipped};
                         // option "fp_contract": bounces after a sample's first closest hit (and every visibility query) are colour, bounded by RMS and not by
                         // bits -- they run the kernels compiled with fused multiply-adds (render_contract.hip; not built for the Cube / CSG variants, which

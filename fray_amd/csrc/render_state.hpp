@@ -84,6 +84,7 @@ struct frayhip_scene {
     bool tightGates = true;           // frayhip_scene_tight_gates: the producers test an eligible mesh's gate by its own triangles' box and a guard (dev_gatecert.hpp) instead of its reference box
     bool cameraSkip = true;           // frayhip_scene_camera_skip: a first-bounce wave leaves out the meshes all its camera rays provably miss (dev_trace.hpp camera_skip_nodes, dev_scene.hpp DCamSkip)
     bool shadeShortcuts = true;       // frayhip_scene_shade_shortcuts: the path tracer's timed kernels shade the hits of an all-untransformed flat-mesh scene without the transform and a stored normal, and axis-scaled lights by their diagonals (dev_shade.hpp finalize_hit, light_nth_sample; dev_trace.hpp light_intersect)
+    bool cameraTiles = true;          // frayhip_scene_camera_tiles: the first bounce reads its tile's pixel origin and skipped nodes from a per-frame table (dev_camtile.hpp, kernels.hpp k_cam_tiles)
     long long lastCameraSkipped = 0, lastCameraWaves = 0;   // the last frame's (wave, node) pairs skipped that way, and the first-bounce wave iterations that evaluated the records (frayhip_scene_camera_skip)
     long long lastShadowCertified = 0;   // the last frame's next-event segments decided that way (frayhip_scene_get_option "shadow_segments_certified"); they are part of lastShadowSegments
     long long lastShadowNodesSkipped = 0;   // the last frame's sum over k_pt_shadow's wave iterations of the nodes skipped that way (frayhip_scene_get_option "shadow_nodes_skipped")

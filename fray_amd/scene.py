@@ -964,6 +964,14 @@ class Scene:
         _check(lib.frayhip_scene_camera_skip(self._dev, -1 if enable is None else int(bool(enable)), C.byref(on), C.byref(n), C.byref(skipped), C.byref(waves)))
         return int(on.value), int(n.value), int(skipped.value), int(waves.value)
 
+    def camera_tiles(self, enable=None):
+        """frayhip_scene_camera_tiles: switches the first bounce's tile table on or off (None leaves the switch alone) and returns the switch: a first-bounce wave
+        reads its tile's pixel origin and the meshes no camera ray of the tile can hit from a table made once per frame."""
+        self._need_dev()
+        on = C.c_int64(0)
+        _check(lib.frayhip_scene_camera_tiles(self._dev, -1 if enable is None else int(bool(enable)), C.byref(on)))
+        return int(on.value)
+
     def shade_shortcuts(self, enable=None):
         """frayhip_scene_shade_shortcuts: switches the shading shortcuts on or off (None leaves the switch alone) and returns (enabled, eligible): bit 0 of eligible --
         every node is an untransformed flat mesh, shaded without its transform and with a stored world normal; bit 1 -- every light is an axis-scaled RectLight."""

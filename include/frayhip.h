@@ -411,6 +411,17 @@ int  frayhip_scene_tight_gates(frayhip_scene* s, int enable, int64_t* enabled, i
  * number of miss records of the scene, as last uploaded or updated; the last frame's (wave, node) pairs left out; and the first-bounce wave iterations of
  * 64 camera rays that evaluated the records (those with a ray in the frame). */
 int  frayhip_scene_camera_skip(frayhip_scene* s, int enable, int64_t* enabled, int64_t* eligible, int64_t* skipped, int64_t* waves);
+/* Camera tiles.  Path tracing, first bounce, the same frames and the same kernel as camera skip above: what is a property of a wave's 8x8 pixel tile is decided
+ * once per frame instead of per lane and per sample.  A small kernel fills a table with one entry per tile of the frame's items -- the tile's pixel origin and,
+ * for a pinhole camera (no depth of field), the eligible meshes that NO camera ray of the tile can hit, whatever its jitter: the certificate of camera skip
+ * evaluated on the tile's four corner directions (fray_amd/csrc/dev_camtile.hpp) -- and a first-bounce wave reads its entry.  The table is made anew by every
+ * such frame.  The skipped meshes are ones no ray of the tile hits as the reference's own arithmetic computes it, so the picture is the same bit for bit
+ * (tests/test_gpu_camera_tiles.py); a tile's word may hold fewer meshes than its 64 rays at one sample index would have agreed on.  With a depth-of-field
+ * camera, or with camera skip switched off, the words are zero (the per-wave test of camera skip serves a depth-of-field camera) and the table gives the pixel
+ * origin only.  On by default; the environment variable FRAYHIP_CAMERA_TILES=0 presets it off at frayhip_scene_create.  frayhip_scene_camera_skip's `skipped`
+ * and `waves` count the same things with either source of the word.
+ * enable: 1 / 0 switches it on / off (not while the scene renders), -1 leaves it.  enabled (may be null): the switch. */
+int  frayhip_scene_camera_tiles(frayhip_scene* s, int enable, int64_t* enabled);
 /* Shade shortcuts.  Path tracing, the timed kernels of scenes without Cube / CSG geometry, KD meshes and textures, in both arithmetics: arithmetic whose
  * result is known before it runs is left out.  Bit 0 of `eligible`, the nodes: EVERY node is an untransformed mesh (offset +0, m = invM = I bit for bit) that is
  * flat, has no KD-tree, at most 32 triangles, a shader that reads no (u, v) and no bump texture -- a hit is then shaded without the node's transform
