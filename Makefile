@@ -28,8 +28,9 @@ HOST_OBJ := $(HOST_SRC:.cpp=.o)
 #   adaptive<st>.o  adaptive_variant.hip   adaptive frames (frayhip_render_adaptive)
 #   samplemap<st>.o samplemap_variant.hip sample maps (frayhip_render_samples_map)
 #   features<st>.o  features_variant.hip   feature frames (frayhip_render_features) and, as a second instantiation, feature + motion frames (frayhip_render_features_motion)
+#   specular<st>.o  features_specular_variant.hip   specular feature frames (frayhip_render_features_specular)
 ST_WORDS := 0 1 2 3 4 5 8 9
-ST_SETS  := variant:render_variant query:query_variant shade:shade_variant adaptive:adaptive_variant samplemap:samplemap_variant features:features_variant
+ST_SETS  := variant:render_variant query:query_variant shade:shade_variant adaptive:adaptive_variant samplemap:samplemap_variant features:features_variant specular:features_specular_variant
 ST_OBJ   := $(foreach set,$(ST_SETS),$(foreach st,$(ST_WORDS),fray_amd/csrc/$(firstword $(subst :, ,$(set)))$(st).o))
 # render_contract.hip: the path tracer's bounce / shadow kernels once more per flag word, built with fused multiply-adds (option "fp_contract")
 CONTRACT_OBJ := $(foreach st,0 1 4 5 8 9,fray_amd/csrc/variantC$(st).o)

@@ -6,6 +6,8 @@ src/main.cpp:494-530):  python -m fray_amd scene.fray -o out.bmp [--width W --he
                                                                                           JSON line: its rungs, mean spp and the share of pixels per rung)
                          python -m fray_amd scene.fray -o out.bmp --denoise [--feature-samples N] [--features-out FILE.npy]   (the frame denoised
                                                                                           with its first-hit features; --features-out alone saves them)
+                         python -m fray_amd scene.fray -o out.bmp --denoise --specular-features K   (the guides follow mirrors and glass through at most K
+                                                                                          steps to what they show; with --features-out and --frames too)
                          python -m fray_amd scene.fray -o out.bmp --denoise --frames N [--yaw-step DEG]   (N frames with temporal accumulation, the scene
                                                                                           file's camera turned by DEG per frame: out_0000.bmp ...)
                          python -m fray_amd scene.fray -o out.bmp --frames N --move NODE DX DY DZ [--move ...] [--denoise]   (N frames of one uploaded
@@ -73,6 +75,10 @@ def build_parser():
                     help="camera samples per pixel of the feature frame (--denoise, --features-out; clamped to the frame's spp; default 4)")
     ap.add_argument("--features-out", metavar="FILE.npy",
                     help="also save the feature frame, float32 [H, W, 10]: position, normal, albedo, depth")
+    ap.add_argument("--specular-features", type=int, default=0, metavar="K",
+                    help="with --denoise, --features-out or --frames: follow Refl / Refr nodes through at most K steps (1 .. 8) and store the virtual "
+                         "hit they show as the guide (Scene.render_features_specular); default 0: first-hit features.  Not with --motion-vectors "
+                         "(motion frames carry first hits only) or --refine")
     ap.add_argument("--frames", type=int, metavar="N",
                     help="with --denoise: render N frames with temporal accumulation (Scene.render_sequence; frame k has seed SEED + k) and write "
                          "OUTPUT's name with _0000, _0001, ... before the extension")
@@ -188,6 +194,16 @@ def check_args(ap, a):
         ap.error("--move needs --frames")
     if a.motion_vectors and not (a.denoise and a.frames is not None and a.move):
         ap.error("--motion-vectors needs --denoise --frames N --move ...")
+    if not 0 <= a.specular_features <= 8:
+        ap.error("--specular-features must be 0 .. 8")
+    if a.specular_features and not (a.denoise or a.features_out):
+        ap.error("--specular-features needs --denoise, --features-out or --denoise --frames N")
+    if a.specular_features and a.frames is not None and not a.denoise:
+        ap.error("--specular-features with --frames needs --denoise: plain frames render no feature frame")
+    if a.specular_features and a.motion_vectors:
+        ap.error("--specular-features cannot be combined with --motion-vectors: motion frames carry first hits only")
+    if a.specular_features and a.refine is not None:
+        ap.error("--specular-features cannot be combined with --refine")
     if a.change_samples < 0:
         ap.error("--change-samples must be >= 0")
     if a.change_samples and not a.motion_vectors:
@@ -337,7 +353,8 @@ def main(argv=None):
         if a.boost is not None:
             boost = dict(target=a.boost, max_units=8 if a.boost_max is None else a.boost_max, budget=a.sample_budget)
         for k, (img, _raw, info) in enumerate(s.render_sequence(orbit(start, a.frames, a.yaw_step), seed=a.seed, feature_samples=a.feature_samples,
-                                                                edit=edit, split=a.split, change_samples=a.change_samples, boost=boost)):
+                                                                edit=edit, split=a.split, change_samples=a.change_samples, boost=boost,
+                                                                specular=a.specular_features)):
             path = sequence_path(a.output, k)
             img = img.cpu().numpy()
             if lib.frayhip_save_bmp(path.encode(), img.ctypes.data, img.shape[1], img.shape[0]):
@@ -388,7 +405,7 @@ def main(argv=None):
             img = denoise_signal(img, noise, feat, demodulate=0)
             spp_text += ", denoised with its own noise estimate"
     elif a.denoise and a.split:
-        img, raw, info = s.render_denoised_split(seed=a.seed, feature_samples=a.feature_samples)
+        img, raw, info = s.render_denoised_split(seed=a.seed, feature_samples=a.feature_samples, specular=a.specular_features)
         st = info["render"]
         spp_text = "%d spp, direct and indirect light denoised apart: features %.1f ms, filters %.1f + %.1f ms" % (
             s.samples_per_pixel(), info["features"]["ms_kernels"], info["denoise_direct"]["ms_kernels"], info["denoise_indirect"]["ms_kernels"])
@@ -403,7 +420,7 @@ def main(argv=None):
         spp_text = "%d spp, direct and indirect light kept apart" % s.samples_per_pixel()
         save_components(a.components_out, direct, indirect, nd, ni, s.samples_per_pixel(), a.seed)
     elif a.denoise:
-        img, raw, info = s.render_denoised(seed=a.seed, feature_samples=a.feature_samples)
+        img, raw, info = s.render_denoised(seed=a.seed, feature_samples=a.feature_samples, specular=a.specular_features)
         st = info["render"]
         spp_text = "%d spp, denoised%s: features %.1f ms, filter %.1f ms" % (
             s.samples_per_pixel(), "" if info["rgb_half"] is not None else " without the half-spp estimate",
@@ -455,7 +472,9 @@ def main(argv=None):
         spp_text = "%d spp" % s.samples_per_pixel()
     print("Render took %.2fs (%d x %d, %s, kernels %.1f ms)" % (time.time() - t0, img.shape[1], img.shape[0], spp_text, st["ms_kernels"]))
     if a.features_out and not a.denoise:
-        np.save(a.features_out, s.render_features(min(a.feature_samples, s.samples_per_pixel()), seed=a.seed))
+        n_feat = min(a.feature_samples, s.samples_per_pixel())
+        np.save(a.features_out, s.render_features_specular(a.specular_features, n_feat, seed=a.seed) if a.specular_features
+                else s.render_features(n_feat, seed=a.seed))
         print("wrote", a.features_out)
     rc = lib.frayhip_save_bmp(a.output.encode(), img.ctypes.data, img.shape[1], img.shape[0])
     if rc:

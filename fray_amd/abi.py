@@ -206,6 +206,7 @@ class Denoise(C.Structure):
 
 FEAT_CHANNELS = 10      # FRAYHIP_FEAT_CHANNELS: position[3], normal[3], albedo[3], depth
 MOTION_CHANNELS = 8     # FRAYHIP_MOTION_CHANNELS: {P'.xyz, moved}, {n'.xyz, 0}
+SPECULAR_MAX_BOUNCES = 8   # FRAYHIP_SPECULAR_MAX_BOUNCES: frayhip_render_features_specular's max_bounces is 1 .. 8
 
 
 class View(C.Structure):
@@ -292,6 +293,8 @@ SYMBOLS = {
     "frayhip_sample_map_budget_device": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, P(SampleMap), P(SampleBudget), VP, VP, P(Stats)]),
     "frayhip_render_features": (C.c_int, [VP, P(Frame), C.c_int, VP, P(Stats)]),
     "frayhip_render_features_device": (C.c_int, [VP, P(Frame), C.c_int, VP, VP, P(Stats)]),
+    "frayhip_render_features_specular": (C.c_int, [VP, P(Frame), C.c_int, C.c_int, VP, VP, P(Stats)]),
+    "frayhip_render_features_specular_device": (C.c_int, [VP, P(Frame), C.c_int, C.c_int, VP, VP, VP, P(Stats)]),
     "frayhip_render_features_motion": (C.c_int, [VP, P(Frame), C.c_int, P(Transform), C.c_int, VP, VP, P(Stats)]),
     "frayhip_render_features_motion_device": (C.c_int, [VP, P(Frame), C.c_int, P(Transform), C.c_int, VP, VP, VP, P(Stats)]),
     "frayhip_denoise_defaults": (C.c_int, [P(Denoise)]),

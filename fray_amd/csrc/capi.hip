@@ -370,6 +370,7 @@ struct SceneEdit {
 
 namespace frayhip_detail {
 const DNode* host_nodes(const frayhip_scene* s) { return (const DNode*)(s->edit->host.data() + s->edit->hostOff[s->edit->F.tNodes]); }
+const DShader* host_shaders(const frayhip_scene* s) { return (const DShader*)(s->edit->host.data() + s->edit->hostOff[s->edit->F.tShaders]); }
 }  // namespace frayhip_detail
 
 namespace {

@@ -1,6 +1,7 @@
-// C ABI, feature frames (include/frayhip.h "feature frames", "motion frames"): frayhip_render_features, frayhip_render_features_motion and their
-// _device entries.  Argument checks, the frame record, the scene's kernel flag word, the motion frame's table of previous transforms, events and
-// counters; the kernel is k_features<ST, MOTION> of features_variant.hip (one object per flag word).
+// C ABI, feature frames (include/frayhip.h "feature frames", "specular feature frames", "motion frames"): frayhip_render_features,
+// frayhip_render_features_specular, frayhip_render_features_motion and their _device entries.  Argument checks, the frame record, the scene's
+// kernel flag word, the motion frame's table of previous transforms, events and counters; the kernels are k_features<ST, MOTION> of
+// features_variant.hip and k_features_specular<ST> of features_specular_variant.hip (one object per flag word each).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,7 +12,7 @@
 #include <string>
 #include <vector>
 
-#include "features.hpp"
+#include "features_specular.hpp"
 #include "kernels.hpp"
 
 namespace {
@@ -39,6 +40,34 @@ __global__ __launch_bounds__(256) void k_motion_zero(DFrame F, int nItems, float
     }
 }
 
+// ... and of the specular frame's plane of bounce counts
+__global__ __launch_bounds__(256) void k_plane_zero(DFrame F, int nItems, float* __restrict__ plane)
+{
+    for (int item = blockIdx.x * blockDim.x + threadIdx.x; item < nItems; item += gridDim.x * blockDim.x) {
+        int x, y;
+        if (!item_pixel(F, item, x, y)) continue;
+        plane[(size_t)y * F.W + x] = 0.0f;
+    }
+}
+
+// The specular frame's request: the bounce limit, and where the plane of counts goes (device, or null)
+struct SpecularCall {
+    int maxBounces;
+    float* d_bounces;
+};
+
+// Whether any node's own shader is Refl or Refr, from the host copies frayhip_scene_update keeps current: looked up per call
+bool has_specular_node(const frayhip_scene* sc, int nNodes)
+{
+    const DNode* const nodes = host_nodes(sc);
+    const DShader* const shaders = host_shaders(sc);
+    for (int i = 0; i < nNodes; i++) {
+        const int kind = shaders[nodes[i].shader].kind;
+        if (kind == 3 || kind == 4) return true;
+    }
+    return false;
+}
+
 // The motion frame's request: the caller's previous transforms (host), and where the frame goes (device)
 struct MotionCall {
     const frayhip_transform* prevT;
@@ -47,13 +76,19 @@ struct MotionCall {
 
 // Every check of both entries, in this order; none touches the device.  FRAYHIP_E_ARG for the arguments, FRAYHIP_E_UNSUPPORTED for a frame
 // whose rays the feature pass does not reproduce (stereo, long generators).
-int check(const char* who, frayhip_scene* s, const frayhip_frame* f, int n, const float* feat, bool device)
+// spec: the specular entries' request (their scene-free checks sit with the others'), or null.
+int check(const char* who, frayhip_scene* s, const frayhip_frame* f, int n, const float* feat, bool device, const SpecularCall* spec = nullptr)
 {
     if (!f) return bad(who, "null frame");
     if (!feat) return bad(who, "null feat");
     if (device && misaligned(feat, 4)) return bad(who, "device pointer to floats not 4-byte aligned");
     if (f->mode != FRAYHIP_MODE_RENDER) return bad(who, "mode must be FRAYHIP_MODE_RENDER");
     if (n < 1) return bad(who, "n_samples must be >= 1");
+    if (spec) {
+        if (spec->maxBounces < 1 || spec->maxBounces > FRAYHIP_SPECULAR_MAX_BOUNCES)
+            return bad(who, "max_bounces must be 1 .. " + std::to_string(FRAYHIP_SPECULAR_MAX_BOUNCES) + " (" + std::to_string(spec->maxBounces) + ")");
+        if (device && misaligned(spec->d_bounces, 4)) return bad(who, "device pointer to floats not 4-byte aligned (bounces)");
+    }
     if (!s) return bad(who, "null scene");
     if (s->rendering) return bad(who, "the scene is rendering a frame (a call from inside its progress callback?)");
     const int nb = frame_record(s, f->bucket_first, f->bucket_stride, f->seed).nBuckets;
@@ -83,10 +118,21 @@ int check_motion(const char* who, frayhip_scene* s, const frayhip_transform* pre
     return FRAYHIP_OK;
 }
 
+// ... and what the specular entries add once the scene is known to be there
+int check_specular(const char* who, frayhip_scene* s, const float* feat, const float* bounces)
+{
+    if (!bounces) return FRAYHIP_OK;
+    const size_t n = (size_t)s->settings.frameWidth * s->settings.frameHeight;
+    const uintptr_t a = (uintptr_t)feat, b = (uintptr_t)bounces;
+    if (a < b + n * 4 && b < a + n * 4 * FRAYHIP_FEAT_CHANNELS) return bad(who, "feat and bounces must not overlap");
+    return FRAYHIP_OK;
+}
+
 // The one device path of both entries (d_feat: device, frame-sized).  The scene is held as a frame holds it (`rendering`), so that nothing
 // re-enters it; on an early return the stream is drained first.  Nothing of the last frame's record is written.
-// mc: the motion frame's request, or null.
-int run(frayhip_scene* sc, const frayhip_frame* f, int n, float* d_feat, hipStream_t stream, frayhip_stats* st, const MotionCall* mc = nullptr)
+// mc: the motion frame's request, or null; spec: the specular frame's, or null (never both).
+int run(frayhip_scene* sc, const frayhip_frame* f, int n, float* d_feat, hipStream_t stream, frayhip_stats* st, const MotionCall* mc = nullptr,
+        const SpecularCall* spec = nullptr)
 {
     const auto t0 = std::chrono::steady_clock::now();
     Busy busy(sc, stream);
@@ -144,13 +190,28 @@ int run(frayhip_scene* sc, const frayhip_frame* f, int n, float* d_feat, hipStre
             hipLaunchKernelGGL(k_motion_zero, dim3(grid_for((size_t)nItems)), dim3(256), 0, stream, F, nItems, mc->d_motion);
             HIP_TRY(hipGetLastError());
         }
+        if (spec && spec->d_bounces) {
+            hipLaunchKernelGGL(k_plane_zero, dim3(grid_for((size_t)nItems)), dim3(256), 0, stream, F, nItems, spec->d_bounces);
+            HIP_TRY(hipGetLastError());
+        }
     } else if (nItems > 0) {
         hipEvent_t e0 = pool_event(sc->evPool, 0), e1 = pool_event(sc->evPool, 1);
         if (!e0 || !e1) return FRAYHIP_E_HIP;
         const FeatureArgs A{S, C, F, nItems, n, d_feat, sc->d_stats, cursors, mc ? mc->d_motion : nullptr, d_prev, d_moved};
         HIP_TRY(hipEventRecord(e0, stream));
-        for_flag_word(flag_word(sc, stats), [&](auto w) { launch_features<decltype(w)::value>(stream, A, mc != nullptr); });
-        HIP_TRY(hipGetLastError());
+        if (spec && has_specular_node(sc, S.nNodes)) {
+            const SpecularFeatureArgs SA{S, C, F, nItems, n, spec->maxBounces, d_feat, spec->d_bounces, sc->d_stats, cursors};
+            for_flag_word(flag_word(sc, stats), [&](auto w) { launch_features_specular<decltype(w)::value>(stream, SA); });
+            HIP_TRY(hipGetLastError());
+        } else {
+            // (a specular call on a scene without a Refl / Refr node: no chain can start, so the first-hit kernel and a zero plane)
+            for_flag_word(flag_word(sc, stats), [&](auto w) { launch_features<decltype(w)::value>(stream, A, mc != nullptr); });
+            HIP_TRY(hipGetLastError());
+            if (spec && spec->d_bounces) {
+                hipLaunchKernelGGL(k_plane_zero, dim3(grid_for((size_t)nItems)), dim3(256), 0, stream, F, nItems, spec->d_bounces);
+                HIP_TRY(hipGetLastError());
+            }
+        }
         HIP_TRY(hipEventRecord(e1, stream));
         nEvents = 2;
     }
@@ -159,7 +220,7 @@ int run(frayhip_scene* sc, const frayhip_frame* f, int n, float* d_feat, hipStre
     DStats d;
     HIP_TRY(hipMemcpy(&d, sc->d_stats, sizeof d, hipMemcpyDeviceToHost));
     if (d.rngOverflow) {
-        set_error(std::string(mc ? "frayhip_render_features_motion" : "frayhip_render_features") + ": a camera sample left the supported envelope (a lens sample past 227 generator words, or a CsgOp operand "
+        set_error(std::string(mc ? "frayhip_render_features_motion" : spec ? "frayhip_render_features_specular" : "frayhip_render_features") + ": a camera sample left the supported envelope (a lens sample past 227 generator words, or a CsgOp operand "
                   "with more intersections than the device path holds)");
         return FRAYHIP_E_UNSUPPORTED;
     }
@@ -199,6 +260,39 @@ int frayhip_render_features(frayhip_scene* s, const frayhip_frame* f, int n_samp
     if (f->bucket_stride > 1 || f->bucket_first != 0) HIP_TRY(hipMemcpy(d, feat, bytes, hipMemcpyHostToDevice));
     if (const int rc = run(s, f, n_samples, d, nullptr, st)) return rc;
     HIP_TRY(hipMemcpy(feat, d, bytes, hipMemcpyDeviceToHost));
+    return FRAYHIP_OK;
+}
+
+int frayhip_render_features_specular_device(frayhip_scene* s, const frayhip_frame* f, int n_samples, int max_bounces, float* d_feat, float* d_bounces,
+                                            void* hip_stream, frayhip_stats* st)
+{
+    const char* who = "frayhip_render_features_specular_device";
+    const SpecularCall spec{max_bounces, d_bounces};
+    if (const int rc = check(who, s, f, n_samples, d_feat, true, &spec)) return rc;
+    if (const int rc = check_specular(who, s, d_feat, d_bounces)) return rc;
+    return run(s, f, n_samples, d_feat, (hipStream_t)hip_stream, st, nullptr, &spec);
+}
+
+int frayhip_render_features_specular(frayhip_scene* s, const frayhip_frame* f, int n_samples, int max_bounces, float* feat, float* bounces, frayhip_stats* st)
+{
+    const char* who = "frayhip_render_features_specular";
+    const SpecularCall asked{max_bounces, bounces};
+    if (const int rc = check(who, s, f, n_samples, feat, false, &asked)) return rc;
+    if (const int rc = check_specular(who, s, feat, bounces)) return rc;
+    const size_t px = (size_t)s->settings.frameWidth * s->settings.frameHeight, nf = px * FRAYHIP_FEAT_CHANNELS;
+    DeviceArrays B(std::string(who) + ": out of device memory");
+    float* d;
+    if (const int rc = B.alloc(d, nf + (bounces ? px : 0))) return rc;
+    float* const db = bounces ? d + nf : nullptr;
+    // pixels outside this call's buckets keep what the caller had in the buffers
+    if (f->bucket_stride > 1 || f->bucket_first != 0) {
+        HIP_TRY(hipMemcpy(d, feat, nf * sizeof(float), hipMemcpyHostToDevice));
+        if (bounces) HIP_TRY(hipMemcpy(db, bounces, px * sizeof(float), hipMemcpyHostToDevice));
+    }
+    const SpecularCall spec{max_bounces, db};
+    if (const int rc = run(s, f, n_samples, d, nullptr, st, nullptr, &spec)) return rc;
+    HIP_TRY(hipMemcpy(feat, d, nf * sizeof(float), hipMemcpyDeviceToHost));
+    if (bounces) HIP_TRY(hipMemcpy(bounces, db, px * sizeof(float), hipMemcpyDeviceToHost));
     return FRAYHIP_OK;
 }
 

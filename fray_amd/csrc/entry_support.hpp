@@ -64,6 +64,8 @@ int frame_spp(const frayhip_scene* s);
 DScene frame_scene(const frayhip_scene* s);
 // The host copy of the uploaded scene's node table (frayhip_scene_update keeps it current): S.nNodes records, inner pointers not to be followed
 const DNode* host_nodes(const frayhip_scene* s);
+// ... and of its shader table (S.nShaders records), kept current the same way
+const DShader* host_shaders(const frayhip_scene* s);
 // Size and bucket grid of a frame; frame_record: with the call's buckets (stride <= 0: 1; nBuckets < 0: a bad range) and the frame's spp, seed and jitter
 inline DFrame frame_grid(int W, int H)
 {

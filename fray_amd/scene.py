@@ -1485,6 +1485,38 @@ class Scene:
         _check(lib.frayhip_render_features(self._dev, C.byref(fr), int(n_samples), feat.ctypes.data, C.byref(st)))
         return (feat, st.as_dict()) if stats else feat
 
+    def render_features_specular(self, max_bounces=4, n_samples=4, seed=42, bucket_first=0, bucket_stride=1, stats=False, out=None, bounces=False):
+        """render_features with every camera sample followed through Refl / Refr nodes to the first hit that is neither, at most max_bounces
+        (1 .. 8) steps (frayhip_render_features_specular, "specular feature frames"): float32 [H, W, 10] with the virtual hit's position (the
+        point at the path's length along the primary ray: the mirror image for a planar mirror), the terminal normal unfolded through the
+        mirrors, the product of the chain's mult and the terminal albedo, and the path's length as depth.  A sample whose first hit is not
+        specular has render_features' row bit for bit.  Layered glass, glossy lobes and total internal reflection are not followed.
+        bounces=True also returns the plane of steps taken, float32 [H, W] (the mean over the samples).  out: an array to fill instead of a new
+        zeroed one, or with bounces=True a (feat, bounces) pair (pixels outside the call's buckets keep their values).
+        Returns feat, then the plane with bounces=True, then the stats dict with stats=True."""
+        self._need_dev()
+        W, H = self.frame_size
+        if bounces:
+            feat, plane = out if out is not None else (np.zeros((H, W, abi.FEAT_CHANNELS), np.float32), np.zeros((H, W), np.float32))
+        else:
+            feat, plane = (out if out is not None else np.zeros((H, W, abi.FEAT_CHANNELS), np.float32)), None
+        for a, shape in ((feat, (H, W, abi.FEAT_CHANNELS)), (plane, (H, W))):
+            if a is not None and (not isinstance(a, np.ndarray) or a.shape != shape or a.dtype != np.float32 or not a.flags.c_contiguous):
+                raise ValueError("render_features_specular: out must be C-contiguous float32, shaped %s (and %s for the bounces)"
+                                 % ((H, W, abi.FEAT_CHANNELS), (H, W)))
+        st = abi.Stats()
+        fr = self._frame(abi.MODE_RENDER, seed, bucket_first, bucket_stride, 0, stats)
+        _check(lib.frayhip_render_features_specular(self._dev, C.byref(fr), int(n_samples), int(max_bounces), feat.ctypes.data,
+                                                    plane.ctypes.data if plane is not None else None, C.byref(st)))
+        res = (feat,) + ((plane,) if bounces else ()) + ((st.as_dict(),) if stats else ())
+        return res if len(res) > 1 else feat
+
+    def _features_for(self, n_samples, seed, specular):
+        """(feat, stats dict) of render_denoised / render_denoised_split: first-hit guides, or with specular=K > 0 the virtual-hit ones."""
+        if specular:
+            return self.render_features_specular(int(specular), n_samples, seed=seed, stats=True)
+        return self.render_features(n_samples, seed=seed, stats=True)
+
     def node_transforms(self):
         """A copy of the current nodes' frayhip_transform records (self.desc's, as update() pushes them), as a ctypes array of abi.Transform: the
         snapshot a caller takes before editing the nodes, for render_features_motion."""
@@ -1526,11 +1558,13 @@ class Scene:
                                                   C.byref(st)))
         return (feat, motion, st.as_dict()) if stats else (feat, motion)
 
-    def render_denoised(self, seed=42, feature_samples=4, **params):
+    def render_denoised(self, seed=42, feature_samples=4, specular=0, **params):
         """A denoised frame: (denoised, raw, stats).  raw is the ordinary frame (= render(seed), bit for bit), rendered progressively; with an even
         spp >= 2 its preview at spp / 2 samples is the filter's rgb_half (the exact spp/2 frame, no second render), otherwise the filter runs without
         it.  The features take min(feature_samples, spp) samples.  params: denoise_params.  stats: the "render", "features" and "denoise" stats dicts,
-        and the filter's inputs "rgb_half" (None without it) and "features_frame"."""
+        and the filter's inputs "rgb_half" (None without it) and "features_frame".
+        specular=K > 0: the guides are render_features_specular(K, ...) instead (what mirrors and glass show, followed through at most K
+        steps); 0 is render_features."""
         self._need_dev()
         W, H = self.frame_size
         spp = self.samples_per_pixel()
@@ -1551,11 +1585,11 @@ class Scene:
             half = keep.get("half")
             if half is None:
                 raise FrayError(abi.E_HIP, "render_denoised: no preview at spp / 2 = %d samples" % (spp // 2))
-        feat, fst = self.render_features(min(int(feature_samples), spp), seed=seed, stats=True)
+        feat, fst = self._features_for(min(int(feature_samples), spp), seed, specular)
         out, dst = denoise(raw, feat, half, stats=True, **params)
         return out, raw, {"render": rst, "features": fst, "denoise": dst, "rgb_half": half, "features_frame": feat}
 
-    def render_denoised_split(self, seed=42, feature_samples=4, refine=None, max_count=None, passes=8, budget=None, **params):
+    def render_denoised_split(self, seed=42, feature_samples=4, refine=None, max_count=None, passes=8, budget=None, specular=0, **params):
         """A frame whose direct and indirect light are filtered apart: (denoised, raw, info).  The components of the frame's spp samples come from
         render_components with their noise estimates, each goes through denoise_signal with the feature frame (demodulate=0: the states' noise is
         in rgb's domain) and the two results are added in FP32.  raw = direct_rgb + indirect_rgb.  params: denoise_params, but demodulate=1 is
@@ -1564,7 +1598,7 @@ class Scene:
         refine=TOL: the components come from Scene.refine on a new pair of states instead (tolerance TOL, at most max_count samples in a pixel --
         required -- and at most `passes` passes); "render" is then refine's info, info gains "refine" (that info with "counts", the int32 [H, W]
         plane of samples held) and the features take min(feature_samples, the largest count) samples.  budget: refine's frame-wide sample
-        budget (it needs refine)."""
+        budget (it needs refine).  specular=K > 0: the guides are render_features_specular(K, ...), as in render_denoised."""
         if refine is None and max_count is not None:
             raise ValueError("render_denoised_split: max_count needs refine")
         if refine is None and budget is not None:
@@ -1585,7 +1619,7 @@ class Scene:
             held = state[0].count_plane()
             spp = max(int(held.max()), 1)
             extra["refine"] = dict(rst, counts=held)
-        feat, fst = self.render_features(min(int(feature_samples), spp), seed=seed, stats=True)
+        feat, fst = self._features_for(min(int(feature_samples), spp), seed, specular)
         d_out, dst = denoise_signal(d_rgb, d_noise, feat, stats=True, **params)
         i_out, ist = denoise_signal(i_rgb, i_noise, feat, stats=True, **params)
         return d_out + i_out, d_rgb + i_rgb, dict({"render": rst, "features": fst, "denoise_direct": dst, "denoise_indirect": ist, "direct": d_out,
@@ -1632,7 +1666,7 @@ class Scene:
         return rgb, st.as_dict()
 
     def render_sequence(self, cameras, seed=42, feature_samples=4, temporal=None, edit=None, split=False, temporal_direct=None, temporal_indirect=None,
-                        change_samples=0, change=None, boost=None, **denoise_params):
+                        change_samples=0, change=None, boost=None, specular=0, **denoise_params):
         """A generator over a fly-through of a static scene with temporal accumulation (include/frayhip.h "temporal accumulation"): for the k-th
         abi.Camera of `cameras` it sets the view, renders the feature frame and the frame with seed + k (equal seeds would accumulate the same
         noise every frame), accumulates onto the previous frame's history reprojected into this view, runs the a-trous levels on the accumulated
@@ -1683,7 +1717,16 @@ class Scene:
         on the state that holds n; n <= spp <= add always), so that every pixel of raw is that pixel of render(seed + k) at add[pixel] samples bit for
         bit; temporal_accumulate(weight=, units_in=) accumulates raw.  info gains "counts" (int32 [H, W]: the samples each pixel of raw holds),
         "weight", "units" (the units plane that goes with "history") and "boost" (history_map's info).  target=1, max_units=1 gives every output bit
-        of the boost=None sequence.  target 8 and max_units 8 are a choice, not a measurement."""
+        of the boost=None sequence.  target 8 and max_units 8 are a choice, not a measurement.
+        specular: 0 runs exactly the launches above.  K > 0 (1 .. 8) renders every frame's guides with frayhip_render_features_specular_device
+        (max_bounces = K) in place of the first-hit pass and changes nothing else, with split= and boost= too: what a static mirror or pane of
+        glass shows is then reprojected as the geometry it is, under a moving camera.  With edit= it raises ValueError: motion frames carry
+        first hits only, so a moved object seen in a mirror cannot be followed (and change_samples=, which needs edit=, goes with it)."""
+        specular = int(specular)
+        if specular < 0 or specular > abi.SPECULAR_MAX_BOUNCES:
+            raise ValueError("render_sequence: specular must be 0 .. %d, got %d" % (abi.SPECULAR_MAX_BOUNCES, specular))
+        if specular and edit is not None:
+            raise ValueError("render_sequence: specular= is not offered with edit=: motion frames carry first hits only")
         bparams = None
         if boost is not None:                   # what the arguments alone decide, before the device is asked for
             if split:
@@ -1769,6 +1812,9 @@ class Scene:
                     motion = torch.empty((H, W, abi.MOTION_CHANNELS), dtype=torch.float32, device="cuda")
                     _check(lib.frayhip_render_features_motion_device(self._dev, C.byref(fr), n_feat, prev, len(prev), feat.data_ptr(),
                                                                      motion.data_ptr(), handle, C.byref(fst)))
+                elif specular:
+                    _check(lib.frayhip_render_features_specular_device(self._dev, C.byref(fr), n_feat, specular, feat.data_ptr(), None, handle,
+                                                                       C.byref(fst)))
                 else:
                     _check(lib.frayhip_render_features_device(self._dev, C.byref(fr), n_feat, feat.data_ptr(), handle, C.byref(fst)))
                 if split:

@@ -909,6 +909,44 @@ int  frayhip_render_features(frayhip_scene* s, const frayhip_frame* f, int n_sam
 int  frayhip_render_features_device(frayhip_scene* s, const frayhip_frame* f, int n_samples, float* d_feat,
                                     void* hip_stream, frayhip_stats* st);
 
+/* ---- specular feature frames (virtual-hit guides: mirrors and glass followed to the first non-specular hit) ------------------------------------
+ * frayhip_render_features with every camera sample followed through Refl / Refr nodes.  Reflection::spawnRay and Refraction::spawnRay draw no
+ * random number, so the chain behind a specular first hit is a function of the camera sample alone.  Same ten channels, so the filter and the
+ * temporal entries take such a frame as they take a first-hit one.  Per camera sample, (o0, d0) being the sample's ray as frayhip_render_features
+ * makes it: b = 0, T = 0.0 (FP64), M = I (3x3, FP64), no albedo product yet.
+ *   specular step  taken when the closest hit of the current ray is a node whose OWN shader is Refl or Refr (a Layered shader is never
+ *                  followed), b < max_bounces, and, for Refr, refract() did not return the zero vector (total internal reflection is not
+ *                  followed).  The hit is finished and bumped as a first hit is; the next ray is the one Reflection / Refraction::spawnRay
+ *                  returns (path-traced and Whitted frames alike: a glossy Refl is followed along its ideal direction); T = T + dist;
+ *                  A = mult (first step) or A * mult; for Refl, with m the hit's normal after the bump,
+ *                      u[i] = (M[i][0] m.x + M[i][1] m.y) + M[i][2] m.z,   M[i][j] = M[i][j] - (2 u[i]) m[j]          (M <- M (I - 2 m m^T));
+ *                  Refr leaves M alone; b = b + 1.
+ *   terminal       the first hit at which no step is taken: any node, a rect light, a miss, or a Refl / Refr hit at the bounce limit or under
+ *                  total internal reflection.
+ *                  b == 0        frayhip_render_features' row of this sample, bit for bit
+ *                  b > 0, hit    position = o0 + d0 * (T + dist) (FP64: the point at the path's length along the primary ray, the mirror image
+ *                                for one planar mirror), normal = M n with the row dots in the order above, n the normal the first-hit rule
+ *                                stores; albedo = A * the first-hit rule's albedo at this hit; depth = T + dist
+ *                  b > 0, miss   position, normal, depth 0 (the reflected sky takes no history, as a primary miss takes none);
+ *                                albedo = A * the environment's colour in the last direction
+ * Conversion to float, the sums in sample order and the division by n_samples are the feature channels'.  bounces (W*H floats, may be NULL in
+ * both entries): (float)b per sample, reduced the same way.
+ * max_bounces is 1 .. 8: it caps the loop; the kernel's state does not grow with it.
+ * A scene none of whose nodes carries a Refl / Refr shader (looked up per call, so frayhip_scene_update's edits count) takes
+ * frayhip_render_features' kernel and a zero plane.
+ * Everything else is frayhip_render_features' contract: buckets, untouched pixels outside them (both outputs), options and last-frame figures
+ * left alone, *st (with FRAYHIP_FRAME_STATS the work counters include every segment's search), the stream contract of the _device entry (both
+ * device pointers 4-byte aligned), maxTraceDepth < 0 gives zeros in both outputs.
+ * FRAYHIP_E_ARG, before the device is touched: what frayhip_render_features refuses, max_bounces outside 1 .. 8, a misaligned d_bounces,
+ *   feat and bounces overlapping.  FRAYHIP_E_UNSUPPORTED: as there.
+ * Not covered: motion frames through a chain (frayhip_render_features_motion carries first hits only, so a sequence under scene edits cannot
+ *   use these guides), Layered glass (no Fresnel branch is chosen), glossy lobes, unfolding the normal through a refraction. */
+#define FRAYHIP_SPECULAR_MAX_BOUNCES 8
+int  frayhip_render_features_specular(frayhip_scene* s, const frayhip_frame* f, int n_samples, int max_bounces, float* feat,
+                                      float* bounces /* W*H, may be NULL */, frayhip_stats* st);
+int  frayhip_render_features_specular_device(frayhip_scene* s, const frayhip_frame* f, int n_samples, int max_bounces, float* d_feat,
+                                             float* d_bounces /* W*H, may be NULL */, void* hip_stream, frayhip_stats* st);
+
 /* ---- motion frames (where the first hit was in the previous frame's state of the scene) ------------------------------------------------------
  * frayhip_render_features with a second output for temporal accumulation across frayhip_scene_update: prev_T (a HOST pointer in both entries,
  * n_prev records, n_prev = the uploaded scene's node count) holds the transforms the scene's nodes had when the previous frame was rendered.
@@ -930,7 +968,8 @@ int  frayhip_render_features_device(frayhip_scene* s, const frayhip_frame* f, in
  * FRAYHIP_E_ARG, before the device is touched: what frayhip_render_features refuses, a NULL prev_T or motion, n_prev != the node count, a
  *   non-finite double in prev_T, feat and motion overlapping.  FRAYHIP_E_UNSUPPORTED: as there.
  * Not covered: moved lights; shadows and reflections of moved objects (their pixels' first hits did not move, so they ghost as in a static
- *   sequence); motion blur; vertex edits (frayhip_scene_update does not take them).  Moved lights and those shadows and reflections are what
+ *   sequence; a specular feature frame follows STATIC reflections under camera motion, and has no motion frame); motion blur; vertex edits
+ *   (frayhip_scene_update does not take them).  Moved lights and those shadows and reflections are what
  *   a change frame detects (frayhip_change_frame, frayhip_temporal_accumulate_adaptive below): the motion frame itself still follows a node's
  *   own pixels only. */
 #define FRAYHIP_MOTION_CHANNELS 8   /* per pixel, two 16-byte rows: {P'.xyz, moved}, {n'.xyz, 0} */
@@ -1117,7 +1156,8 @@ int  frayhip_temporal_accumulate_split_device(int width, int height, const float
  * and seed before the edit and the same samples after it (two frayhip_render_samples or frayhip_render_components states); a pixel none of
  * whose paths met anything that changed holds the same bits in both, and its difference is exactly zero.  frayhip_change_frame turns such a
  * pair into a per-pixel change in [0, 1], and frayhip_temporal_accumulate_adaptive shortens the history where it is not zero -- which covers
- * moved lights and the shadows and reflections of moved objects, whose pixels pass every surface test.
+ * moved lights and the shadows and reflections of moved objects, whose pixels pass every surface test.  (Reflections of a static scene under
+ * a moving camera need no change frame: frayhip_render_features_specular gives their pixels the guides of what the mirror shows.)
  *
  * accum_before, accum_after: two FRAYHIP_ACCUM_CHANNELS states (W*H*4 floats) that hold the same samples of the same seed and view; the
  * caller's word is trusted.  The sample count cancels, so the states' sums are used as they stand.  motion: a motion frame or NULL.  FP32
@@ -1276,7 +1316,8 @@ int  frayhip_history_map_device(int width, int height, const float* d_feat, cons
 
 /* Not covered: SVGF's wider 3 x 3 retry when no bilinear tap counts, feeding a filtered level back into the history, moved lights and the
  * shadows and reflections of moved objects (only a pixel's own first hit is carried back: frayhip_render_features_motion), motion blur,
- * specular motion vectors (what a mirror shows moves with the camera while its first hit does not), learned
+ * specular motion vectors for moved objects (what a static mirror or pane of glass shows under a moving camera IS followed, by the virtual-hit
+ * guides of frayhip_render_features_specular; a moved object seen in a mirror, Layered glass and glossy lobes are not), learned
  * denoisers, frayhip_render_adaptive's frames (they return no variance; a state refined under a sample map does: "sample maps") and stereo frames,
  * and denoising across ranks (gather the frame and its features first: frayhip_gather_buckets takes a
  * channel count).  With a change frame the accumulation does shorten the history under a moved light and under the shadows and reflections of
