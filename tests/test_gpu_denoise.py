@@ -13,6 +13,7 @@ import pytest
 
 import denoise_ref
 from conftest import ROOT, open_scene
+from specular_ref import _checker
 
 pytestmark = pytest.mark.gpu
 
@@ -36,15 +37,6 @@ def _features_raw(fray, abi, s, n, seed=42, first=0, stride=1, chunk=0, out=None
     fr = abi.Frame(mode=abi.MODE_RENDER, seed=seed, bucket_first=first, bucket_stride=stride, spp_chunk=chunk)
     rc = fray.lib.frayhip_render_features(s._dev, C.byref(fr), n, feat.ctypes.data, None)
     return rc, feat
-
-
-def _checker(tex, u, v):
-    """CheckerTexture::sample (shading.cpp:40-46): int(floor(u * scaling) / 5.0), C++ truncation and remainder."""
-    ix = np.trunc(np.floor(u * tex.scaling) / 5.0).astype(np.int64)
-    iy = np.trunc(np.floor(v * tex.scaling) / 5.0).astype(np.int64)
-    even = np.fmod(ix + iy, 2) == 0
-    c1, c2 = np.array(tex.color1[:], np.float32), np.array(tex.color2[:], np.float32)
-    return np.where(even[..., None], c1, c2)
 
 
 # ---- 1. sample 0 of a plain Whitted frame, pinned ---------------------------------------------------------------------------------------------

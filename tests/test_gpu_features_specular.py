@@ -18,130 +18,8 @@ pytestmark = pytest.mark.gpu
 F32 = np.float32
 
 
-# ---- the chain, restated --------------------------------------------------------------------------------------------------------------------------
-# dev_math.hpp's operation order: dot = (x + y) + z, V3 * double componentwise, no contraction (numpy's ufuncs round every operation).
-def _dot(a, b):
-    return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
-
-
-def _faceforward(d, n):
-    return np.where((_dot(d, n) < 0)[:, None], n, -n)
-
-
-def _reflect(i, n):
-    return i + (2 * _dot(-i, n))[:, None] * n
-
-
-def _normalized(a):
-    m = 1.0 / np.sqrt((a[:, 0] * a[:, 0] + a[:, 1] * a[:, 1]) + a[:, 2] * a[:, 2])
-    return a * m[:, None]
-
-
-def _refract(i, n, ior):
-    """(direction, total internal reflection): refract() returns the zero vector there"""
-    ndi = _dot(i, n)
-    k = 1 - (ior * ior) * (1 - ndi * ndi)
-    tir = k < 0.0
-    with np.errstate(invalid="ignore"):
-        out = _normalized(ior[:, None] * i - (ior * ndi + np.sqrt(k))[:, None] * n)
-    return np.where(tir[:, None], 0.0, out), tir
-
-
-def _known_albedo(desc, hid):
-    """(albedo float32 [n, 3], known [n]) by the first-hit rule where this file can restate it: untextured Const / Lambert / Phong colour,
-    Refl / Refr mult, a light's colour, black at a miss (the scenes here have no environment)."""
-    alb, known = np.zeros((len(hid), 3), F32), np.zeros(len(hid), bool)
-    for i in np.unique(hid):
-        px = hid == i
-        if i >= 0:
-            sh = desc.shaders[desc.nodes[int(i)].shader]
-            if sh.kind in (3, 4):
-                alb[px] = np.array(sh.mult[:], F32)
-            elif sh.kind in (0, 1, 2) and sh.texture < 0:
-                alb[px] = np.array(sh.color[:], F32)
-            else:
-                continue
-        elif i <= -2:
-            alb[px] = np.array(desc.lights[-2 - int(i)].color[:], F32)
-        known[px] = True
-    return alb, known
-
-
-def walk_chain(s, K):
-    """Every pixel's chain of the integer-pixel camera rays (sample 0 of a Whitted frame without AA or DOF), at most K steps.  FP64 rows as the
-    header defines them, the terminal hit's id / ip / normal, the first hit's ip and normal, and the flags."""
-    desc = s.desc
-    assert not any(desc.nodes[i].bump_tex >= 0 for i in range(desc.n_nodes)), "this walk applies no bump"
-    o0, d0 = s.camera_rays()
-    H, W = o0.shape[:2]
-    n = H * W
-    o0, d0 = o0.reshape(n, 3), d0.reshape(n, 3)
-    kind = np.array([desc.shaders[desc.nodes[i].shader].kind for i in range(desc.n_nodes)])
-    mult = np.array([desc.shaders[desc.nodes[i].shader].mult[:] for i in range(desc.n_nodes)], F32)
-    ior = np.array([desc.shaders[desc.nodes[i].shader].ior for i in range(desc.n_nodes)], np.float64)
-    o, d = o0.copy(), d0.copy()
-    T, b = np.zeros(n), np.zeros(n, np.int32)
-    A = np.ones((n, 3), F32)
-    M = np.tile(np.eye(3), (n, 1, 1))
-    live = np.ones(n, bool)
-    pos, nrm, alb, depth = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3), F32), np.zeros(n)
-    alb_known, tir_end, limit_end = np.zeros(n, bool), np.zeros(n, bool), np.zeros(n, bool)
-    t_id, t_ip, t_n = np.full(n, -1, np.int32), np.zeros((n, 3)), np.zeros((n, 3))
-    m_ip, m_n = np.zeros((n, 3)), np.zeros((n, 3))
-    for _ in range(K + 1):
-        idx = np.nonzero(live)[0]
-        if not len(idx):
-            break
-        r = s.trace_rays(o[idx], d[idx], record=True)
-        hid, rec = r["hit_id"], r["hit_rec"]
-        dist, ip, nm = rec[:, 0], rec[:, 1:4], rec[:, 4:7]
-        node = np.where(hid >= 0, hid, 0)
-        spec = (hid >= 0) & np.isin(kind[node], (3, 4))
-        want = spec & (b[idx] < K)
-        di = d[idx]
-        nf = _faceforward(di, nm)
-        # Refraction::spawnRay: from outside 1 / ior, from inside ior / 1
-        my = np.where(_dot(nf, nm) > 0, 1.0 / ior[node], ior[node] / 1.0)
-        rd, tir = _refract(di, nf, my)
-        is_refr = kind[node] == 4
-        step = want & ~(is_refr & tir)
-        # the terminal rows
-        e = ~step
-        g = idx[e]
-        first, hit = b[g] == 0, hid[e] != -1
-        a0, known = _known_albedo(desc, hid[e])
-        Tn = T[g] + dist[e]
-        virt = o0[g] + d0[g] * Tn[:, None]
-        Mg, q = M[g], nm[e]
-        unf = np.stack([(Mg[:, i, 0] * q[:, 0] + Mg[:, i, 1] * q[:, 1]) + Mg[:, i, 2] * q[:, 2] for i in range(3)], axis=1)
-        z3 = np.zeros((len(g), 3))
-        pos[g] = np.where(hit[:, None], np.where(first[:, None], ip[e], virt), z3)
-        nrm[g] = np.where(hit[:, None], np.where(first[:, None], q, unf), z3)
-        depth[g] = np.where(hit, np.where(first, dist[e], Tn), 0.0)
-        alb[g] = np.where(first[:, None], a0, A[g] * a0)
-        alb_known[g] = known
-        tir_end[g] = (want & is_refr & tir)[e]
-        limit_end[g] = (spec & ~want)[e]
-        t_id[g], t_ip[g], t_n[g] = hid[e], ip[e], nm[e]
-        live[g] = False
-        # the steps
-        g = idx[step]
-        was_first = b[g] == 0
-        m_ip[g[was_first]], m_n[g[was_first]] = ip[step][was_first], nm[step][was_first]
-        A[g] = np.where(was_first[:, None], mult[node[step]], A[g] * mult[node[step]])
-        T[g] = T[g] + dist[step]
-        refl = kind[node[step]] == 3
-        m = nm[step]
-        Mg = M[g]
-        u = np.stack([(Mg[:, i, 0] * m[:, 0] + Mg[:, i, 1] * m[:, 1]) + Mg[:, i, 2] * m[:, 2] for i in range(3)], axis=1)
-        M[g] = np.where(refl[:, None, None], Mg - (2 * u)[:, :, None] * m[:, None, :], Mg)
-        o[g] = np.where(refl[:, None], ip[step] + nf[step] * 1e-6, ip[step] - nf[step] * 1e-6)
-        d[g] = np.where(refl[:, None], _reflect(di[step], m), rd[step])
-        b[g] = b[g] + 1
-    assert not live.any()
-    sh = lambda a: a.reshape((H, W) + a.shape[1:])
-    return dict(pos=sh(pos), nrm=sh(nrm), alb=sh(alb), alb_known=sh(alb_known), depth=sh(depth), b=sh(b), tir=sh(tir_end), limit=sh(limit_end),
-                t_id=sh(t_id), t_ip=sh(t_ip), t_n=sh(t_n), m_ip=sh(m_ip), m_n=sh(m_n), o0=sh(o0), d0=sh(d0))
+# the chain, restated: tests/specular_ref.py; walk_chain here is its walk over the integer-pixel camera rays, fed by the ray queries
+from specular_ref import _faceforward, walk_frame as walk_chain
 
 
 def _assert_pinned(s, ch, K, label):
